@@ -2,6 +2,7 @@
 """Headline benchmark: stereo pairs/s of the cost-volume aggregation hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--mode native|native-eager|...|train|train-graph]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,9 +12,11 @@ resident in HBM: BASELINE.json configs[1] = 540x960 run at 544x960 (as the refer
 D=192 (COARSE.NUM_SAMPLE=12), single frame, batch 1 per GPU, fp32, eval mode.  Ranks are independent replicas (stereo
 pairs shard with no data-path collective): value = pairs all ranks processed / max-over-ranks time ("weak" scaling).
 
-This file: arguments, rank set-up, THE TIMED REGION (`timed_steps`), the CPU baseline / parity leg (the only code
-outside tests/ that runs oracle/) and the one JSON line.  Every other measurement lives in benchlegs/ and runs AFTER
-the timed region:
+A plain run sets up, conditions and warms up the device, times the K steps, writes the last timed step's outputs if
+--dump-outputs is given, and prints the line.  Everything below runs only with --full, AFTER the timed region.
+
+This file: arguments, rank set-up, THE TIMED REGION (`timed_steps`), --dump-outputs, the CPU baseline / parity leg (the
+only code outside tests/ that runs oracle/) and the one JSON line.  Every other measurement lives in benchlegs/:
   roofline            benchlegs/k1.py        cost-volume build at the 1/4 level: algorithmic bytes over
                                              its mean duration by HIP events, against the 8.0 TB/s HBM peak AND against
                                              this board's fill ceiling measured in the same run
@@ -27,6 +30,9 @@ import json
 import os
 import sys
 import time
+import zlib
+
+import numpy as np
 
 # the one framework pass this script makes (BatchNorm calibration) should not trigger MIOpen's exhaustive solver search
 os.environ.setdefault("MIOPEN_FIND_MODE", "2")
@@ -77,11 +83,22 @@ def parse_args():
                     help="rounds 1-2 protocol: random weights with calibrated BatchNorm statistics on independent "
                          "smooth-noise features instead of the committed trained checkpoint on a planted-disparity "
                          "scene (same shapes, kernels and speed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline, after the timed region: roofline, "
+                         "one_pass_at_a_time, f32_mfma_only, sequence, training, cpu_baseline and parity (the "
+                         "options below switch single ones off); off by default: a plain run times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (disparities, costs, samples, "
+                         "offsets, ranges, temporal state) as DIR/<name>.npy, float32 / float64, at most 64 MB in all "
+                         "(larger arrays cut to a fixed, seeded sample of their elements), with DIR/dump_index.json "
+                         "(shapes, samples, inputs); that step always runs on buffer set 0, the same seeded frame "
+                         "whatever the timing; rank 0 only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-all-cores", action="store_true",
                     help="cpu_baseline: also one pass on ALL host threads (slow: oversubscribed)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the `training` and `sequence` objects of the default line")
+                    help="skip the `f32_mfma_only`, `training` and `sequence` objects of the --full line")
     ap.add_argument("--calibrate", action="store_true",
                     help="also launch the known-size read / fill / copy streams of csrc/calib.hip (1 GiB each) once, "
                          "so that a PMC pass of this command carries its own FETCH_SIZE / WRITE_SIZE calibration "
@@ -156,16 +173,17 @@ def condition_device(step, bound_s):
 
 def timed_steps(step, warmup, steps, dist, dev):
     """THE TIMED REGION: W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize on both sides.
-    -> seconds (MAX over ranks)."""
+    -> (seconds (MAX over ranks), what the last timed step returned)."""
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -175,7 +193,56 @@ def timed_steps(step, warmup, steps, dist, dev):
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    return elapsed
+    return elapsed, last
+
+
+DUMP_LIMIT = 64 * 10 ** 6      # bytes, all files of --dump-outputs together (.npy headers included)
+
+
+def _named_arrays(name, obj, acc):
+    """Tensors (and numbers) of a step's result, depth first, as (name, float32 | float64 array)."""
+    if torch.is_tensor(obj):
+        t = obj.detach().cpu()
+        acc.append((name, t.numpy() if t.dtype in (torch.float32, torch.float64)
+                    else t.to(torch.float32 if t.is_floating_point() else torch.float64).numpy()))
+    elif isinstance(obj, (list, tuple)):
+        for i, o in enumerate(obj):
+            _named_arrays("%s_%d" % (name, i), o, acc)
+    elif isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            _named_arrays("%s_%s" % (name, "".join(c if c.isalnum() else "_" for c in str(k))), obj[k], acc)
+    elif isinstance(obj, (bool, int, float)):
+        acc.append((name, np.asarray(obj, dtype=np.float64)))
+    return acc
+
+
+def dump_outputs(out, path, about):
+    """--dump-outputs: what one timed step returned, DIR/<name>.npy per array, and DIR/dump_index.json (`about` = the
+    step's inputs; per array its shape, dtype and how many elements were kept).  Over DUMP_LIMIT in all, the budget is
+    shared out smallest array first and an array beyond its share keeps a fixed, seeded sample of its flattened
+    elements: np.sort(np.random.default_rng(seed).choice(size, kept, replace=False)), seed = zlib.crc32(name), the same
+    for every run of the same arguments.  -> {name: index entry}"""
+    names = ("disps", "costs", "samples", "offsets", "ranges", "info")
+    arrays = []
+    for n, o in zip(names, out if isinstance(out, (list, tuple)) else (out,)):
+        _named_arrays(n, o, arrays)
+    os.makedirs(path, exist_ok=True)
+    left, written = DUMP_LIMIT - 256 * len(arrays) - 65536, {}   # room for each .npy header and the index
+    arrays.sort(key=lambda na: na[1].nbytes)
+    for i, (name, arr) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        flat = arr.reshape(-1)
+        entry = dict(shape=list(arr.shape), dtype=str(arr.dtype), size=int(arr.size))
+        if arr.nbytes > share:
+            seed = zlib.crc32(name.encode())
+            flat = flat[np.sort(np.random.default_rng(seed).choice(flat.size, share // arr.itemsize, replace=False))]
+            entry.update(sampled=True, kept=int(flat.size), seed=seed)
+        np.save(os.path.join(path, name + ".npy"), flat if flat.size != arr.size else arr)
+        left -= flat.nbytes
+        written[name] = entry
+    with open(os.path.join(path, "dump_index.json"), "w") as f:
+        json.dump(dict(about, arrays=written), f, indent=1, sort_keys=True)
+    return written
 
 
 def cpu_baseline(sd, inputs_cpu, budget_s=20.0, all_cores=False):
@@ -248,6 +315,8 @@ def main():
     rank, world, dev, dist = init_ranks(a)
     seed = synth.SEED0 + 2                      # config index 2
     if a.mode in ("train", "train-graph"):
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of the inference modes; --mode %s has none" % a.mode)
         return trainlegs.train_mode_main(a, dev, rank, world, dist, seed)
 
     # ---- workload: weights, inputs, engine
@@ -297,18 +366,32 @@ def main():
             step()
         torch.cuda.synchronize()
         conditioning = condition_device(step, a.condition_s) if a.condition_s > 0 else None
-        elapsed = timed_steps(step, a.warmup, a.steps, dist, dev)
-        # (not timed) `out` below = the pass on buffer set 0, the frame the oracle is run on
-        while calls[0] % depth != 0:
+        # untimed: the conditioning's pass count depends on timing; line the buffer sets up so that the last timed step
+        # always runs on set 0 (`inputs`: the frame --dump-outputs writes and the oracle is run on)
+        while (calls[0] + a.warmup + a.steps - 1) % depth != 0:     # the last timed step is call calls + W + N - 1
             step()
-        out = step()
         torch.cuda.synchronize()
-        launched = list(k1.calls)        # what the pipeline itself launched (before the measurements below add keys)
+        elapsed, last = timed_steps(step, a.warmup, a.steps, dist, dev)
+        if a.dump_outputs and rank == 0:
+            # before any further pass: a pipelined call's outputs stay valid for depth - 1 further calls only
+            written = dump_outputs(last, a.dump_outputs, dict(
+                buffer_set=(calls[0] - 1) % depth, input_seed=seed + rank, batch=a.batch, mode=mode,
+                weights_and_inputs="planted" if planted else "random"))
+            print("dump-outputs: %d arrays -> %s" % (len(written), a.dump_outputs), file=sys.stderr, flush=True)
+        del last
+        roofline = None
+        if a.full:
+            # (not timed) `out` below = the pass on buffer set 0, the frame the oracle is run on
+            while calls[0] % depth != 0:
+                step()
+            out = step()
+            torch.cuda.synchronize()
+            launched = list(k1.calls)    # what the pipeline itself launched (before the measurements below add keys)
 
-        # ---- everything below is outside the timed region
-        # ------------------------------------------------------------------------
-        roofline = k1legs.run(k1, launched, runner, dev, a.batch, max(a.steps, 200), mode.startswith("native"),
-                              ceilings=not a.calibrate) if rank == 0 else None
+            # ---- --full: everything below is outside the timed region
+            # ----------------------------------------------------------------
+            roofline = k1legs.run(k1, launched, runner, dev, a.batch, max(a.steps, 200), mode.startswith("native"),
+                                  ceilings=not a.calibrate) if rank == 0 else None
         if a.calibrate and rank == 0:
             from temporalstereo_amd import _lib
             nbytes = 1 << 30
@@ -319,8 +402,8 @@ def main():
             torch.cuda.synchronize()
             del ca, cb
 
-    native_extras = mode == "native" and not a.no_extras
-    one = extras.one_pass_at_a_time(net, inputs, a.steps, a.batch) if (depth > 1 and rank == 0) else None
+    native_extras = a.full and mode == "native" and not a.no_extras
+    one = extras.one_pass_at_a_time(net, inputs, a.steps, a.batch) if (a.full and depth > 1 and rank == 0) else None
     f32_only = extras.f32_mfma_only(net, inputs, a.steps, a.batch, depth) if (native_extras and rank == 0) else None
     concurrent = None
     if a.inflight > 1 and mode == "native":
@@ -352,8 +435,7 @@ def main():
                                   run_hw=[RUN_H, RUN_W], max_disp=MAX_DISP, batch_per_gpu=a.batch,
                                   parallelism="replicas x%d" % world, exec_mode=mode, frames_in_flight=depth,
                                   input_buffer_sets=depth, weights_and_inputs=weights,
-                                  conv_arithmetic=_CONV_ARITHMETIC),
-                      roofline=roofline)
+                                  conv_arithmetic=_CONV_ARITHMETIC))
         if mode == "native" and depth > 1:
             # disclosed with the passes in flight: the streams a pass is cut over (NativeAggregator._stages_for)
             streams = {id(v) for v in runner.net._stages_for(a.batch).values() if v is not None}
@@ -364,11 +446,12 @@ def main():
             result["config"]["training_hipgraph_ms_per_step"] = (training.get("hipgraph") or {}).get("ms_per_step")
         if one is not None:
             result["config"]["one_pass_at_a_time_pairs_per_s"] = one.get("value")
-        for key, val in (("conditioning", conditioning), ("one_pass_at_a_time", one), ("f32_mfma_only", f32_only),
-                         ("concurrent_pairs", concurrent), ("training", training), ("sequence", sequence)):
+        for key, val in (("roofline", roofline), ("conditioning", conditioning), ("one_pass_at_a_time", one),
+                         ("f32_mfma_only", f32_only), ("concurrent_pairs", concurrent), ("training", training),
+                         ("sequence", sequence)):
             if val is not None:
                 result[key] = val
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # the oracle with the very same weights (incl. BatchNorm statistics) on the very same inputs (buffer set
             # 0): timed as the CPU baseline, and its first pass is the parity reference for `out`
             sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}

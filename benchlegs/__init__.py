@@ -7,5 +7,5 @@ here:
     copy
                  ceilings, the beyond-the-Infinity-Cache launch, the contracted first layer (`roofline.fused`)
     extras.py    one pass at a time, the f32-only engine, concurrent lanes, temporal sequences
-    training.py  the data-parallel training step (`--mode train | train-graph`, `training` of the default line)
+    training.py  the data-parallel training step (`--mode train | train-graph`, `training` of the --full line)
 """

@@ -1,5 +1,5 @@
 """The data-parallel TRAINING step of the same path (temporalstereo_amd.train.TrainStep), BASELINE configs[1] geometry,
-T = 2: `python bench.py --mode train | train-graph [--gpus N]`, and the `training` object of the default line.
+T = 2: `python bench.py --mode train | train-graph [--gpus N]`, and the `training` object of the --full line.
 Reference: TemporalStereo.training_step + multi_frame_forward (projects/TemporalStereo/TemporalStereo.py:130-168,
 :250-280) under pl.Trainer(strategy='ddp', sync_batchnorm=True, gradient_clip_val=0.1) (dist_train.py:82-96)."""
 import json

@@ -2,13 +2,14 @@
 """HBM traffic of the judged K1 launch from two rocprofv3 PMC passes of the BENCH command (FETCH_SIZE and WRITE_SIZE cannot share
 a pass: TCC has 4 slots, FETCH_SIZE takes 3, WRITE_SIZE 2 -- MI355X_MICROARCH.md "rocprofv3 PMC slots"):
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d gpurun_out/pmc_fetch -o f -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --calibrate
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace -d gpurun_out/pmc_write -o w -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --calibrate
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d <out>/pmc_fetch -o f -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --calibrate
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace -d <out>/pmc_write -o w -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --calibrate
     python tools/k1_traffic.py <fetch.db> <write.db> > profiles/rNN_k1_hbm_traffic_pmc.json
 
 Corrections as the guide prescribes (HBM section): on gfx950 FETCH_SIZE tallies the 128-byte requests of wide coalesced reads at
 64 bytes -> x2; WRITE_SIZE x1.  Both factors are re-measured in the same passes on bench.py's --calibrate streams (csrc/calib.hip:
-a read, a fill and a copy of a known 1 GiB) and reported next to the result."""
+a read, a fill and a copy of a known 1 GiB) and reported next to the result.  `--full`: the complete op `ts_block_cost_sampled_fwd`
+is launched by the roofline leg, which a plain bench run leaves out."""
 import json
 import sqlite3
 import sys
