@@ -188,6 +188,22 @@ int ts_disp_smooth_l1_bwd(const float* est, const float* gt, const float* grad_l
                           int B, int h, int w, int Hg, int Wg, float max_disp, float start_disp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation of the returned disparities (validation_step / test_step, projects/TemporalStereo/TemporalStereo.py:170-214).
+ * ts_disp_metrics_fwd: log_metric (:463-486) of up to four levels in one call -- calc_error (data/evaluation/pixel_error.py:6-71)
+ *   of each level and, when gt_right is given, do_occlusion_evaluation (data/evaluation/eval.py:45-105).
+ *   est<l> [B,1,h<l>,w<l>] (n_est = 1..4; unused pointers may be NULL); a level smaller or larger than the ground truth is read
+ *   through F.interpolate(est * Wg / w, (Hg,Wg), bilinear, align_corners) (:183) evaluated in registers.
+ *   gt / gt_right [B,1,Hg,Wg]; gt_right NULL: only the `all` split (occ / noc written as 0); else Hg, Wg >= 2.
+ *   flags bit0: lb given (valid needs gt > lb), bit1: ub given (gt < ub).
+ *   out [n_est][3][5] fp32: split all / occ / noc x {1px, 2px, 3px, 5px, epe} (percent; 0 when no pixel is valid).
+ *   Counts are exact integers, sums fp64 in a fixed order: bit-identical from run to run.  Two launches, no synchronisation.
+ * ---------------------------------------------------------------------------------------- */
+size_t ts_disp_metrics_workspace_bytes(int B, int Hg, int Wg);
+int ts_disp_metrics_fwd(const float* est0, const float* est1, const float* est2, const float* est3, int n_est, int h0, int w0,
+                        int h1, int w1, int h2, int w2, int h3, int w3, const float* gt, const float* gt_right, int B, int Hg,
+                        int Wg, float lb, float ub, int flags, float* out, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K4  disparity regression.  cost / sample / offset are [B,D,H,W].
  * ts_topk_softargmax_*: predict_disp()  .../aggregation/TemporalStereo/coarse.py:69-75
  *   (== fine.py:70-76, precise.py:61-67): top-k (1 <= k <= 8, ties: lowest index first) ->

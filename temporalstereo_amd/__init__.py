@@ -14,3 +14,5 @@ from .registry import (AGGREGATION_REGISTRY, PREDICTION_REGISTRY, build_aggregat
 from .aggregation import (TEMPORALSTEREO, CoarseAggregation, FineAggregation, PreciseAggregation)  # noqa: F401
 from .prediction import SOFTARGMIN, ARGMIN  # noqa: F401
 from . import temporal  # noqa: F401
+from . import evaluation  # noqa: F401
+from .evaluation import validation_metrics  # noqa: F401

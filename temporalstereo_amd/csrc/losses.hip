@@ -17,9 +17,14 @@
 //   smooth_l1_bwd     one lane per LOW-resolution pixel gathers the full-resolution pixels whose bilinear footprint contains it
 //                     (the adjoint of the rescale without atomics: deterministic)
 // All HBM/latency-bound and tiny next to K1/K3; what they remove is ~40 framework launches per training step.
+#include "bilinear.hpp"
 #include "ts_common.hpp"
 
 namespace {
+
+using ts::ac_scale;
+using ts::lin_src;
+using ts::rescaled;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -137,24 +142,6 @@ wasserstein_bwd_kernel(const float* __restrict__ cost, const float* __restrict__
   }
 }
 
-// align_corners bilinear source of one output index (the arithmetic of ts_resize_bilinear_fwd)
-__device__ __forceinline__ void lin_src(float scale, int dst, int in_size, int& i0, int& i1, float& l1) {
-  const float s = scale * static_cast<float>(dst);
-  i0 = static_cast<int>(s);
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = s - static_cast<float>(i0);
-}
-
-__device__ __forceinline__ float rescaled(const float* __restrict__ e, int h, int w, float sh, float sw, float vs, int oy, int ox) {
-  int y0, y1, x0, x1;
-  float ly, lx;
-  lin_src(sh, oy, h, y0, y1, ly);
-  lin_src(sw, ox, w, x0, x1, lx);
-  const float top = (1.f - lx) * e[y0 * w + x0] + lx * e[y0 * w + x1];
-  const float bot = (1.f - lx) * e[y1 * w + x0] + lx * e[y1 * w + x1];
-  return ((1.f - ly) * top + ly * bot) * vs;
-}
-
 __global__ void __launch_bounds__(256)
 smooth_l1_fwd_kernel(const float* __restrict__ est, const float* __restrict__ gt, float* __restrict__ partial_sum,
                      float* __restrict__ partial_cnt, int B, int h, int w, int Hg, int Wg, float sh, float sw, float vs, float lo,
@@ -245,10 +232,6 @@ smooth_l1_bwd_kernel(const float* __restrict__ est, const float* __restrict__ gt
   }
   for (int o = lpp >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
   if (sub == 0) gest[i] = G * vs * acc;
-}
-
-inline float ac_scale(int in_size, int out_size) {
-  return out_size > 1 ? static_cast<float>(in_size - 1) / static_cast<float>(out_size - 1) : 0.f;
 }
 
 inline int blocks_for(long long n, int per_block) { return static_cast<int>((n + per_block - 1) / per_block); }

@@ -544,6 +544,169 @@ def backbone_memory_cases(M):
         save(name, **arrs)
 
 
+def _reference_evaluation():
+    """The reference's calc_error / do_evaluation / do_occlusion_evaluation (architecture/data/evaluation).  The package's
+    __init__ imports the dataset readers (cv2 and more, absent from this image), so pixel_error.py is loaded by file path and
+    eval.py's two functions are taken from its syntax tree and compiled as they are (nothing is copied)."""
+    import ast
+    import importlib.util
+    import warnings
+    from architecture.modeling.layers import inverse_warp
+    base = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "data", "evaluation")
+    spec = importlib.util.spec_from_file_location("_ref_pixel_error", os.path.join(base, "pixel_error.py"))
+    pe = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(pe)
+    path = os.path.join(base, "eval.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    fns = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in ("do_evaluation", "do_occlusion_evaluation")]
+    ns = {"torch": torch, "warnings": warnings, "inverse_warp": inverse_warp, "calc_error": pe.calc_error}
+    exec(compile(ast.Module(body=fns, type_ignores=[]), path, "exec"), ns)
+    return pe.calc_error, ns["do_evaluation"], ns["do_occlusion_evaluation"], inverse_warp
+
+
+EVAL_KEYS = ('1px', '2px', '3px', '5px', 'epe')
+EVAL_MARGIN = 1e-3
+
+
+def eval_cases(M):
+    """Disparity evaluation (validation_step / test_step, projects/TemporalStereo/TemporalStereo.py:170-214): the reference's own
+    calc_error, do_evaluation and do_occlusion_evaluation on seeded ground truths and estimates, and log_metric (:463-486) composed
+    from them after validation_step's F.interpolate (:183), with LightningModule (pytorch_lightning) left out.
+
+    Inputs are stored compactly: gt_left / gt_right as int16 in units of 1/128 px, the full-resolution estimate as gt_left plus an
+    int8 offset in units of 1/16 px, shifted by 1/32 (so its error is never an integer), the low-resolution levels as float32.
+    gt_left is then nudged (deterministically, in steps of 3/128, never a zero hole of a sparse map) until no pixel is within
+    1e-3 of a decision threshold of any quantity that is computed rather than read: |e| vs 1/2/3/5 of every level and every
+    valid pixel, |warp - gt| vs 1 and |warp| vs 1e-6 (an exact 0 is exact), gt vs lb/ub (an exact 0 hole is exact).  The
+    smallest margin achieved is stored as `margin`."""
+    import torch.nn.functional as F
+    calc_error, do_evaluation, do_occlusion_evaluation, inverse_warp = _reference_evaluation()
+    q = lambda hw: [hw, (hw[0] // 4, hw[1] // 4), (hw[0] // 4, hw[1] // 4), (hw[0] // 8, hw[1] // 8)]
+    cases = {"eval_dense": dict(hw=(64, 128), lb=0, ub=192, sparse=0.0, band=False, out_of_range=True),
+             "eval_sparse": dict(hw=(64, 128), lb=0, ub=192, sparse=0.6, band=False),
+             "eval_none_valid": dict(hw=(64, 128), lb=0, ub=192, sparse=1.0, band=False),
+             "eval_no_bounds": dict(hw=(64, 128), lb=None, ub=None, sparse=0.0, band=True),
+             "eval_ragged": dict(hw=(50, 70), lb=0, ub=192, sparse=0.0, band=True, levels=[(50, 70), (13, 18), (13, 18), (7, 9)]),
+             "eval_nonfinite": dict(hw=(64, 128), lb=0, ub=192, sparse=0.0, band=False, nonfinite=True),
+             "eval_occlusion": dict(hw=(64, 128), lb=0, ub=192, sparse=0.0, band=True)}
+    for ci, (name, c) in enumerate(cases.items()):
+        seed = synth.SEED0 + 500 + ci
+        B = 2
+        H, W = c["hw"]
+        levels = c.get("levels", q((H, W)))
+        lb, ub = c["lb"], c["ub"]
+        # a smooth left disparity, and the right view's disparity consistent with it (x_r = x_l - d(x_l), by fixed point)
+        ph = synth.uniform(seed, "phase", (B, 1, 1, 1), 0.0, 6.283)
+        yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+        d = lambda y, x: 9.0 + 5.0 * y / H + 3.0 * np.sin(2 * np.pi * x / W + ph) + 1.5 * np.cos(2 * np.pi * y / H + 0.5 * ph)
+        dl = d(yy, xx)
+        xl = xx + d(yy, xx)
+        for _ in range(30):
+            xl = xx + d(yy, xl)
+        dr = d(yy, xl)
+        if c["band"]:       # a foreground object seen only in the right view: the left pixels that land on it are occluded
+            x0 = W // 3
+            dr[..., :, x0:x0 + max(4, W // 8)] += 15.0
+        if c.get("out_of_range"):
+            r = synth.uniform(seed, "oor", (B, 1, H, W))
+            dl = np.where(r < 0.03, 200.0, np.where(r > 0.97, -1.0, dl))
+        ql = np.round(dl * 128).astype(np.int64)
+        qr = np.round(dr * 128).astype(np.int64)
+        if c["sparse"] > 0:
+            ql = ql * (synth.uniform(seed, "keepl", (B, 1, H, W)) >= c["sparse"])
+            # the right map's holes are whole columns: inverse_warp's Y round trip can land a hair off the row (a tap weight
+            # of ~1e-7 on the next row), which next to a hole in the row itself would put |warp| at ~1e-6, on the threshold
+            qr = qr * (synth.uniform(seed, "keepr", (B, 1, 1, W)) >= c["sparse"])
+        ql = ql.astype(np.int16)
+        qr = qr.astype(np.int16)
+        off = np.clip(np.round(synth.normal(seed, "off", (B, 1, H, W), 40.0)), -127, 126).astype(np.int8)
+        lows = [synth.normal(seed, "noise%d" % li, (B, 1, h, w), 2.0 * w / W) for li, (h, w) in enumerate(levels[1:], 1)]
+        nonfinite = np.array([-1, -1], dtype=np.int64)
+        if c.get("nonfinite"):
+            nonfinite = np.array([(0 * H + 10) * W + 20, ((1 * 1) * H + 30) * W + 50], dtype=np.int64)   # NaN at [0,0,10,20], inf at [1,0,30,50]
+
+        def inputs(ql):
+            gl = ql.astype(np.float32) / np.float32(128)
+            gr = qr.astype(np.float32) / np.float32(128)
+            e0 = gl + (off.astype(np.float32) + np.float32(0.5)) / np.float32(16)
+            if nonfinite[0] >= 0:
+                e0.reshape(-1)[nonfinite[0]] = np.nan
+                e0.reshape(-1)[nonfinite[1]] = np.inf
+            ests = [e0]
+            for li, (h, w) in enumerate(levels[1:], 1):
+                iy = (np.arange(h) * H) // h
+                ix = (np.arange(w) * W) // w
+                ests.append((gl[:, :, iy][:, :, :, ix] * np.float32(w / W) + lows[li - 1]).astype(np.float32))
+            return gl, gr, ests
+
+        def margins(gl, gr, ests):
+            g, gtr = T(gl), T(gr)
+            full = [F.interpolate(T(e) * W / e.shape[-1], size=(H, W), mode='bilinear', align_corners=True) for e in ests]
+            valid = torch.ones_like(g, dtype=torch.bool)
+            if lb is not None:
+                valid &= g > lb
+            if ub is not None:
+                valid &= g < ub
+            relevant = valid if (lb is not None and lb >= 0) else torch.ones_like(valid)
+            m = torch.full_like(g, np.inf)
+            for f in full:
+                a = (g - f).abs()
+                for t in (1, 2, 3, 5):
+                    m = torch.where(valid & torch.isfinite(a), torch.minimum(m, (a - t).abs()), m)
+            warp = inverse_warp(gtr.clone(), -g.clone(), mode='disparity')
+            m = torch.where(relevant, torch.minimum(m, ((warp - g).abs() - 1.0).abs()), m)
+            m = torch.where(relevant & (warp != 0), torch.minimum(m, (warp.abs() - 1e-6).abs()), m)
+            for bnd in (lb, ub):
+                if bnd is not None:
+                    m = torch.where(g != 0, torch.minimum(m, (g - bnd).abs()), m)
+            occ = ((warp - g).abs() > 1.0) | (warp.abs() < 1e-6)
+            return m, full, occ, valid
+
+        for it in range(200):
+            gl, gr, ests = inputs(ql)
+            m, full, occ, valid = margins(gl, gr, ests)
+            bad = (m < EVAL_MARGIN).numpy() & (ql != 0)
+            if not bad.any():
+                break
+            ql = np.where(bad, ql + 3, ql).astype(np.int16)
+        margin = float(m.min()) if torch.isfinite(m.min()) else 1e9
+        if margin < EVAL_MARGIN:
+            idx = np.argwhere((m < EVAL_MARGIN).numpy())
+            print("BAD", name, idx[:5].tolist(), [float(m[tuple(i)]) for i in idx[:5]], [int(ql[tuple(i)]) for i in idx[:5]])
+        assert margin >= EVAL_MARGIN, (name, margin)
+        g, gtr, e0 = T(gl), T(gr), T(ests[0])
+        stack = lambda dct, prefix='': np.array([float(dct[prefix + k]) for k in EVAL_KEYS], dtype=np.float32)
+        ce = calc_error(e0, g, lb=lb, ub=ub)
+        de = do_evaluation(e0, g, lb, ub)
+        oe = do_occlusion_evaluation(e0, g, gtr, lb, ub)
+        # log_metric after validation_step's resize (TemporalStereo.py:183, :463-486), VAL.EVAL_DISPARITY_IDS = [0, 1, 2, 3]
+        whole = {}
+        for i in range(len(full)):
+            for k, v in do_evaluation(full[i], g, lb, ub).items():
+                whole['metric_disparity_{}/all_'.format(i) + k] = v
+            for k, v in do_occlusion_evaluation(full[i], g, gtr, lb, ub).items():
+                whole['metric_disparity_{}/'.format(i) + k] = v
+        lm = np.array([[[float(whole['metric_disparity_{}/{}_{}'.format(i, s, k)]) for k in EVAL_KEYS] for s in ("all", "occ", "noc")]
+                       for i in range(len(full))], dtype=np.float32)
+        gm = lambda mask: int((mask & (((g * mask) > lb) if lb is not None else True) & (((g * mask) < ub) if ub is not None else True)).sum())
+        n_valid = np.array([gm(torch.ones_like(occ)), gm(occ), gm(~occ)], dtype=np.int64)
+        arrs = dict(gt_left_q128=ql, gt_right_q128=qr, est0_off_q16=off, nonfinite_at=nonfinite,
+                    has_lb=int(lb is not None), lb=np.float32(lb if lb is not None else 0), has_ub=int(ub is not None),
+                    ub=np.float32(ub if ub is not None else 0), levels=np.array(levels, dtype=np.int64), margin=np.float64(margin),
+                    calc_error=stack(ce), do_evaluation=stack(de), occ=np.stack([stack(oe, 'occ_'), stack(oe, 'noc_')]),
+                    log_metric=lm, log_metric_keys=np.array(sorted(whole.keys())), n_valid=n_valid, nudge_rounds=it)
+        for li in range(1, len(ests)):
+            arrs["est%d" % li] = ests[li]
+        save(name, **arrs)
+        print("   margin %.4g after %d nudge rounds, N(all/occ/noc) = %s" % (margin, it, n_valid.tolist()))
+    with open(os.path.join(OUT, "PROVENANCE_eval.txt"), "w") as fh:
+        fh.write("eval_*.npz: tools/gen_golden.py --only-eval, torch %s CPU -- the reference's own calc_error / do_evaluation /\n"
+                 "do_occlusion_evaluation (architecture/data/evaluation) and log_metric composed from them after validation_step's\n"
+                 "F.interpolate, on seven seeded B=2 cases (dense, sparse, none valid, no bounds, ragged 50x70, NaN / inf estimate,\n"
+                 "occluder band); inputs stored quantised (int16 / int8), ground truth nudged to a 1e-3 threshold margin.\n"
+                 % torch.__version__)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -557,6 +720,9 @@ def main():
         return
     if "--only-losses" in sys.argv:
         loss_cases(M)
+        return
+    if "--only-eval" in sys.argv:
+        eval_cases(M)
         return
     if "--only-backbone-memory" in sys.argv:
         backbone_memory_cases(M)
@@ -577,6 +743,7 @@ def main():
     temporal_update_cases(M)
     loss_cases(M)
     backbone_memory_cases(M)
+    eval_cases(M)
     planted_cases(M)
     planted_gradient_case(M)
     aggregator_case("agg_tiny_single", TINY, synth.SEED0 + 100, 2, 96, 160, temporal=False, store_inputs=True)
