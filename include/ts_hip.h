@@ -204,6 +204,47 @@ int ts_disp_metrics_fwd(const float* est0, const float* est1, const float* est2,
                         int Wg, float lb, float ub, int flags, float* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rendering of a frame's disparities (projects/TemporalStereo/video_inference.py:169-227 `visualize`, TemporalStereo.py:488-622
+ * `log_image`; architecture/utils/visualization/disparity_colormap.py): colour maps and the 16-bit map, ready for one copy to the host.
+ * ts_disp_render_fwd: est [B,1,h,w] is read at the size of the target (Hg,Wg) through F.interpolate(est * Wg / w, (Hg,Wg), bilinear,
+ *   align_corners) (video_inference.py:182) evaluated in registers ((h,w) == (Hg,Wg): read as it is); gt [B,1,Hg,Wg] (NULL when no
+ *   selected output needs it).  flags selects the outputs and their form:
+ *     TS_RENDER_EST_COLOR / TS_RENDER_GT_COLOR  disp_to_color (:69-98) of est / gt into disp_color: [B,Hg,Wg,3], or with both set
+ *                            [B,2Hg,Wg,3], est above gt.  The maximum is each map's own (np.max, per image), the one of both maps
+ *                            with TS_RENDER_MAX_SHARED (video_inference.py:201-202), or max_disp[b] with TS_RENDER_MAX_GIVEN.
+ *                            TS_RENDER_CLIP clamps the colours to [0,1] (the reference's callers do; disp_map itself extrapolates).
+ *     TS_RENDER_ERR_CLASS    disp_err_to_color (:102-170) into err_class [B,Hg,Wg,3]
+ *     TS_RENDER_ERR_JET      disp_err_to_colorbar (:172-219) into err_jet [B,Hg,Wg,3]; with TS_RENDER_BAR [B,Hg+50,Wg,3], the legend
+ *                            below.  jet: the 256 x 3 fp32 table of the colour map (device pointer).
+ *     TS_RENDER_U16          (est * scale16) truncated toward zero into disp_u16 [B,Hg,Wg] uint16, saturated to [0,65535], NaN -> 0
+ *                            (video_inference.py:220)
+ *     TS_RENDER_UINT8        colour outputs are uint8, floor(255 v + 0.5) after a clamp to [0,1], NaN -> 0; else fp32
+ *     TS_RENDER_CHW          colour outputs are [B,3,rows,Wg] instead of [B,rows,Wg,3]
+ *   stats [B][TS_RENDER_STATS_FLOATS] (written when a maximum is taken from the data or the jet map is selected; needs workspace):
+ *     [0] max est  [1] max gt  [2] max of both  [3] max err, err = |est - gt| * (gt > 0)  [4] max(192, max err), 192 for a NaN
+ *     [8..13] / [16..21] minimum / maximum of err inside (0,1] (1,2] (2,4] (4,12] (12,16] (16,[4]]  (+inf / -inf: no member)
+ *     [24..29] the members' counts, int32 bit patterns.  Maxima propagate a NaN as np.max does.
+ *   Two launches (statistics + finish) are skipped when stats is not needed; then the colour launch.  No atomics, no
+ *   synchronisation; bit-identical from run to run.
+ * ---------------------------------------------------------------------------------------- */
+#define TS_RENDER_EST_COLOR 1
+#define TS_RENDER_GT_COLOR 2
+#define TS_RENDER_ERR_CLASS 4
+#define TS_RENDER_ERR_JET 8
+#define TS_RENDER_U16 16
+#define TS_RENDER_UINT8 32
+#define TS_RENDER_CHW 64
+#define TS_RENDER_BAR 128
+#define TS_RENDER_CLIP 256
+#define TS_RENDER_MAX_SHARED 512
+#define TS_RENDER_MAX_GIVEN 1024
+#define TS_RENDER_STATS_FLOATS 32
+size_t ts_disp_render_workspace_bytes(int B, int Hg, int Wg);
+int ts_disp_render_fwd(const float* est, const float* gt, const float* max_disp, const float* jet, int B, int h, int w, int Hg,
+                       int Wg, int flags, float scale16, void* disp_color, void* err_class, void* err_jet, void* disp_u16,
+                       float* stats, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K4  disparity regression.  cost / sample / offset are [B,D,H,W].
  * ts_topk_softargmax_*: predict_disp()  .../aggregation/TemporalStereo/coarse.py:69-75
  *   (== fine.py:70-76, precise.py:61-67): top-k (1 <= k <= 8, ties: lowest index first) ->

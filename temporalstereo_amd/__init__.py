@@ -16,3 +16,5 @@ from .prediction import SOFTARGMIN, ARGMIN  # noqa: F401
 from . import temporal  # noqa: F401
 from . import evaluation  # noqa: F401
 from .evaluation import validation_metrics  # noqa: F401
+from . import visualization  # noqa: F401
+from .visualization import render_frame  # noqa: F401

@@ -707,6 +707,250 @@ def eval_cases(M):
                  % torch.__version__)
 
 
+RENDER_CAP_SAME, RENDER_CAP_RESCALED = 0.01, 0.08
+
+
+def _reference_colormaps():
+    """The reference's disparity_colormap.py, loaded by file path (the package __init__ imports more than this image has).  Its
+    `plt` is wrapped so that the array handed to the colour map -- the re-valued error, the quantity that gets quantised -- can
+    be read back; the colours still come from matplotlib's own jet."""
+    import importlib.util
+    import types
+    os.environ.setdefault("MPLBACKEND", "Agg")
+    path = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "utils", "visualization", "disparity_colormap.py")
+    spec = importlib.util.spec_from_file_location("_ref_disparity_colormap", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    real = mod.plt
+    seen = []
+
+    def get_cmap(name):
+        cm = real.cm.get_cmap(name)
+
+        def call(x):
+            seen.append(np.array(x, copy=True))
+            return cm(x)
+        return call
+    mod.plt = types.SimpleNamespace(cm=types.SimpleNamespace(get_cmap=get_cmap), xticks=lambda **k: None)
+    return mod, seen, real
+
+
+def render_cases(M):
+    """Colour maps and the 16-bit map (architecture/utils/visualization/disparity_colormap.py, video_inference.py:169-227): the
+    reference's own disp_to_color / disp_err_to_color / disp_err_to_colorbar on seeded maps, once on the float32 inputs (what the
+    reference computes: the expected outputs) and once on the same values as float64 (how far its own rounding moves every
+    quantity that gets quantised).  Per quantity tau = 4 x that deviation, taken over the same-size cases and over the rescaled
+    case separately; a pixel within tau of a decision point is in the output's near-tie mask, where a test may accept the
+    adjacent class / index / code.  A mask may hold at most 1 % of a case's pixels (8 % in the rescaled case): asserted here.
+    Discrete outputs are stored as indices into the recorded tables (lossless), continuous ones as float32."""
+    import warnings
+    import matplotlib
+    import torch.nn.functional as F
+    warnings.filterwarnings("ignore")
+    ref, seen, plt = _reference_colormaps()
+    jet = plt.cm.get_cmap('jet')
+    jet_table = jet(np.arange(256))[:, :3]
+    class_bounds = np.array([0, 0.1875, 0.375, 0.75, 1.5, 3, 6, 12, 24, 48], dtype=np.float64) / 3.0
+    class_rgb = np.array([[49, 54, 149], [69, 117, 180], [116, 173, 209], [171, 217, 233], [224, 243, 248], [254, 224, 144],
+                          [253, 174, 97], [244, 109, 67], [215, 48, 39], [165, 0, 38]], dtype=np.float64) / 255.0
+    breaks = [0, 1, 2, 4, 12, 16]
+    # name: target size, estimate's size, batch, fraction of ground-truth zeros, error scale, options
+    cases = {"render_dense": dict(hw=(48, 80), B=1, sparse=0.0, err=6.0),
+             "render_sparse": dict(hw=(50, 78), B=1, sparse=0.7, err=6.0),
+             "render_rescaled": dict(hw=(56, 88), low=(14, 22), B=1, sparse=0.0, err=3.0),
+             "render_empty_range": dict(hw=(52, 92), B=1, sparse=0.0, err=6.0, hole=(12.0, 16.0)),
+             "render_small_errors": dict(hw=(48, 80), B=1, sparse=0.1, err=0.25, clamp=0.95),
+             "render_given_max": dict(hw=(49, 83), B=1, sparse=0.0, err=6.0, max_disp=60.0, below_zero=True),
+             "render_batch3": dict(hw=(30, 50), B=3, sparse=0.3, err=5.0),
+             "render_nonfinite": dict(hw=(40, 60), B=2, sparse=0.2, err=6.0, nonfinite=True)}
+    runs = {}
+    for ci, (name, c) in enumerate(cases.items()):
+        seed = synth.SEED0 + 800 + ci
+        B = c["B"]
+        H, W = c["hw"]
+        h, w = c.get("low", c["hw"])
+        yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+        amp = synth.uniform(seed, "amp", (B, 1, 1), 20.0, 70.0).astype(np.float64)
+        gt = 5.0 + amp * (0.55 + 0.3 * np.sin(2 * np.pi * xx / W + amp) + 0.15 * np.cos(2 * np.pi * yy / H))
+        gt = (np.round((gt + synth.uniform(seed, "gtn", (B, H, W), -0.5, 0.5)) * 16) / 16).astype(np.float32)      # 1/16 px: compresses
+        # errors spread over every range: a few large ones, many small ones
+        u = synth.uniform(seed, "eu", (B, H, W))
+        mag = np.where(u < 0.55, 1.0, np.where(u < 0.8, 4.0, np.where(u < 0.93, 12.0, 30.0))) * c["err"] / 6.0
+        e = synth.normal(seed, "en", (B, H, W), 1.0).astype(np.float64) * mag
+        if "clamp" in c:
+            e = c["clamp"] * np.tanh(e)              # every error below 1, without a pile of equal values at the bound
+        if "hole" in c:                               # no error inside (lo, hi]: pushed beyond hi
+            lo, hi = c["hole"]
+            e = np.where((np.abs(e) > lo - 0.2) & (np.abs(e) <= hi + 0.2), np.sign(e) * (hi + 0.2 + np.abs(e) - lo), e)
+        full = (gt.astype(np.float64) + e).astype(np.float32)
+        if c.get("below_zero"):
+            full = np.where(synth.uniform(seed, "neg", (B, H, W)) < 0.03, -full * 0.1, full).astype(np.float32)
+        gt = (gt * (synth.uniform(seed, "keep", (B, H, W)) >= c["sparse"])).astype(np.float32)
+        if (h, w) != (H, W):
+            iy, ix = (np.arange(h) * H) // h, (np.arange(w) * W) // w
+            est = (full[:, iy][:, :, ix] * np.float32(w / W)).astype(np.float32)
+        else:
+            est = full
+        if c.get("nonfinite"):
+            est = est.copy()
+            est[0, 10, 20] = np.nan          # on a valid pixel of image 0
+            est[1, 30, 50] = np.inf          # image 1: an infinite error, no NaN
+            gt[1, 30, 50] = max(gt[1, 30, 50], 7.0)
+        runs[name] = dict(c=c, est=est, gt=gt)
+
+    def rescale(est, H, W, dt):
+        t = torch.from_numpy(est).to(dt).unsqueeze(1)
+        if tuple(est.shape[-2:]) == (H, W):
+            return t[:, 0].numpy()
+        return F.interpolate(t * W / est.shape[-1], size=(H, W), mode='bilinear', align_corners=True)[:, 0].numpy()
+
+    def run(est_full, gt, max_disp):
+        """The reference on one image at one precision -> outputs and the quantised quantities."""
+        r = {}
+        with np.errstate(all="ignore"):
+            r["disp_color"] = ref.disp_to_color(est_full, max_disp)
+            r["cat_color"] = ref.disp_to_color(np.concatenate((est_full, gt), axis=0))
+            r["err_class"] = ref.disp_err_to_color(est_full, gt)
+            del seen[:]
+            r["err_jet"] = ref.disp_err_to_colorbar(est_full, gt, with_bar=True, cmap='jet')
+            r["x"], r["bar_x"] = seen[0], seen[1]
+            del seen[:]
+            assert np.array_equal(ref.disp_err_to_colorbar(est_full, gt), r["err_jet"][:-50], equal_nan=True)
+            r["u16_q"] = est_full * 256
+            # E of disp_err_to_color, restated (margins only; checked against the reference's classes below)
+            a, b = est_full * 255.0, gt * 255.0
+            E = np.abs(a - b)
+            ok = b > 0
+            tmp = np.zeros_like(b)
+            tmp[ok] = E[ok] / b[ok] / 0.05
+            r["E"] = np.minimum(E / 3.0, tmp)
+            r["E_valid"] = ok
+        return r
+
+    # first pass: both precisions of every case, the deviations per group
+    dev = {g: dict(E=0.0, x256=0.0, u16=0.0, c255=0.0, rescale=0.0) for g in ("same", "rescaled")}
+    for name, r in runs.items():
+        c = r["c"]
+        H, W = c["hw"]
+        grp = "rescaled" if "low" in c else "same"
+        f32, f64 = rescale(r["est"], H, W, torch.float32), rescale(r["est"], H, W, torch.float64)
+        r["full32"] = f32
+        r["grp"] = grp
+        r["r32"] = [run(f32[b], r["gt"][b], c.get("max_disp")) for b in range(c["B"])]
+        r["r64"] = [run(f64[b], r["gt"][b].astype(np.float64), c.get("max_disp")) for b in range(c["B"])]
+        d = dev[grp]
+        fin = lambda a, b: np.isfinite(a) & np.isfinite(b)
+        md = lambda a, b: float(np.abs(a.astype(np.float64) - b)[fin(a, b)].max()) if fin(a, b).any() else 0.0
+        d["rescale"] = max(d["rescale"], md(f32, f64))
+        for a, b in zip(r["r32"], r["r64"]):
+            d["E"] = max(d["E"], md(np.where(a["E_valid"], a["E"], 0), np.where(b["E_valid"], b["E"], 0)))
+            # the jet quantity is compared where both runs re-valued inside the same range (a pixel that changes range is a tie anyway)
+            d["x256"] = max(d["x256"], md(a["x"] * 256.0, b["x"] * 256.0) if np.abs(a["x"].astype(np.float64) - b["x"])[fin(a["x"], b["x"])].max(initial=0) < 0.05 else d["x256"])
+            d["u16"] = max(d["u16"], md(a["u16_q"], b["u16_q"]))
+            for k in ("disp_color", "cat_color"):
+                d["c255"] = max(d["c255"], md(np.clip(a[k], 0, 1) * 255.0, np.clip(b[k], 0, 1) * 255.0))
+    tau = {g: {k: 4.0 * v for k, v in d.items()} for g, d in dev.items()}
+
+    lines = ["render_*.npz: tools/gen_golden.py --only-render, numpy %s, matplotlib %s, torch %s CPU -- the reference's own disp_to_color /"
+             % (np.__version__, matplotlib.__version__, torch.__version__),
+             "disp_err_to_color / disp_err_to_colorbar (architecture/utils/visualization/disparity_colormap.py) on seeded maps; the rescaled",
+             "case goes through F.interpolate(est * W / w, align_corners=True) as video_inference.py:182 does.  Expected outputs: the float32",
+             "run.  Deviation = largest difference of a quantised quantity between that run and the same functions on float64 inputs",
+             "(the rescale included); tau = 4 x deviation; near-tie mask = pixels within tau of a decision point."]
+    for g in ("same", "rescaled"):
+        lines.append("group %-8s deviation: E %.3g, jet x*256 %.3g, disp*256 %.3g, 255*colour %.3g, rescaled map %.3g" %
+                     (g, dev[g]["E"], dev[g]["x256"], dev[g]["u16"], dev[g]["c255"], dev[g]["rescale"]))
+        lines.append("group %-8s tau:       E %.3g, jet x*256 %.3g, disp*256 %.3g, 255*colour %.3g" %
+                     (g, tau[g]["E"], tau[g]["x256"], tau[g]["u16"], tau[g]["c255"]))
+    save("render_tables", jet=jet_table, class_rgb=class_rgb, class_bounds=class_bounds,
+         versions=np.array([np.__version__, matplotlib.__version__, torch.__version__]))
+
+    for name, r in runs.items():
+        c, grp = r["c"], r["grp"]
+        t = tau[grp]
+        cap = RENDER_CAP_RESCALED if grp == "rescaled" else RENDER_CAP_SAME
+        B = c["B"]
+        H, W = c["hw"]
+        arrs = dict(est=r["est"][:, None], gt=r["gt"][:, None], group=grp, cap=np.float64(cap),
+                    has_max=int("max_disp" in c), max_disp=np.float32(c.get("max_disp", 0)),
+                    tau=np.array([t["E"], t["x256"], t["u16"], t["c255"]]), rescale_dev=np.float64(dev[grp]["rescale"]))
+        out = {k: [] for k in ("disp_color", "cat_color", "class_idx", "class_tie", "jet_idx", "jet_tie", "u16", "u16_tie",
+                               "disp_color_u8_tie", "cat_color_u8_tie", "stats", "count_slack")}
+        for a in r["r32"]:
+            out["disp_color"].append(a["disp_color"].astype(np.float32))
+            out["cat_color"].append(a["cat_color"].astype(np.float32))
+            # classes: the index of the reference's colour (255: black), checked against the restated E
+            img = a["err_class"]
+            idx = np.full(img.shape[:2], 255, dtype=np.uint8)
+            for k in range(10):
+                idx[np.all(img == class_rgb[k], axis=-1)] = k
+            assert np.all((idx == 255) == np.all(img == 0, axis=-1))
+            E = a["E"].astype(np.float64)
+            mine = np.where(a["E_valid"] & ~np.isnan(E), (E[..., None] >= class_bounds[1:]).sum(-1), 255)
+            assert np.array_equal(mine, idx), name
+            out["class_idx"].append(idx)
+            out["class_tie"].append(a["E_valid"] & (np.abs(E[..., None] - class_bounds[1:]) <= t["E"]).any(-1))
+            # jet: the index matplotlib took (x * 256 truncated, 1 -> 255), -1 for its `bad` colour
+            x = a["x"]
+            with np.errstate(all="ignore"):
+                xi = x.astype(np.float32) * np.float32(256)
+                ji = np.where(np.isnan(xi), -1, np.where(xi >= 256, 255, np.where(xi < 0, 0, xi.astype(np.int64)))).astype(np.int16)
+            full = a["err_jet"]
+            assert np.array_equal(np.where(ji[..., None] >= 0, jet_table[np.maximum(ji, 0)], 0.0), full[:-50]), name
+            bi = np.where(a["bar_x"][0] * 256 >= 256, 255, (a["bar_x"][0] * 256).astype(np.int64)).astype(np.int16)
+            assert np.array_equal(jet_table[bi], full[-1]), name
+            out["jet_idx"].append(ji)
+            with np.errstate(all="ignore"):
+                frac = np.abs(xi.astype(np.float64) - np.round(xi.astype(np.float64)))
+                out["jet_tie"].append(np.isfinite(xi) & (x != 0) & (frac <= t["x256"]))
+                q = a["u16_q"].astype(np.float64)
+                out["u16"].append(np.where(np.isnan(q), 0, np.clip(np.trunc(q), 0, 65535)).astype(np.uint16))
+                out["u16_tie"].append(np.isfinite(q) & (np.abs(q - np.round(q)) <= t["u16"]) & (t["u16"] > 0))
+                for k in ("disp_color", "cat_color"):
+                    v = np.clip(a[k], 0, 1) * 255.0
+                    out[k + "_u8_tie"].append(np.isfinite(v) & (np.abs(v - np.floor(v) - 0.5) <= t["c255"]))
+            # statistics: maxima and the ranges of the error, from the reference's own arithmetic (|est - gt| * valid in float32)
+            with np.errstate(all="ignore"):
+                est_full = a["u16_q"] / 256
+                g = r["gt"][len(out["stats"])]
+                err = np.abs(est_full - g) * (g > 0)
+                mx = err.max()
+                ups = breaks[1:] + [max(192, mx)]
+                st = [est_full.max(), g.max(), np.concatenate((est_full, g)).max(), mx]
+                mn_, mx_, cn_, sl_ = [], [], [], []
+                for lo, hi in zip(breaks, ups):
+                    m = (err > lo) & (err <= hi)
+                    mn_.append(err[m].min() if m.any() else np.inf)
+                    mx_.append(err[m].max() if m.any() else -np.inf)
+                    cn_.append(int(m.sum()))
+                    sl_.append(int(((np.abs(err - lo) <= 4 * dev[grp]["rescale"]) | (np.abs(err - hi) <= 4 * dev[grp]["rescale"])).sum())
+                               if grp == "rescaled" else 0)
+            out["stats"].append(np.array(st + mn_ + mx_ + cn_, dtype=np.float64))
+            out["count_slack"].append(np.array(sl_, dtype=np.int64))
+        bar = np.where(r["r32"][0]["bar_x"][0] * 256 >= 256, 255, (r["r32"][0]["bar_x"][0] * 256).astype(np.int64)).astype(np.int16)
+        arrs["bar_idx"] = bar
+        shares = {}
+        # disp_to_color with its own maximum is what cat_color's rows are (one map, one maximum): stored only where a maximum is given
+        for k in (("cat_color", "cat_color_u8_tie") if "max_disp" in c else ("disp_color", "disp_color_u8_tie")):
+            del out[k]
+        for k, v in out.items():
+            arrs[k] = np.stack(v)
+            if k.endswith("_tie"):
+                shares[k] = float(arrs[k].mean())
+                assert shares[k] <= cap, "%s: near-tie share of %s is %.4f, above the cap %.2f -- change the case" % (name, k, shares[k], cap)
+        arrs["tie_shares"] = np.array([shares[k] for k in sorted(shares)])
+        arrs["tie_names"] = np.array(sorted(shares))
+        save(name, **arrs)
+        sz = os.path.getsize(os.path.join(OUT, name + ".npz"))
+        assert sz <= 100 * 1024, (name, sz)
+        lines.append("%-20s %s B=%d %dx%d est %s  near-tie shares: %s" % (name, grp, B, H, W, tuple(r["est"].shape[-2:]),
+                     ", ".join("%s %.4f" % (k.replace("_tie", ""), shares[k]) for k in sorted(shares))))
+        lines.append("%-20s range counts %s" % ("", [a[-6:].astype(int).tolist() for a in out["stats"]]))
+    with open(os.path.join(OUT, "PROVENANCE_render.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -723,6 +967,9 @@ def main():
         return
     if "--only-eval" in sys.argv:
         eval_cases(M)
+        return
+    if "--only-render" in sys.argv:
+        render_cases(M)
         return
     if "--only-backbone-memory" in sys.argv:
         backbone_memory_cases(M)

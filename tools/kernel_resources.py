@@ -1,6 +1,7 @@
 """Register / scratch / occupancy table of every kernel in a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
 
     python tools/kernel_resources.py temporalstereo_amd/csrc/block_cost.hip [name filter]
+    python tools/kernel_resources.py temporalstereo_amd/csrc/render.hip          (the rendering kernels: no scratch)
 """
 import re
 import subprocess
