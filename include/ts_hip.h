@@ -245,6 +245,36 @@ int ts_disp_render_fwd(const float* est, const float* gt, const float* max_disp,
                        float* stats, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Preparation of the input frames (projects/TemporalStereo/video_inference.py:100-110 `read_image`, :135-140 `read_disparity`, :246-251;
+ * architecture/data/datasets/base.py:99-187 `do_transform`, :231-248 the intrinsics pyramid): uint8 frames in, the batch's tensors out.
+ * ts_frames_prepare_fwd: one launch for the whole batch and both eyes.
+ *   left / right  uint8 [B,Hs,Ws,3], or [B,3,Hs,Ws] with TS_PREPARE_CHW; right may be NULL (then color_r / color_aug_r must be).
+ *   color_*       fp32 [B,3,Hc,Wc] = byte / 255 (ToTensor), image b at color_* + b * color_stride (floats, >= 3 Hc Wc)
+ *   color_aug_*   fp32 [B,3,H,W] = ((byte / 255) - mean[c]) / std[c] (normalize; both divisions correctly rounded), then
+ *                 image b at color_aug_* + b * color_aug_stride (floats, >= 3 H W).  Any output pointer may be NULL, not all.
+ *   crop NULL, (H,W) == (Hs,Ws)   the values as they are; (Hc,Wc) = (Hs,Ws)
+ *   crop NULL, (H,W) != (Hs,Ws)   color_aug = F.interpolate(normalised, (H,W), bilinear, align_corners=True) (base.py:183,
+ *                                 video_inference.py:108), any ratio; normalised first, then interpolated; (Hc,Wc) = (Hs,Ws)
+ *   crop given                    DEVICE pointer to int32 [B,2] = (ch, cw) per image: rows ch..ch+H-1, columns cw..cw+W-1 of both
+ *                                 outputs (base.py:155); (Hc,Wc) = (H,W); needs H <= Hs, W <= Ws.  The origins are read by the
+ *                                 kernel, so the host cannot refuse them: an origin outside [0,Hs-H] x [0,Ws-W] is CLAMPED into it
+ *                                 (nothing is read out of bounds).
+ *   No workspace, no atomics; bit-identical from run to run.
+ * ts_intrinsics_pyramid_fwd: K_norm [B,4,4] fp32 (is_fp64 0) or fp64 (1), the "K / (h, w)" form -> K, inv_K fp32 [B,S,4,4]:
+ *   rows 0 / 1 times kw >> s / kh >> s (base.py:241-242), the inverse by cofactors in fp64 rounded once (the reference: np.linalg.pinv
+ *   in fp64, then .float()).  K_norm must be invertible and kh >> (S-1), kw >> (S-1) positive.
+ * ts_disp_u16_decode_fwd: raw uint16 [B,H,W] -> disp fp32 [B,1,H,W] = raw / scale where raw > 0 (exact for a power of two such as
+ *   256), else 0; valid (may be NULL) uint8 [B,1,H,W] = raw > 0.
+ * ---------------------------------------------------------------------------------------- */
+#define TS_PREPARE_CHW 1
+int ts_frames_prepare_fwd(const void* left, const void* right, int B, int Hs, int Ws, int flags, float mean0, float mean1,
+                          float mean2, float std0, float std1, float std2, int H, int W, const int* crop, float* color_l,
+                          float* color_r, long long color_stride, float* color_aug_l, float* color_aug_r,
+                          long long color_aug_stride, void* stream);
+int ts_intrinsics_pyramid_fwd(const void* K_norm, int is_fp64, int B, int kh, int kw, int S, float* K, float* inv_K, void* stream);
+int ts_disp_u16_decode_fwd(const void* raw, int B, int H, int W, float scale, float* disp, void* valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K4  disparity regression.  cost / sample / offset are [B,D,H,W].
  * ts_topk_softargmax_*: predict_disp()  .../aggregation/TemporalStereo/coarse.py:69-75
  *   (== fine.py:70-76, precise.py:61-67): top-k (1 <= k <= 8, ties: lowest index first) ->

@@ -18,3 +18,5 @@ from . import evaluation  # noqa: F401
 from .evaluation import validation_metrics  # noqa: F401
 from . import visualization  # noqa: F401
 from .visualization import render_frame  # noqa: F401
+from . import preprocess  # noqa: F401
+from .preprocess import prepare_frames, prepare_batch, intrinsics_pyramid, disp_from_uint16  # noqa: F401

@@ -1,0 +1,289 @@
+"""Input frames prepared on the device, on the kernels of csrc/preprocess.hip: uint8 frames in, the batch dictionary out.
+
+What the reference does on the host for every frame, restated on device tensors:
+  read_image                     projects/TemporalStereo/video_inference.py:100-110   ToTensor, normalize, F.interpolate
+  StereoDatasetBase.do_transform architecture/data/datasets/base.py:99-187            the same, "pad by resize" (:183) for evaluation,
+                                                                                      a crop window (:155) for training
+  StereoDatasetBase.__getitem__  base.py:231-248, video_inference.py:246-251          the ('K', s) / ('inv_K', s) pyramid
+  read_disparity                 video_inference.py:135-140                           (raw * (raw > 0)) / 256.0
+  the batch dictionary           video_inference.py:262-293                           `prepare_batch`
+
+Semantics kept from the reference:
+  - ('color', t, side) is byte / 255; ('color_aug', t, side) is ((byte / 255) - mean[c]) / std[c] in fp32 with correctly rounded
+    divisions, in that order, and only THEN resized (bilinear, align_corners=True).  Without a resize every value has the
+    reference's bits; a resized value is within the distance the reference's own fp32 run keeps from a float64 run;
+  - evaluation form (`size` alone): `color` keeps the source size, `color_aug` is resized, up or down (base.py:183);
+    training form (`size` and `crop`): both are the window [ch:ch+H, cw:cw+W] (base.py:155);
+  - the intrinsics of scale s multiply rows 0 / 1 of K_norm by kw // 2**s / kh // 2**s, integer division as written; (kh, kw) is
+    the final size for evaluation and the UN-cropped resolution for training (base.py:235-238: pass `k_size`);
+  - the 16-bit ground truth is raw / 256 where raw > 0, else 0.
+Differences, deliberate:
+  - inputs are uint8 GPU tensors, HWC (what a decoder hands over) or CHW, one image or a batch, and both eyes go through ONE launch;
+    results are device tensors; nothing here synchronises with the host, so a frame can be prepared inside a stream capture;
+  - a crop given as Python ints is refused when it leaves the image; given as an int32 device tensor it cannot be inspected
+    without a synchronisation and is CLAMPED into the image by the kernel instead;
+  - inv_K is the closed-form inverse evaluated in fp64 and rounded once (the reference: np.linalg.pinv): equal after rounding to
+    fp32 within one unit in the last place, and exactly 0 where pinv leaves a residue of ~1e-18;
+  - `disp_from_uint16` takes torch.uint16 where this torch has it, or int16 storage REINTERPRETED as unsigned (the bits a 16-bit
+    PNG reader hands over viewed as int16); an int32 tensor is accepted with its low 16 bits taken (a cast on the device);
+    the valid mask comes from the kernel (torch's comparisons do not cover uint16).
+Out of scope, on purpose: decoding files (PIL / cv2), ColorJitter / gamma (PIL-space uint8 operations with host random draws), the
+random occlusion patches of base.py:157-173, PFM / flow loaders.  Cropping an fp32 ground-truth map is a tensor slice.
+uint8 GPU tensors only: a CPU tensor raises, there is no CPU fallback.
+"""
+import math
+
+import torch
+
+from . import _lib
+from .functional import _stream
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)       # base.py:41
+IMAGENET_STD = (0.229, 0.224, 0.225)
+CHW = 1                                     # TS_PREPARE_CHW (include/ts_hip.h)
+_U16 = getattr(torch, "uint16", None)
+
+
+def _on_gpu(what, *tensors):
+    dev = None
+    for t in tensors:
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError("%s: expected a tensor, got %s" % (what, type(t).__name__))
+        if not t.is_cuda:
+            raise RuntimeError("temporalstereo_amd ops run on the GPU only (got a %s tensor of shape %s); "
+                               "there is deliberately no CPU fallback" % (t.device, tuple(t.shape)))
+        if dev is not None and t.device != dev:
+            raise RuntimeError("%s: tensors on %s and %s" % (what, dev, t.device))
+        dev = t.device
+    if dev is not None and dev.index != torch.cuda.current_device():
+        raise RuntimeError("%s: tensors on %s while the current device is cuda:%d" % (what, dev, torch.cuda.current_device()))
+    return dev
+
+
+def _frames(what, left, right, layout):
+    """uint8 images, one or a batch, of one shape -> (left, right, B, Hs, Ws, batched)"""
+    if layout not in ('HWC', 'CHW'):
+        raise ValueError("layout must be 'HWC' or 'CHW' (got %r)" % (layout,))
+    for t in (left, right):
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError("%s: expected a uint8 tensor, got %s" % (what, type(t).__name__))
+        if t.dtype != torch.uint8:
+            raise TypeError("%s: frames must be uint8 (got %s of shape %s)" % (what, t.dtype, tuple(t.shape)))
+        if t.dim() not in (3, 4):
+            raise ValueError("%s: a frame is [H,W,3] / [B,H,W,3] (HWC) or [3,H,W] / [B,3,H,W] (CHW), got shape %s" % (what, tuple(t.shape)))
+        if t.shape[-1 if layout == 'HWC' else -3] != 3:
+            raise ValueError("%s: three channels expected in layout %s, got shape %s" % (what, layout, tuple(t.shape)))
+        if t.numel() == 0:
+            raise ValueError("%s: empty batch of shape %s" % (what, tuple(t.shape)))
+    if right is not None and tuple(right.shape) != tuple(left.shape):
+        raise ValueError("%s: left has shape %s, right %s" % (what, tuple(left.shape), tuple(right.shape)))
+    _on_gpu(what, left, right)
+    batched = left.dim() == 4
+    B = left.shape[0] if batched else 1
+    Hs, Ws = (left.shape[-3], left.shape[-2]) if layout == 'HWC' else (left.shape[-2], left.shape[-1])
+    return _lib.contiguous(left), (None if right is None else _lib.contiguous(right)), B, Hs, Ws, batched
+
+
+def _three(name, v):
+    v = tuple(float(x) for x in v)
+    if len(v) != 3:
+        raise ValueError("%s must hold three numbers (got %d)" % (name, len(v)))
+    return v
+
+
+def _out_tensor(what, t, shape, dev):
+    if t.dtype != torch.float32 or not t.is_cuda or t.device != dev:
+        raise TypeError("%s: out must be fp32 on %s (got %s on %s)" % (what, dev, t.dtype, t.device))
+    if tuple(t.shape) != shape:
+        raise ValueError("%s: out has shape %s, %s expected" % (what, tuple(t.shape), shape))
+    _, _, H, W = shape
+    if t.stride(3) != 1 or t.stride(2) != W or t.stride(1) != H * W or (shape[0] > 1 and t.stride(0) < 3 * H * W):
+        raise ValueError("%s: an image of out must be dense (strides %s of shape %s); only the batch stride is free" % (what, t.stride(), shape))
+    return t.stride(0) if shape[0] > 1 else 3 * H * W
+
+
+def prepare_frames(left, right=None, size=None, crop=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, layout='HWC', color=True, out=None):
+    """ToTensor + normalize + resize / crop of both eyes in one launch.  left / right: uint8 GPU tensors, [H,W,3] / [B,H,W,3]
+    (layout 'HWC') or [3,H,W] / [B,3,H,W] ('CHW').  Returns {'color_l', 'color_aug_l'} and, with `right`, {'color_r', 'color_aug_r'}:
+    fp32 [B,3,.,.] ([3,.,.] for an unbatched input); `color=False` leaves the plain / 255 images out.
+      size=None, crop=None    the values at the source size
+      size=(H, W)             evaluation form: color_aug resized (bilinear, align_corners=True), color at the source size
+      size=(H, W), crop=...   training form: the window [ch:ch+H, cw:cw+W] of both; crop is one (ch, cw) per image as a list
+                              (checked here, uploaded) or an int32 device tensor [B,2] (clamped into the image by the kernel)
+      out=                    pre-allocated color_aug tensor(s), `out_l` or `(out_l, out_r)`, fp32 [B,3,H,W] with dense images
+                              and any batch stride (the same for both), e.g. slices of a larger buffer: written in place and
+                              returned."""
+    what = "prepare_frames"
+    left, right, B, Hs, Ws, batched = _frames(what, left, right, layout)
+    dev = left.device
+    mean, std = _three("mean", mean), _three("std", std)
+    if size is None:
+        if crop is not None:
+            raise ValueError("%s: a crop needs the window's size" % what)
+        H, W = Hs, Ws
+    else:
+        H, W = (int(v) for v in size)
+        if H <= 0 or W <= 0:
+            raise ValueError("%s: size %s" % (what, (H, W)))
+    crop_t = None
+    if crop is not None:
+        if H > Hs or W > Ws:
+            raise ValueError("%s: an image of shape %s cannot be cropped to %s" % (what, (Hs, Ws), (H, W)))
+        if torch.is_tensor(crop):
+            _on_gpu(what, crop)
+            if crop.dtype != torch.int32 or tuple(crop.shape) != (B, 2):
+                raise ValueError("%s: a crop tensor is int32 [%d,2] (got %s %s)" % (what, B, crop.dtype, tuple(crop.shape)))
+            crop_t = _lib.contiguous(crop)
+        else:
+            rows = [tuple(int(v) for v in c) for c in ([crop] if len(crop) == 2 and not hasattr(crop[0], '__len__') else crop)]
+            if len(rows) == 1 and B > 1:
+                rows = rows * B
+            if len(rows) != B or any(len(r) != 2 for r in rows):
+                raise ValueError("%s: one (ch, cw) per image expected (%d), got %s" % (what, B, rows))
+            for ch, cw in rows:
+                if not (0 <= ch <= Hs - H and 0 <= cw <= Ws - W):
+                    raise ValueError("%s: the crop origin %s puts a %s window outside an image of shape %s" % (what, (ch, cw), (H, W), (Hs, Ws)))
+            crop_t = torch.tensor(rows, dtype=torch.int32, device=dev)
+    resize = crop_t is None and (H, W) != (Hs, Ws)
+    Hc, Wc = (Hs, Ws) if resize else (H, W)
+    res = {}
+    sides = ('l', 'r') if right is not None else ('l',)
+    aug_shape = (B, 3, H, W)
+    if out is not None:
+        outs = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+        if len(outs) != len(sides):
+            raise ValueError("%s: %d out tensors for %d eyes" % (what, len(outs), len(sides)))
+        strides = {_out_tensor(what, t, aug_shape, dev) for t in outs}
+        if len(strides) != 1:
+            raise ValueError("%s: the out tensors must share one batch stride (got %s)" % (what, sorted(strides)))
+        aug_stride = strides.pop()
+    else:
+        outs = tuple(torch.empty(aug_shape, device=dev, dtype=torch.float32) for _ in sides)
+        aug_stride = 3 * H * W
+    for s, t in zip(sides, outs):
+        res['color_aug_' + s] = t
+    if color:
+        for s in sides:
+            res['color_' + s] = torch.empty((B, 3, Hc, Wc), device=dev, dtype=torch.float32)
+    _lib.check(_lib.lib().ts_frames_prepare_fwd(
+        _lib.ptr(left), _lib.ptr(right), B, Hs, Ws, CHW if layout == 'CHW' else 0, *mean, *std, H, W, _lib.ptr(crop_t),
+        _lib.ptr(res.get('color_l')), _lib.ptr(res.get('color_r')), 3 * Hc * Wc,
+        _lib.ptr(res['color_aug_l']), _lib.ptr(res.get('color_aug_r')), aug_stride, _stream()), "ts_frames_prepare_fwd")
+    if not batched:
+        res = {k: v[0] for k, v in res.items()}
+    return res
+
+
+def default_num_scales(size):
+    """min(int(log2(W)), int(log2(H))) of base.py:231"""
+    H, W = size
+    return min(int(math.log2(W)), int(math.log2(H)))
+
+
+def intrinsics_pyramid(K_norm, size, num_scales=None):
+    """base.py:231-248: K_norm, the intrinsics divided by the image's (h, w) -- fp32 or fp64 GPU tensor [4,4] or [B,4,4] -- and
+    size = (kh, kw) -> (K, inv_K), fp32 [B,S,4,4] ([S,4,4] for an unbatched K_norm); [:, s] is ('K', s) / ('inv_K', s)."""
+    what = "intrinsics_pyramid"
+    _on_gpu(what, K_norm)
+    if K_norm.dtype not in (torch.float32, torch.float64):
+        raise TypeError("%s: K_norm must be fp32 or fp64 (got %s)" % (what, K_norm.dtype))
+    if K_norm.dim() not in (2, 3) or tuple(K_norm.shape[-2:]) != (4, 4) or K_norm.numel() == 0:
+        raise ValueError("%s: K_norm must be [4,4] or [B,4,4] (got %s)" % (what, tuple(K_norm.shape)))
+    kh, kw = (int(v) for v in size)
+    S = default_num_scales((kh, kw)) if num_scales is None else int(num_scales)
+    if kh <= 0 or kw <= 0 or S <= 0 or (kh >> (S - 1)) == 0 or (kw >> (S - 1)) == 0:
+        raise ValueError("%s: %d scales of a %dx%d image" % (what, S, kh, kw))
+    batched = K_norm.dim() == 3
+    B = K_norm.shape[0] if batched else 1
+    kn = _lib.contiguous(K_norm)
+    K = torch.empty((B, S, 4, 4), device=kn.device, dtype=torch.float32)
+    inv = torch.empty_like(K)
+    _lib.check(_lib.lib().ts_intrinsics_pyramid_fwd(_lib.ptr(kn), 1 if kn.dtype == torch.float64 else 0, B, kh, kw, S, _lib.ptr(K),
+                                                    _lib.ptr(inv), _stream()), "ts_intrinsics_pyramid_fwd")
+    return (K, inv) if batched else (K[0], inv[0])
+
+
+def disp_from_uint16(raw, scale=256.0, with_valid=False):
+    """video_inference.py:135-140: a 16-bit disparity map [H,W] / [B,H,W] / [B,1,H,W] -> fp32 [H,W] / [B,1,H,W] = raw / scale where
+    raw > 0 (exact for scale 256), 0 elsewhere; with_valid also returns the mask raw > 0 (bool, same shape).
+    raw: torch.uint16; or torch.int16, whose bits are REINTERPRETED as unsigned (-1 is 65535); or torch.int32, whose low 16 bits
+    are taken (a cast on the device; not while a launch plan is being recorded)."""
+    what = "disp_from_uint16"
+    _on_gpu(what, raw)
+    if raw.dtype == torch.int32:
+        if _lib.recording():
+            raise RuntimeError("%s: an int32 map needs a cast that a launch plan would not replay; hand over 16-bit storage" % what)
+        raw = raw.to(torch.int16)
+    elif raw.dtype != torch.int16 and (_U16 is None or raw.dtype != _U16):
+        raise TypeError("%s: raw must be uint16, int16 (reinterpreted) or int32 (got %s of shape %s)" % (what, raw.dtype, tuple(raw.shape)))
+    if raw.dim() not in (2, 3, 4) or (raw.dim() == 4 and raw.shape[1] != 1) or raw.numel() == 0:
+        raise ValueError("%s: raw must be a non-empty [H,W], [B,H,W] or [B,1,H,W] map (got %s)" % (what, tuple(raw.shape)))
+    if not float(scale) > 0:
+        raise ValueError("%s: scale %r" % (what, scale))
+    batched = raw.dim() > 2
+    B = raw.shape[0] if batched else 1
+    H, W = raw.shape[-2:]
+    r = _lib.contiguous(raw)
+    disp = torch.empty((B, 1, H, W), device=r.device, dtype=torch.float32)
+    valid = torch.empty((B, 1, H, W), device=r.device, dtype=torch.uint8) if with_valid else None
+    _lib.check(_lib.lib().ts_disp_u16_decode_fwd(_lib.ptr(r), B, H, W, float(scale), _lib.ptr(disp), _lib.ptr(valid), _stream()),
+               "ts_disp_u16_decode_fwd")
+    if not batched:
+        disp = disp[0, 0]
+        valid = valid[0, 0] if with_valid else None
+    return (disp, valid.view(torch.bool)) if with_valid else disp
+
+
+def prepare_batch(left, right, K_norm, baseline, size, timestamp=0, disp_gt_raw=None, crop=None, k_size=None, num_scales=None,
+                  mean=IMAGENET_MEAN, std=IMAGENET_STD, layout='HWC', gt_scale=256.0, out=None):
+    """The reference's batch dictionary (video_inference.py:262-293; base.py __getitem__) from uint8 frames, in three launches and
+    without touching the host:
+      ('color', t, 'l' / 'r')       [B,3,Hc,Wc]   ('color_aug', t, 'l' / 'r')  [B,3,H,W]      prepare_frames(size, crop)
+      ('K', s), ('inv_K', s)        [B,4,4]       views of the [B,S,4,4] pyramid (batch stride 16 S) for s < num_scales, built at
+                                                  k_size (default: `size`; training passes the un-cropped resolution, base.py:235)
+      'baseline'                    [B,1,1,1]     a number, or a device tensor of B values
+      ('disp_gt', t, 'l')           [B,1,Hg,Wg]   disp_from_uint16(disp_gt_raw, gt_scale) when given
+    t = timestamp.  num_scales: None = base.py:231's min(int(log2 W), int(log2 H)) of `size`; video_inference.py uses 1."""
+    what = "prepare_batch"
+    if right is None:
+        raise ValueError("%s: a stereo pair is needed" % what)
+    if size is None:
+        raise ValueError("%s: the network's input size is needed" % what)
+    size = tuple(int(v) for v in size)
+    fr = prepare_frames(left, right, size=size, crop=crop, mean=mean, std=std, layout=layout, color=True, out=out)
+    batched = fr['color_aug_l'].dim() == 4
+    if not batched:
+        fr = {k: v.unsqueeze(0) for k, v in fr.items()}
+    B = fr['color_aug_l'].shape[0]
+    dev = fr['color_aug_l'].device
+    t = timestamp
+    batch = {('color', t, 'l'): fr['color_l'], ('color', t, 'r'): fr['color_r'],
+             ('color_aug', t, 'l'): fr['color_aug_l'], ('color_aug', t, 'r'): fr['color_aug_r']}
+    S = default_num_scales(size) if num_scales is None else int(num_scales)
+    _on_gpu(what, K_norm)
+    kn = K_norm if K_norm.dim() == 3 else K_norm.unsqueeze(0)
+    if kn.shape[0] not in (1, B):
+        raise ValueError("%s: K_norm of shape %s for a batch of %d" % (what, tuple(K_norm.shape), B))
+    K, inv = intrinsics_pyramid(kn, size if k_size is None else k_size, S)
+    if K.shape[0] != B:
+        K, inv = K.expand(B, S, 4, 4), inv.expand(B, S, 4, 4)
+    for s in range(S):
+        batch[('K', s)] = K[:, s]
+        batch[('inv_K', s)] = inv[:, s]
+    if torch.is_tensor(baseline):
+        _on_gpu(what, baseline)
+        if baseline.numel() != B:
+            raise ValueError("%s: baseline of shape %s for a batch of %d" % (what, tuple(baseline.shape), B))
+        batch['baseline'] = baseline.to(torch.float32).reshape(B, 1, 1, 1)
+    else:
+        batch['baseline'] = torch.full((B, 1, 1, 1), float(baseline), device=dev, dtype=torch.float32)
+    if disp_gt_raw is not None:
+        g = disp_gt_raw if disp_gt_raw.dim() > 2 else disp_gt_raw.unsqueeze(0)
+        if g.shape[0] != B:
+            raise ValueError("%s: disp_gt_raw of shape %s for a batch of %d" % (what, tuple(disp_gt_raw.shape), B))
+        batch[('disp_gt', t, 'l')] = disp_from_uint16(g, gt_scale)
+    return batch

@@ -951,6 +951,287 @@ def render_cases(M):
     print("\n".join(lines))
 
 
+# ----------------------------------------------------------------------------------------------
+PREPARE_CASES = ("prepare_same", "prepare_ramp", "prepare_dataset_up", "prepare_video_up", "prepare_down", "prepare_train_crop",
+                 "prepare_degenerate", "prepare_disp16")
+
+
+def _torchvision_stand_in(state):
+    """torchvision is not installed: a stand-in of the project's own writing, registered before the reference's dataset module is
+    imported.  ToTensor of a PIL RGB image and functional.normalize as torchvision defines them (uint8 HWC -> float CHW / 255;
+    (t - mean) / std with mean / std in the tensor's dtype).  state['dtype'] switches the float type, so that the reference's own
+    functions can be run again on float64 inputs.  ColorJitter / adjust_gamma are never called (colour augmentation is pinned off)."""
+    import types
+
+    class ToTensor:
+        def __call__(self, pic):
+            return torch.from_numpy(np.array(pic, dtype=np.uint8, copy=True)).permute(2, 0, 1).contiguous().to(state["dtype"]).div(255)
+
+    class Compose:
+        def __init__(self, ts):
+            self.transforms = ts
+
+        def __call__(self, x):
+            for t in self.transforms:
+                x = t(x)
+            return x
+
+    class ColorJitter:
+        def __init__(self, *a, **k):
+            pass
+
+        def __call__(self, x):
+            raise RuntimeError("colour augmentation is pinned off in the fixtures")
+
+    def normalize(tensor, mean, std, inplace=False):
+        mean = torch.as_tensor(mean, dtype=tensor.dtype)
+        std = torch.as_tensor(std, dtype=tensor.dtype)
+        return (tensor - mean[:, None, None]) / std[:, None, None]
+
+    def adjust_gamma(*a, **k):
+        raise RuntimeError("colour augmentation is pinned off in the fixtures")
+
+    fn = types.ModuleType("torchvision.transforms.functional")
+    fn.normalize, fn.adjust_gamma = normalize, adjust_gamma
+    tr = types.ModuleType("torchvision.transforms")
+    tr.ToTensor, tr.Compose, tr.ColorJitter, tr.functional = ToTensor, Compose, ColorJitter, fn
+    tv = types.ModuleType("torchvision")
+    tv.transforms = tr
+    sys.modules.setdefault("torchvision", tv)
+    sys.modules.setdefault("torchvision.transforms", tr)
+    sys.modules.setdefault("torchvision.transforms.functional", fn)
+    return tr, fn
+
+
+def _reference_prepare(state):
+    """The reference's dataset base class (by file path: the package __init__ imports loaders this image lacks) and the top-level
+    functions of video_inference.py by the AST route of reference_update_map (its module-level imports do not resolve here)."""
+    import ast
+    import importlib.util
+    import types
+    import torch.nn.functional as F
+    from PIL import Image
+    tr, fn = _torchvision_stand_in(state)
+    path = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "data", "datasets", "base.py")
+    spec = importlib.util.spec_from_file_location("_ref_dataset_base", path)
+    base = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(base)
+
+    def imread(path, flags=None):                      # cv2.imread(IMREAD_ANYDEPTH): PIL's 16-bit reader
+        with Image.open(path) as im:
+            assert im.mode in ("I;16", "I;16B", "I"), im.mode
+            return np.array(im).astype(np.uint16)
+    cv2 = types.SimpleNamespace(imread=imread, IMREAD_ANYDEPTH=2, IMREAD_ANYCOLOR=4)
+    path = os.path.join(ref_import.REFERENCE_ROOT, "projects", "TemporalStereo", "video_inference.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    want = ("pil_loader", "read_image", "read_intrinsics", "read_disparity")
+    fns = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in want]
+    assert len(fns) == len(want)
+    # the single-scale intrinsics of inference_stereo (:245-251): the assignments to norm_K / kh, kw / scale_K / inv_scale_K
+    outer = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "inference_stereo")
+    names = {"norm_K", "baseline", "kh", "kw", "scale_K", "inv_scale_K"}
+    k_stmts = [n for n in outer.body if isinstance(n, ast.Assign) and
+               {x.id for t in n.targets for x in ast.walk(t) if isinstance(x, ast.Name)} & names]
+    assert len(k_stmts) == 7, len(k_stmts)
+    k_fn = ast.parse("def single_scale_K(resize_to_shape):\n    pass\n    return scale_K, inv_scale_K, baseline").body[0]
+    k_fn.body[0:1] = k_stmts
+    ns = {"Image": Image, "transforms": tr, "transF": fn, "F": F, "np": np, "cv2": cv2, "torch": torch}
+    exec(compile(ast.fix_missing_locations(ast.Module(body=fns + [k_fn], type_ignores=[])), path, "exec"), ns)
+    return base, ns
+
+
+def prepare_cases(M):
+    """Input preparation (video_inference.py:100-140, :245-251; datasets/base.py:99-187, :231-248): the reference's own
+    StereoDatasetBase.__getitem__ / do_transform on a throw-away dataset (seeded uint8 PNGs, a JSON annotation file) and its
+    read_image / read_disparity, once in float32 (the expected outputs) and, for the resized cases, once more on float64 inputs;
+    dev32_64 = max |fp32 run - fp64 run| of a case is the distance the reference itself keeps from the float64 answer."""
+    import json
+    import random as pyrandom
+    import tempfile
+    import types
+    import PIL
+    from PIL import Image
+    state = {"dtype": torch.float32}
+    base, vi = _reference_prepare(state)
+    K_of = {k: vi["read_intrinsics"](k)[0] for k in ("kitti", "tartanair")}
+    full_res = {"kitti": (375, 1242), "tartanair": (480, 640)}
+
+    class ThrowAway(base.StereoDatasetBase):
+        camera = "kitti"
+        resolution = None
+
+        def Loader(self, image_path):
+            return base.pil_loader(os.path.join(self.root, image_path))
+
+        def intrinsicLoader(self, intrinsic_path):
+            K = K_of[self.camera].copy()
+            h, w = self.resolution
+            full_K = K.copy()
+            full_K[0] *= w
+            full_K[1] *= h
+            return K, full_K, (h, w)
+
+    def noise(seed, tag, shape):
+        return synth._rs(seed, tag).randint(0, 256, size=shape).astype(np.uint8)
+
+    def ramp(H, W):
+        """every byte value in every channel, the channels out of step"""
+        idx = np.arange(H * W).reshape(H, W)
+        return np.stack([(idx * 1 + 0) % 256, (idx * 3 + 85) % 256, (255 - idx) % 256], axis=-1).astype(np.uint8)
+
+    def dataset_run(tmp, lefts, rights, size, is_train, camera, dtype, crops=None):
+        """the reference's dataset over B stereo pairs -> stacked sample tensors"""
+        state["dtype"] = dtype
+        items = []
+        for b, (l, r) in enumerate(zip(lefts, rights)):
+            for side, img in (("left", l), ("right", r)):
+                Image.fromarray(img, "RGB").save(os.path.join(tmp, "%s_%d.png" % (side, b)))
+            items.append({"0": {"left_image_path": "left_%d.png" % b, "right_image_path": "right_%d.png" % b}})
+        ann = os.path.join(tmp, "ann.json")
+        with open(ann, "w") as fh:
+            json.dump(items, fh)
+        draws = iter([v for c in (crops or []) for v in c])
+        taken = []
+
+        def randint(lo, hi):
+            v = next(draws)
+            assert lo <= v <= hi
+            taken.append(v)
+            return v
+        # pinned draws: no colour augmentation (random.random), the recorded crop origins (random.randint), no occlusion patch
+        base.random = types.SimpleNamespace(random=lambda: 0.0, randint=randint, uniform=pyrandom.uniform)
+        real_binomial = np.random.binomial
+        np.random.binomial = lambda n, p: 0
+        try:
+            ThrowAway.camera, ThrowAway.resolution = camera, lefts[0].shape[:2]
+            ds = ThrowAway(ann, tmp, size[0], size[1], [0], is_train=is_train)
+            samples = [ds[b] for b in range(len(items))]
+        finally:
+            np.random.binomial = real_binomial
+            base.random = pyrandom
+        assert taken == [v for c in (crops or []) for v in c]
+        S = min(int(np.log2(size[1])), int(np.log2(size[0])))
+        out = {"color_l": torch.stack([s[("color", 0, "l")] for s in samples]), "color_r": torch.stack([s[("color", 0, "r")] for s in samples]),
+               "aug_l": torch.stack([s[("color_aug", 0, "l")] for s in samples]), "aug_r": torch.stack([s[("color_aug", 0, "r")] for s in samples]),
+               "K": torch.stack([torch.stack([s[("K", k)] for k in range(S)]) for s in samples]),
+               "inv_K": torch.stack([torch.stack([s[("inv_K", k)] for k in range(S)]) for s in samples]),
+               "baseline": torch.stack([s["baseline"] for s in samples])}
+        assert all(("K", S) not in s for s in samples)
+        return {k: v.numpy() for k, v in out.items()}
+
+    def video_run(tmp, left, right, size, dtype):
+        state["dtype"] = dtype
+        out = {}
+        for side, img in (("l", left), ("r", right)):
+            path = os.path.join(tmp, "v_%s.png" % side)
+            Image.fromarray(img, "RGB").save(path)
+            image, proc = vi["read_image"](path, size)
+            out["color_" + side], out["aug_" + side] = image[None].numpy(), proc[None].numpy()
+        return out
+
+    lines = ["prepare_*.npz: tools/gen_golden.py --only-prepare, numpy %s, PIL %s, torch %s CPU -- the reference's own" % (np.__version__, PIL.__version__, torch.__version__),
+             "StereoDatasetBase.__getitem__ / do_transform (architecture/data/datasets/base.py) on a throw-away dataset of seeded uint8 PNGs,",
+             "and read_image / read_intrinsics / read_disparity and the single-scale K of inference_stereo (projects/TemporalStereo/",
+             "video_inference.py, taken by their syntax trees: the module's own imports do not resolve here).",
+             "torchvision is not installed: ToTensor / functional.normalize / Compose come from a stand-in written for this generator",
+             "(PIL RGB -> from_numpy(...).permute(2,0,1).contiguous().to(float).div(255); (t - mean[:,None,None]) / std[:,None,None] with",
+             "mean / std in the tensor's dtype); cv2.imread is stood in by PIL's 16-bit reader.  Training cases pin random.random (no colour",
+             "augmentation), random.randint (the recorded crop origins) and np.random.binomial (no occlusion patch).",
+             "Expected outputs: the float32 run.  Resized cases also hold the same functions run on float64 inputs (stored as the float32",
+             "run plus a float32 difference); dev32_64 = max |fp32 run - fp64 run| over the case."]
+    seed0 = synth.SEED0 + 900
+
+    def finish(name, subs):
+        """subs: list of dicts of arrays; key<k> per sub-case"""
+        arrs = {"subs": np.int64(len(subs))}
+        dev = 0.0
+        resized = False
+        for k, sub in enumerate(subs):
+            for key, v in sub.items():
+                if key.startswith("aug64_"):
+                    a32 = sub["aug_" + key[-1]]
+                    d = v - a32.astype(np.float64)
+                    dev = max(dev, float(np.abs(d).max()))
+                    resized = True
+                    arrs["d64_%s%d" % (key[-1], k)] = d.astype(np.float32)
+                else:
+                    arrs["%s%d" % (key, k)] = v
+        if resized:
+            assert dev > 0
+            arrs["dev32_64"] = np.float64(dev)
+        save(name, **arrs)
+        sz = os.path.getsize(os.path.join(OUT, name + ".npz"))
+        assert sz <= 110 * 1024, (name, sz)
+        lines.append("%-20s %d sub-case(s), %s%s" % (name, len(subs), "; ".join(
+            "%s -> %s B=%d" % (tuple(s["left"].shape[1:3]), tuple(s["aug_l"].shape[-2:]), s["left"].shape[0]) for s in subs if "left" in s),
+            ("  dev32_64 %.3g" % dev) if resized else "  exact"))
+
+    with tempfile.TemporaryDirectory() as tmp:
+        # --- same size, through the dataset (evaluation form, source == target)
+        L, R = noise(seed0, "sameL", (1, 31, 45, 3)), noise(seed0, "sameR", (1, 31, 45, 3))
+        r = dataset_run(tmp, L, R, (31, 45), False, "kitti", torch.float32)
+        finish("prepare_same", [dict(left=L, right=R, K_norm=K_of["kitti"], k_size=np.array([31, 45]), **r)])
+
+        # --- every byte value in every channel, ragged widths
+        subs = []
+        for H, W in ((20, 13), (19, 14), (18, 15)):
+            L = ramp(H, W)[None]
+            R = L[:, ::-1, ::-1].copy()
+            assert all(len(np.unique(L[..., c])) == 256 for c in range(3))
+            r = dataset_run(tmp, L, R, (H, W), False, "kitti", torch.float32)
+            subs.append(dict(left=L, right=R, color_l=r["color_l"], color_r=r["color_r"], aug_l=r["aug_l"], aug_r=r["aug_r"]))
+        finish("prepare_ramp", subs)
+
+        # --- "pad by resize" of base.py:183, B=2, and the K pyramid at the resized size
+        L, R = noise(seed0 + 1, "upL", (2, 19, 33, 3)), noise(seed0 + 1, "upR", (2, 19, 33, 3))
+        r = dataset_run(tmp, L, R, (24, 36), False, "kitti", torch.float32)
+        r64 = dataset_run(tmp, L, R, (24, 36), False, "kitti", torch.float64)
+        assert r64["aug_l"].dtype == np.float64
+        finish("prepare_dataset_up", [dict(left=L, right=R, K_norm=K_of["kitti"], k_size=np.array([24, 36]), aug64_l=r64["aug_l"],
+                                           aug64_r=r64["aug_r"], **r)])
+
+        # --- read_image, the unsqueeze(dim=1) form, and inference_stereo's single-scale K
+        for name, src, dst, sd in (("prepare_video_up", (30, 40), (34, 52), 2), ("prepare_down", (45, 77), (16, 30), 3)):
+            L, R = noise(seed0 + sd, "vL", (1,) + src + (3,)), noise(seed0 + sd, "vR", (1,) + src + (3,))
+            r = video_run(tmp, L[0], R[0], dst, torch.float32)
+            r64 = video_run(tmp, L[0], R[0], dst, torch.float64)
+            K, invK, baseline = vi["single_scale_K"](dst)
+            finish(name, [dict(left=L, right=R, K_norm=K_of["tartanair"], k_size=np.array(dst),
+                               K=torch.from_numpy(K).float()[None, None].numpy(), inv_K=torch.from_numpy(invK).float()[None, None].numpy(),
+                               baseline=np.float32(baseline), aug64_l=r64["aug_l"], aug64_r=r64["aug_r"], **r)])
+
+        # --- training crop: both outputs cropped, K at the un-cropped resolution
+        L, R = noise(seed0 + 4, "cropL", (2, 37, 57, 3)), noise(seed0 + 4, "cropR", (2, 37, 57, 3))
+        crops = [(0, 0), (37 - 24, 57 - 40)]
+        r = dataset_run(tmp, L, R, (24, 40), True, "tartanair", torch.float32, crops=crops)
+        assert r["color_l"].shape[-2:] == (24, 40)
+        finish("prepare_train_crop", [dict(left=L, right=R, crop=np.array(crops, dtype=np.int32), K_norm=K_of["tartanair"],
+                                           k_size=np.array([37, 57]), **r)])
+
+        # --- degenerate sizes: a 1 x W and an H x 1 source, a target of height 1 (ac_scale's zero branch)
+        subs = []
+        for k, (src, dst) in enumerate((((1, 21), (5, 30)), ((17, 1), (20, 7)), ((9, 13), (1, 20)))):
+            L, R = noise(seed0 + 5, "dgL%d" % k, (1,) + src + (3,)), noise(seed0 + 5, "dgR%d" % k, (1,) + src + (3,))
+            r = video_run(tmp, L[0], R[0], dst, torch.float32)
+            r64 = video_run(tmp, L[0], R[0], dst, torch.float64)
+            subs.append(dict(left=L, right=R, aug64_l=r64["aug_l"], aug64_r=r64["aug_r"], **r))
+        finish("prepare_degenerate", subs)
+
+        # --- read_disparity on a 16-bit PNG
+        raw = synth._rs(seed0 + 6, "d16").randint(0, 65536, size=(40, 61)).astype(np.uint16)
+        raw[synth.uniform(seed0 + 6, "d16z", (40, 61)) < 0.3] = 0
+        raw[0, :3] = (0, 1, 65535)
+        path = os.path.join(tmp, "disp.png")
+        Image.fromarray(raw).save(path)
+        disp = vi["read_disparity"](path)
+        assert disp.dtype == np.float64 and np.array_equal(disp.astype(np.float32).astype(np.float64), disp)
+        save("prepare_disp16", subs=np.int64(1), raw0=raw[None], disp0=disp.astype(np.float32)[None, None], valid0=(raw > 0)[None, None])
+        lines.append("%-20s 40x61, %.0f %% zeros, holds 0, 1 and 65535  exact" % ("prepare_disp16", 100 * (raw == 0).mean()))
+    with open(os.path.join(OUT, "PROVENANCE_prepare.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -970,6 +1251,9 @@ def main():
         return
     if "--only-render" in sys.argv:
         render_cases(M)
+        return
+    if "--only-prepare" in sys.argv:
+        prepare_cases(M)
         return
     if "--only-backbone-memory" in sys.argv:
         backbone_memory_cases(M)
