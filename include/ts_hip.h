@@ -275,6 +275,41 @@ int ts_intrinsics_pyramid_fwd(const void* K_norm, int is_fp64, int B, int kh, in
 int ts_disp_u16_decode_fwd(const void* raw, int B, int H, int W, float scale, float* disp, void* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Augmentation of the training frames (architecture/data/datasets/base.py:65-187: ColorJitter in a random order, AdjustGamma, the
+ * crop, the occlusion rectangles on the right eye's color_aug).  The random draws are made on the host and handed over as ONE table:
+ * table  DEVICE pointer to int32 [eyes,B,TS_AUGMENT_ROW_INTS], eyes = 2 with a right image, else 1; the words of a row:
+ *     [0]      flags: TS_AUGMENT_GAMMA = the row's gamma table is applied after the colour operations
+ *     [1]      the order: byte k (k = 0 lowest) is the k-th operation, 0 brightness, 1 contrast, 2 saturation, 3 hue, 4 none;
+ *              an operation appears at most once
+ *     [2..4]   the factors of brightness, contrast, saturation (fp32 bit patterns)      [5] the hue shift in bytes, 0..255
+ *     [6],[7]  the crop origin (ch, cw); outside [0,Hs-H] x [0,Ws-W] it is CLAMPED (the kernel reads it, the host cannot refuse it)
+ *     [8]      the number of rectangles, 0..TS_AUGMENT_MAX_RECTS   [9..24] (sh, sw, occh, occw) each, window coordinates, in the order
+ *              they are applied (a later one overwrites an earlier one); the part outside the window is ignored
+ *     [25],[26] the noise seed, low and high word                   [27..31] zero
+ *     [32..95] the gamma table, 256 bytes, byte e of word 32 + e / 4 at bits 8 (e % 4)
+ * ts_frames_augment_fwd: two launches for the whole batch and both eyes (grey-level sums of the full frames for contrast, then
+ *   the window).  left / right / flags / mean / std / strides as ts_frames_prepare_fwd; H <= Hs, W <= Ws.
+ *   color_*      fp32 [B,3,H,W] = byte / 255 of the window of the frame as it came
+ *   color_aug_*  fp32 [B,3,H,W] = the window of normalize(gamma(operations(frame))) in PIL's uint8 arithmetic, bit for bit; inside a
+ *                rectangle (n - mean[c]) / std[c], n ~ N(0, 0.1) from Philox-4x32-10 keyed by the row's seed and counted by
+ *                (column, row in the rectangle, channel, rectangle): independent of B, of the image's place and of the strides.
+ *   workspace    ts_frames_augment_workspace_bytes(B, Hs, Ws) bytes, 8-byte aligned; need not be zeroed.  No atomics; bit-identical
+ *                from run to run.
+ * ts_disp_u16_window_fwd: ts_disp_u16_decode_fwd of the window [ch:ch+H, cw:cw+W] whose origin is words [6],[7] of row b of the
+ *   table (the left eye's rows), clamped alike: raw uint16 [B,Hs,Ws] -> disp fp32 [B,1,H,W], valid (may be NULL) uint8 [B,1,H,W].
+ * ---------------------------------------------------------------------------------------- */
+#define TS_AUGMENT_ROW_INTS 96
+#define TS_AUGMENT_MAX_RECTS 4
+#define TS_AUGMENT_GAMMA 1
+size_t ts_frames_augment_workspace_bytes(int B, int Hs, int Ws);
+int ts_frames_augment_fwd(const void* left, const void* right, int B, int Hs, int Ws, int flags, float mean0, float mean1,
+                          float mean2, float std0, float std1, float std2, int H, int W, const int* table, float* color_l,
+                          float* color_r, long long color_stride, float* color_aug_l, float* color_aug_r,
+                          long long color_aug_stride, void* workspace, size_t workspace_bytes, void* stream);
+int ts_disp_u16_window_fwd(const void* raw, int B, int Hs, int Ws, int H, int W, const int* table, float scale, float* disp,
+                           void* valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * K4  disparity regression.  cost / sample / offset are [B,D,H,W].
  * ts_topk_softargmax_*: predict_disp()  .../aggregation/TemporalStereo/coarse.py:69-75
  *   (== fine.py:70-76, precise.py:61-67): top-k (1 <= k <= 8, ties: lowest index first) ->

@@ -20,3 +20,6 @@ from . import visualization  # noqa: F401
 from .visualization import render_frame  # noqa: F401
 from . import preprocess  # noqa: F401
 from .preprocess import prepare_frames, prepare_batch, intrinsics_pyramid, disp_from_uint16  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import (Augmentation, draw_augmentation, gamma_table, augment_frames, prepare_train_batch,  # noqa: F401
+                      disp_window_from_uint16)

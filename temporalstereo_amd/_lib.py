@@ -80,6 +80,10 @@ SIGNATURES = {
                               [ctypes.c_longlong] + [c_f32p] * 2 + [ctypes.c_longlong, c_ptr]),
     "ts_intrinsics_pyramid_fwd": (c_int, [c_ptr] + [c_int] * 5 + [c_f32p] * 2 + [c_ptr]),
     "ts_disp_u16_decode_fwd": (c_int, [c_ptr] + [c_int] * 3 + [c_float, c_f32p, c_ptr, c_ptr]),
+    "ts_frames_augment_workspace_bytes": (c_size, [c_int] * 3),
+    "ts_frames_augment_fwd": (c_int, [c_ptr] * 2 + [c_int] * 4 + [c_float] * 6 + [c_int] * 2 + [c_ptr] + [c_f32p] * 2 +
+                              [ctypes.c_longlong] + [c_f32p] * 2 + [ctypes.c_longlong, c_ptr, c_size, c_ptr]),
+    "ts_disp_u16_window_fwd": (c_int, [c_ptr] + [c_int] * 5 + [c_ptr, c_float, c_f32p, c_ptr, c_ptr]),
     "ts_softsplat_sum_fwd": (c_int, [c_f32p] * 3 + [c_int] * 4 + [c_ptr]),
     "ts_softsplat_sum_fwd_deterministic": (c_int, [c_f32p] * 3 + [c_ptr] + [c_int] * 4 + [c_ptr]),
     "ts_softsplat_sum_bwd_input": (c_int, [c_f32p] * 3 + [c_int] * 4 + [c_ptr]),

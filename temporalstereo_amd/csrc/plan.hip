@@ -100,6 +100,7 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_conv_weight_layout_many2), TS_PLAN_OP(ts_conv_wgrad_finish_many), TS_PLAN_OP(ts_channel_sum_fwd),
     TS_PLAN_OP(ts_block_cost_sampled_warped_bwd),
     TS_PLAN_OP(ts_frames_prepare_fwd),      TS_PLAN_OP(ts_intrinsics_pyramid_fwd),  TS_PLAN_OP(ts_disp_u16_decode_fwd),
+    TS_PLAN_OP(ts_frames_augment_fwd),      TS_PLAN_OP(ts_disp_u16_window_fwd),
 };
 
 struct Call {

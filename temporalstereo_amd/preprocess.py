@@ -27,8 +27,9 @@ Differences, deliberate:
   - `disp_from_uint16` takes torch.uint16 where this torch has it, or int16 storage REINTERPRETED as unsigned (the bits a 16-bit
     PNG reader hands over viewed as int16); an int32 tensor is accepted with its low 16 bits taken (a cast on the device);
     the valid mask comes from the kernel (torch's comparisons do not cover uint16).
-Out of scope, on purpose: decoding files (PIL / cv2), ColorJitter / gamma (PIL-space uint8 operations with host random draws), the
-random occlusion patches of base.py:157-173, PFM / flow loaders.  Cropping an fp32 ground-truth map is a tensor slice.
+Out of scope, on purpose: decoding files (PIL / cv2), PFM / flow loaders.  ColorJitter / gamma, the random occlusion patches of
+base.py:157-173 and the ground truth cut to a window whose origin lives on the device are in augment.py (`prepare_train_batch`).
+Cropping an fp32 ground-truth map is a tensor slice.
 uint8 GPU tensors only: a CPU tensor raises, there is no CPU fallback.
 """
 import math

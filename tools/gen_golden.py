@@ -1232,6 +1232,234 @@ def prepare_cases(M):
     print("\n".join(lines))
 
 
+# ----------------------------------------------------------------------------------------------
+AUGMENT_CASES = ("augment_ops", "augment_orders", "augment_chain", "augment_occlusion", "augment_large", "augment_identity")
+
+
+def augment_cases(M):
+    """Colour augmentation, crop and occlusion of the training input (datasets/base.py:65-187): the reference's own
+    StereoDatasetBase.do_transform (is_train=True) on a throw-away dataset of seeded uint8 PNGs with every random source pinned to
+    recorded values.  torchvision is not installed: ColorJitter / adjust_gamma are stood in by the PIL calls torchvision's PIL path
+    makes (ImageEnhance.Brightness / Contrast / Color, the HSV round trip with the numpy uint8 hue shift, Image.point with the
+    truncating table); the stand-in takes its order and factors from the recorded list instead of torch's random stream."""
+    import json
+    import random as pyrandom
+    import tempfile
+    import types
+    import PIL
+    from PIL import Image, ImageEnhance
+    state = {"dtype": torch.float32, "jitter": None, "stages": None}
+    base, vi = _reference_prepare(state)
+    K_of = {"tartanair": vi["read_intrinsics"]("tartanair")[0]}
+    NAMES = ("brightness", "contrast", "saturation", "hue")
+
+    class ColorJitter:                                   # the PIL path of torchvision's ColorJitter with pinned draws
+        def __init__(self, *a, **k):
+            pass
+
+        def __call__(self, img):
+            par = next(state["jitter"])
+            for op in par["order"]:
+                f = par[NAMES[op]]
+                if op == 0:
+                    img = ImageEnhance.Brightness(img).enhance(f)
+                elif op == 1:
+                    img = ImageEnhance.Contrast(img).enhance(f)
+                elif op == 2:
+                    img = ImageEnhance.Color(img).enhance(f)
+                else:
+                    h, s, v = img.convert("HSV").split()
+                    np_h = np.array(h, dtype=np.uint8)
+                    np_h = (np_h.astype(np.int64) + int(np.array(int(f * 255)).astype(np.uint8))).astype(np.uint8)    # uint8 wrap-around
+                    img = Image.merge("HSV", (Image.fromarray(np_h, "L"), s, v)).convert("RGB")
+            return img
+
+    def adjust_gamma(img, gamma, gain=1):
+        table = [min(255, int((255 + 1 - 1e-3) * gain * pow(e / 255.0, gamma))) for e in range(256)] * 3
+        out = img.point(table)
+        state["stages"].append(np.array(out, dtype=np.uint8))
+        return out
+
+    base.transforms.ColorJitter = ColorJitter
+    base.transforms.functional.adjust_gamma = adjust_gamma
+
+    class ThrowAway(base.StereoDatasetBase):
+        def Loader(self, image_path):
+            return base.pil_loader(os.path.join(self.root, image_path))
+
+        def intrinsicLoader(self, intrinsic_path):
+            K = K_of["tartanair"].copy()
+            full_K = K.copy()
+            return K, full_K, self.resolution
+
+    def picture(seed, tag, H, W, block=2):
+        """noise in block x block tiles (it keeps the files small) with greys, saturated primaries / secondaries, black, white and
+        pixels with two equal channels planted"""
+        tiles = synth._rs(seed, tag).randint(0, 256, size=((H + block - 1) // block, (W + block - 1) // block, 3)).astype(np.uint8)
+        img = np.repeat(np.repeat(tiles, block, axis=0), block, axis=1)[:H, :W].copy()
+        img[0] = img[0, :, :1]                                                   # greys
+        prim = np.array([(255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0), (0, 255, 255), (255, 0, 255), (0, 0, 0), (255, 255, 255)], dtype=np.uint8)
+        img[1, :len(prim)] = prim[:min(len(prim), W)]
+        img[2, :, 1] = img[2, :, 0]                                              # R == G
+        img[3, :, 2] = img[3, :, 1]                                              # G == B
+        img[4, :, 2] = img[4, :, 0]                                              # R == B
+        return img
+
+    def run(tmp, lefts, rights, size, rows, crops, rects, color=True):
+        """rows[e][b]: dict(order, brightness, contrast, saturation, hue, gamma); rects[b]: list of (sh, sw, occh, occw) for the right
+        eye.  One dataset object per image (do_color_aug and the pins are per object)."""
+        B = len(lefts)
+        Hs, Ws = lefts[0].shape[:2]
+        out = {k: [] for k in ("color_l", "color_r", "aug_l", "aug_r", "stage_l", "stage_r")}
+        for b in range(B):
+            for side, img in (("left", lefts[b]), ("right", rights[b])):
+                Image.fromarray(img, "RGB").save(os.path.join(tmp, "%s.png" % side))
+            ann = os.path.join(tmp, "ann.json")
+            with open(ann, "w") as fh:
+                json.dump([{"0": {"left_image_path": "left.png", "right_image_path": "right.png"}}], fh)
+            state["jitter"] = iter([rows[0][b], rows[1][b]])
+            state["stages"] = []
+            uni = iter([v for e in (0, 1) for v in (1.0, rows[e][b]["gamma"])])          # AdjustGamma: gain, then gamma
+            ints = iter(list(crops[b]))
+            base.random = types.SimpleNamespace(random=lambda: 1.0 if color else 0.0, randint=lambda lo, hi: next(ints),
+                                                uniform=lambda lo, hi: next(uni))
+            # occlusion: binomial 1 for every key (only the right eye's color_aug takes it), the count, then per rectangle occw, occh, sw, sh
+            rc = rects[b]
+            np_uni = iter([float(v) + 0.25 for (sh, sw, oh, ow) in rc for v in (ow, oh, sw, sh)])
+            real = (np.random.binomial, np.random.randint, np.random.uniform)
+            np.random.binomial = lambda n, p: 1 if rc else 0
+            np.random.randint = lambda lo, hi: len(rc)
+            np.random.uniform = lambda lo, hi: next(np_uni)
+            np.random.seed(1234 + b)
+            try:
+                ThrowAway.resolution = (Hs, Ws)
+                ds = ThrowAway(ann, tmp, size[0], size[1], [0], is_train=True)
+                assert ds.do_color_aug == color
+                sm = ds[0]
+            finally:
+                np.random.binomial, np.random.randint, np.random.uniform = real
+                base.random = pyrandom
+            assert next(np_uni, None) is None and next(ints, None) is None
+            if color:
+                assert len(state["stages"]) == 2 and next(state["jitter"], None) is None
+                out["stage_l"].append(state["stages"][0]); out["stage_r"].append(state["stages"][1])
+            else:
+                out["stage_l"].append(lefts[b]); out["stage_r"].append(rights[b])
+            for k, key in (("color_l", ("color", 0, "l")), ("color_r", ("color", 0, "r")), ("aug_l", ("color_aug", 0, "l")),
+                           ("aug_r", ("color_aug", 0, "r"))):
+                v = sm[key]
+                assert v.dtype == torch.float32 and tuple(v.shape) == (3,) + tuple(size), (key, v.dtype, v.shape)
+                out[k].append(v.numpy().copy())
+        return {k: np.stack(v) for k, v in out.items()}
+
+    def pack(lefts, rights, size, rows, crops, rects, r):
+        B = len(lefts)
+        order = np.full((2, B, 4), 4, dtype=np.int64)
+        factors = np.zeros((2, B, 4), dtype=np.float64)
+        gam = np.zeros((2, B), dtype=np.float64)
+        for e in (0, 1):
+            for b in range(B):
+                order[e, b, :len(rows[e][b]["order"])] = rows[e][b]["order"]
+                factors[e, b] = [rows[e][b][n] for n in NAMES]
+                gam[e, b] = rows[e][b]["gamma"]
+        rc = np.zeros((B, 4, 4), dtype=np.int64)
+        for b in range(B):
+            for k, q in enumerate(rects[b]):
+                rc[b, k] = q
+        return dict(left=np.stack(lefts), right=np.stack(rights), size=np.array(size), order=order, factors=factors, gamma=gam,
+                    crop=np.array(crops, dtype=np.int64), rects=rc, nrect=np.array([len(q) for q in rects]), **r)
+
+    def par(order=(), brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, gamma=1.0):
+        return dict(order=list(order), brightness=brightness, contrast=contrast, saturation=saturation, hue=hue, gamma=gamma)
+
+    lines = ["augment_*.npz: tools/gen_golden.py --only-augment, numpy %s, PIL %s, torch %s CPU -- the reference's own" % (np.__version__, PIL.__version__, torch.__version__),
+             "StereoDatasetBase.do_transform (architecture/data/datasets/base.py:99-187, is_train=True) on a throw-away dataset of seeded",
+             "uint8 PNGs, one dataset object per image.  torchvision is not installed: ToTensor / normalize / Compose are the stand-ins of",
+             "PROVENANCE_prepare.txt; ColorJitter and functional.adjust_gamma are stood in by the PIL calls torchvision's PIL path makes --",
+             "ImageEnhance.Brightness / Contrast / Color(img).enhance(f); img.convert('HSV'), H += uint8(int(f * 255)) with uint8 wrap-around,",
+             "Image.merge('HSV', ...).convert('RGB'); img.point(table * 3) -- with the order and the factors taken from a recorded list",
+             "instead of torch's random stream.  Gamma-table convention: the TRUNCATING integer table of torchvision's current PIL path,",
+             "min(255, int((255 + 1 - 1e-3) * gain * (e / 255.0) ** gamma)); gamma = 1 is then the identity.  (Older torchvision versions hand",
+             "Image.point a float table, which PIL 12 rounds: 113-127 of the 256 entries differ.  The reference pins no version.)",
+             "Pinned: random.random (do_color_aug), random.uniform (gain 1.0, the recorded gamma), random.randint (the recorded crop",
+             "origins), np.random.binomial / randint / uniform (the recorded rectangles; each uniform returns the recorded integer + 0.25).",
+             "np.random.normal is numpy's own, seeded: the values inside rectangles are the reference's noise and are NOT compared.",
+             "stage_l / stage_r: the uint8 frame adjust_gamma returned (the full frame after all colour operations).",
+             "Expected outputs: the float32 tensors do_transform returned."]
+    seed0 = synth.SEED0 + 1000
+    total = 0
+
+    def finish(name, arrs, note):
+        nonlocal total
+        save(name, **arrs)
+        sz = os.path.getsize(os.path.join(OUT, name + ".npz"))
+        total += sz
+        lines.append("%-20s B=%d %s -> %s  %s" % (name, arrs["left"].shape[0], tuple(arrs["left"].shape[1:3]), tuple(int(v) for v in arrs["size"]), note))
+
+    with tempfile.TemporaryDirectory() as tmp:
+        # --- each operation alone: both ends and the middle of its range; gamma alone
+        H, W = 20, 28
+        L, R = picture(seed0, "opsL", H, W), picture(seed0, "opsR", H, W)[::-1].copy()
+        ps = [par((0,), brightness=v) for v in (0.4, 1.2, 2.0)] + [par((1,), contrast=v) for v in (0.5, 1.0, 1.5)] + \
+             [par((2,), saturation=v) for v in (0.5, 1.0, 1.5)] + [par((3,), hue=v) for v in (-0.1, 0.0, 0.1)] + \
+             [par((), gamma=v) for v in (0.8, 1.0, 1.2)]
+        B = len(ps)
+        rows = [ps, ps]
+        r = run(tmp, [L] * B, [R] * B, (H, W), rows, [()] * B, [[]] * B)
+        finish("augment_ops", pack([L] * B, [R] * B, (H, W), rows, [(0, 0)] * B, [[]] * B, r),
+               "brightness 0.4 / 1.2 / 2.0, contrast and saturation 0.5 / 1.0 / 1.5, hue -0.1 / 0 / 0.1, gamma 0.8 / 1.0 / 1.2, each alone")
+
+        # --- all 24 orders with fixed factors: left eye order k, right eye order 23 - k
+        import itertools
+        perms = list(itertools.permutations(range(4)))
+        L, R = picture(seed0 + 1, "ordL", H, W), picture(seed0 + 1, "ordR", H, W)
+        fx = dict(brightness=1.3, contrast=0.7, saturation=1.4, hue=0.07, gamma=1.0)
+        rows = [[par(perms[k], **fx) for k in range(12)], [par(perms[23 - k], **fx) for k in range(12)]]
+        r = run(tmp, [L] * 12, [R] * 12, (H, W), rows, [()] * 12, [[]] * 12)
+        finish("augment_orders", pack([L] * 12, [R] * 12, (H, W), rows, [(0, 0)] * 12, [[]] * 12, r),
+               "all 24 orders (left: k, right: 23 - k), brightness 1.3, contrast 0.7, saturation 1.4, hue 0.07")
+
+        # --- the full chain + gamma + crop, B=2, different parameters per image and eye
+        Ls = [picture(seed0 + 2, "chL%d" % b, 37, 57) for b in range(2)]
+        Rs = [picture(seed0 + 2, "chR%d" % b, 37, 57) for b in range(2)]
+        rows = [[par((2, 0, 3, 1), 0.62, 1.37, 0.81, -0.083, 0.87), par((1, 3, 0, 2), 1.71, 0.58, 1.22, 0.031, 1.16)],
+                [par((3, 2, 1, 0), 1.05, 0.93, 1.45, 0.095, 1.04), par((0, 1, 2, 3), 0.45, 1.49, 0.55, -0.049, 0.93)]]
+        crops = [(0, 17), (13, 3)]
+        r = run(tmp, Ls, Rs, (24, 40), rows, crops, [[], []])
+        finish("augment_chain", pack(Ls, Rs, (24, 40), rows, crops, [[], []], r), "full chain + gamma + crop, per image and eye")
+
+        # --- occlusion: 2, 3 and 4 rectangles, overlapping and touching the window's border; the left eye untouched
+        Ls = [picture(seed0 + 3, "ocL%d" % b, 44, 66, 3) for b in range(3)]
+        Rs = [picture(seed0 + 3, "ocR%d" % b, 44, 66, 3) for b in range(3)]
+        rows = [[par((0, 1, 2, 3), 1.1, 0.9, 1.2, 0.02, 0.95)] * 3, [par((3, 1, 0, 2), 0.8, 1.3, 0.7, -0.06, 1.1)] * 3]
+        rects = [[(0, 0, 9, 12), (5, 8, 10, 10)],
+                 [(30, 48, 10, 12), (2, 50, 12, 7), (20, 20, 6, 30)],
+                 [(0, 40, 15, 20), (10, 30, 20, 20), (25, 0, 15, 35), (12, 33, 5, 5)]]
+        crops = [(1, 2), (4, 6), (0, 0)]
+        r = run(tmp, Ls, Rs, (40, 60), rows, crops, rects)
+        finish("augment_occlusion", pack(Ls, Rs, (40, 60), rows, crops, rects, r), "2 / 3 / 4 rectangles, overlapping, touching the border")
+
+        # --- one case large enough for patches of the default size
+        Ls, Rs = [picture(seed0 + 4, "lgL", 130, 210, 6)], [picture(seed0 + 4, "lgR", 130, 210, 6)]
+        rows = [[par((1, 0, 2, 3), 1.4, 1.2, 0.9, 0.05, 0.9)], [par((2, 3, 1, 0), 0.7, 0.8, 1.3, -0.02, 1.15)]]
+        rects = [[(3, 10, 50, 50), (70, 148, 50, 52)]]
+        r = run(tmp, Ls, Rs, (120, 200), rows, [(7, 5)], rects)
+        finish("augment_large", pack(Ls, Rs, (120, 200), rows, [(7, 5)], rects, r), "two rectangles of the default minimum size, one touching the corner")
+
+        # --- identity: no colour augmentation drawn, no rectangle
+        Ls = [picture(seed0 + 5, "idL%d" % b, 29, 43) for b in range(2)]
+        Rs = [picture(seed0 + 5, "idR%d" % b, 29, 43) for b in range(2)]
+        rows = [[par()] * 2, [par()] * 2]
+        crops = [(2, 0), (5, 11)]
+        r = run(tmp, Ls, Rs, (24, 32), rows, crops, [[], []], color=False)
+        finish("augment_identity", pack(Ls, Rs, (24, 32), rows, crops, [[], []], r), "do_color_aug False")
+    assert total < 700 * 1024, total
+    lines.append("total %.0f KB" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_augment.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -1254,6 +1482,9 @@ def main():
         return
     if "--only-prepare" in sys.argv:
         prepare_cases(M)
+        return
+    if "--only-augment" in sys.argv:
+        augment_cases(M)
         return
     if "--only-backbone-memory" in sys.argv:
         backbone_memory_cases(M)

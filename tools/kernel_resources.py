@@ -3,6 +3,7 @@
     python tools/kernel_resources.py temporalstereo_amd/csrc/block_cost.hip [name filter]
     python tools/kernel_resources.py temporalstereo_amd/csrc/render.hip          (the rendering kernels: no scratch)
     python tools/kernel_resources.py temporalstereo_amd/csrc/preprocess.hip      (the frame-preparation kernels: no scratch)
+    python tools/kernel_resources.py temporalstereo_amd/csrc/augment.hip         (the augmentation kernels: no scratch)
 """
 import re
 import subprocess
