@@ -34,8 +34,8 @@ import torch
 
 from . import _lib
 from .functional import _stream
-from .preprocess import (CHW, IMAGENET_MEAN, IMAGENET_STD, _U16, _frames, _on_gpu, _out_tensor, _three, default_num_scales,
-                         intrinsics_pyramid)
+from ._frameio import _batch_dict, _color_outputs, _frames, _gt_rows, _on_gpu, _three, _u16_map
+from .preprocess import CHW, IMAGENET_MEAN, IMAGENET_STD, default_num_scales
 
 ROW_INTS = 96                               # TS_AUGMENT_ROW_INTS (include/ts_hip.h)
 MAX_RECTS = 4                               # TS_AUGMENT_MAX_RECTS
@@ -297,24 +297,7 @@ def augment_frames(left, right, aug, size, *, mean=IMAGENET_MEAN, std=IMAGENET_S
         raise ValueError("%s: an image of shape %s cannot be cropped to %s" % (what, (Hs, Ws), (H, W)))
     sides = ('l', 'r') if right is not None else ('l',)
     table = _table_for(what, aug, B, len(sides), dev, (Hs, Ws), (H, W))
-    shape = (B, 3, H, W)
-    if out is not None:
-        outs = tuple(out) if isinstance(out, (tuple, list)) else (out,)
-        if len(outs) != len(sides):
-            raise ValueError("%s: %d out tensors for %d eyes" % (what, len(outs), len(sides)))
-        strides = {_out_tensor(what, t, shape, dev) for t in outs}
-        if len(strides) != 1:
-            raise ValueError("%s: the out tensors must share one batch stride (got %s)" % (what, sorted(strides)))
-        aug_stride = strides.pop()
-    else:
-        outs = tuple(torch.empty(shape, device=dev, dtype=torch.float32) for _ in sides)
-        aug_stride = 3 * H * W
-    res = {}
-    for s, t in zip(sides, outs):
-        res['color_aug_' + s] = t
-    if color:
-        for s in sides:
-            res['color_' + s] = torch.empty(shape, device=dev, dtype=torch.float32)
+    res, aug_stride = _color_outputs(what, sides, B, H, W, (H, W), out, color, dev)
     L = _lib.lib()
     nbytes = int(L.ts_frames_augment_workspace_bytes(B, Hs, Ws))
     work = torch.empty((nbytes // 8,), device=dev, dtype=torch.int64)
@@ -332,23 +315,10 @@ def disp_window_from_uint16(raw, aug, size, scale=256.0, with_valid=False):
     [B,1,Hs,Ws] ([Hs,Ws] for B = 1) -> fp32 [B,1,H,W]; with_valid also the mask raw > 0 (bool).  raw: uint16 / int16
     (reinterpreted) / int32 (low 16 bits; a cast on the device, not while a launch plan is recorded), as disp_from_uint16."""
     what = "disp_window_from_uint16"
-    _on_gpu(what, raw)
-    if raw.dtype == torch.int32:
-        if _lib.recording():
-            raise RuntimeError("%s: an int32 map needs a cast that a launch plan would not replay; hand over 16-bit storage" % what)
-        raw = raw.to(torch.int16)
-    elif raw.dtype != torch.int16 and (_U16 is None or raw.dtype != _U16):
-        raise TypeError("%s: raw must be uint16, int16 (reinterpreted) or int32 (got %s of shape %s)" % (what, raw.dtype, tuple(raw.shape)))
-    if raw.dim() not in (2, 3, 4) or (raw.dim() == 4 and raw.shape[1] != 1) or raw.numel() == 0:
-        raise ValueError("%s: raw must be a non-empty [H,W], [B,H,W] or [B,1,H,W] map (got %s)" % (what, tuple(raw.shape)))
-    if not float(scale) > 0:
-        raise ValueError("%s: scale %r" % (what, scale))
-    B = raw.shape[0] if raw.dim() > 2 else 1
-    Hs, Ws = raw.shape[-2:]
+    r, (B, Hs, Ws, _) = _u16_map(what, raw, scale)
     H, W = (int(v) for v in size)
     if H <= 0 or W <= 0 or H > Hs or W > Ws:
         raise ValueError("%s: a map of shape %s cannot be cropped to %s" % (what, (Hs, Ws), (H, W)))
-    r = _lib.contiguous(raw)
     table = _table_for(what, aug, B, 1, r.device, (Hs, Ws), (H, W))
     disp = torch.empty((B, 1, H, W), device=r.device, dtype=torch.float32)
     valid = torch.empty((B, 1, H, W), device=r.device, dtype=torch.uint8) if with_valid else None
@@ -376,36 +346,10 @@ def prepare_train_batch(left, right, K_norm, baseline, size, aug, *, timestamp=0
         raise ValueError("%s: the window's size is needed" % what)
     size = tuple(int(v) for v in size)
     fr = augment_frames(left, right, aug, size, mean=mean, std=std, layout=layout, color=True, out=out)
-    if fr['color_aug_l'].dim() == 3:
-        fr = {k: v.unsqueeze(0) for k, v in fr.items()}
-    B = fr['color_aug_l'].shape[0]
-    dev = fr['color_aug_l'].device
-    t = timestamp
-    batch = {('color', t, 'l'): fr['color_l'], ('color', t, 'r'): fr['color_r'],
-             ('color_aug', t, 'l'): fr['color_aug_l'], ('color_aug', t, 'r'): fr['color_aug_r']}
-    S = default_num_scales(size) if num_scales is None else int(num_scales)
-    _on_gpu(what, K_norm)
-    kn = K_norm if K_norm.dim() == 3 else K_norm.unsqueeze(0)
-    if kn.shape[0] not in (1, B):
-        raise ValueError("%s: K_norm of shape %s for a batch of %d" % (what, tuple(K_norm.shape), B))
     if k_size is None:
         k_size = (left.shape[-3], left.shape[-2]) if layout == 'HWC' else (left.shape[-2], left.shape[-1])
-    K, inv = intrinsics_pyramid(kn, k_size, S)
-    if K.shape[0] != B:
-        K, inv = K.expand(B, S, 4, 4), inv.expand(B, S, 4, 4)
-    for s in range(S):
-        batch[('K', s)] = K[:, s]
-        batch[('inv_K', s)] = inv[:, s]
-    if torch.is_tensor(baseline):
-        _on_gpu(what, baseline)
-        if baseline.numel() != B:
-            raise ValueError("%s: baseline of shape %s for a batch of %d" % (what, tuple(baseline.shape), B))
-        batch['baseline'] = baseline.to(torch.float32).reshape(B, 1, 1, 1)
-    else:
-        batch['baseline'] = torch.full((B, 1, 1, 1), float(baseline), device=dev, dtype=torch.float32)
+    S = default_num_scales(size) if num_scales is None else int(num_scales)
+    batch = _batch_dict(what, fr, K_norm, k_size, S, baseline, timestamp)
     if disp_gt_raw is not None:
-        g = disp_gt_raw if disp_gt_raw.dim() > 2 else disp_gt_raw.unsqueeze(0)
-        if g.shape[0] != B:
-            raise ValueError("%s: disp_gt_raw of shape %s for a batch of %d" % (what, tuple(disp_gt_raw.shape), B))
-        batch[('disp_gt', t, 'l')] = disp_window_from_uint16(g, aug, size, gt_scale)
+        batch[('disp_gt', timestamp, 'l')] = disp_window_from_uint16(_gt_rows(what, disp_gt_raw, batch), aug, size, gt_scale)
     return batch

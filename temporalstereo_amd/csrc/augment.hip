@@ -12,7 +12,7 @@
 //                        contrast operation returns at once, and the operations before contrast are the only ones evaluated.
 // augment_apply_kernel   grid (x, N): the window's pixels only.  A block adds its image's P partials, m = int(sum / pixels + 0.5) with
 //                        the division in double, and recomputes the chain per pixel from the source bytes: operations in the row's
-//                        order, the row's 256-byte gamma table, then the normalisation tables of frames_prepare_kernel (correctly
+//                        order, the row's 256-byte gamma table, then the normalisation tables of frame_io.hpp (ts::ByteTables: correctly
 //                        rounded divisions, built once per block in LDS).  `color` is byte / 255 of the UN-augmented window.  One
 //                        lane = four horizontally adjacent pixels of all three channels; 12 source bytes as three dwords where the
 //                        address allows, one 16-byte store per channel and output.  A pixel inside one of the row's rectangles
@@ -27,7 +27,7 @@
 //   blend         t = deg + f * (x - deg) in fp32, two roundings (never fused); 0 if t <= 0, 255 if t >= 255, else truncated
 //   brightness    deg = 0;  contrast  deg = m;  saturation  deg = grey(pixel)
 //   hue           RGB -> HSV bytes, H += shift (mod 256), HSV -> RGB bytes (the colorsys formulas of PIL's Convert.c)
-#include "ts_common.hpp"
+#include "frame_io.hpp"
 
 #include <climits>
 
@@ -58,13 +58,11 @@ struct AugArgs {
   float* aug_r;
   long long color_stride, aug_stride;
   int B, N, Hs, Ws, H, W, P;
-  float m0, m1, m2, s0, s1, s2;
+  float mean[3], sd[3];
 };
 
-struct Tables {
-  float v[256];                 // byte / 255
-  float n[3][256];              // (v - mean[c]) / std[c]
-};
+using ts::load_quad;
+using ts::store4;
 
 __device__ __forceinline__ int grey_of(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 
@@ -150,41 +148,6 @@ __device__ __forceinline__ int contrast_at(const int* row) {
   return 4;
 }
 
-// the bytes of nv <= 4 adjacent pixels of row ys from column xs of image b: px[v][c]
-template <bool CHW>
-__device__ __forceinline__ void load_quad(const unsigned char* __restrict__ src, int b, int Hs, int Ws, int ys, int xs, int nv,
-                                          unsigned (&px)[4][3]) {
-#pragma unroll
-  for (int v = 0; v < 4; ++v) px[v][0] = px[v][1] = px[v][2] = 0u;
-  if constexpr (!CHW) {
-    const unsigned char* p = src + ((static_cast<size_t>(b) * Hs + ys) * Ws + xs) * 3;
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-      const unsigned* d = reinterpret_cast<const unsigned*>(p);
-      const unsigned w[3] = {d[0], d[1], d[2]};
-#pragma unroll
-      for (int k = 0; k < 12; ++k) px[k / 3][k % 3] = (w[k / 4] >> (8 * (k % 4))) & 255u;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k / 3 < nv) px[k / 3][k % 3] = p[k];
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const unsigned char* p = src + ((static_cast<size_t>(b) * 3 + c) * Hs + ys) * Ws + xs;
-      if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-        const unsigned w = *reinterpret_cast<const unsigned*>(p);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) px[v][c] = (w >> (8 * v)) & 255u;
-      } else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-          if (v < nv) px[v][c] = p[v];
-      }
-    }
-  }
-}
-
 // sum over the block; the result is valid in every lane
 __device__ __forceinline__ unsigned long long block_sum(unsigned long long v, unsigned long long* red) {
 #pragma unroll
@@ -256,7 +219,7 @@ __device__ __forceinline__ float noise_at(unsigned seed_lo, unsigned seed_hi, un
 
 template <bool CHW>
 __global__ void __launch_bounds__(kThreads) augment_apply_kernel(AugArgs a, int items) {
-  __shared__ Tables t;
+  __shared__ ts::ByteTables t;
   __shared__ int row[kHead];
   __shared__ unsigned char gam[256];
   __shared__ unsigned long long red[kThreads / ts::kWave];
@@ -265,15 +228,10 @@ __global__ void __launch_bounds__(kThreads) augment_apply_kernel(AugArgs a, int 
   const int* trow = a.table + static_cast<size_t>(n) * kRow;
   {
     const int i = threadIdx.x;                           // kThreads == 256: one byte value per lane
-    const float v = __fdiv_rn(static_cast<float>(i), 255.f);
-    t.v[i] = v;
-    t.n[0][i] = __fdiv_rn(__fsub_rn(v, a.m0), a.s0);
-    t.n[1][i] = __fdiv_rn(__fsub_rn(v, a.m1), a.s1);
-    t.n[2][i] = __fdiv_rn(__fsub_rn(v, a.m2), a.s2);
     if (i < kHead) row[i] = trow[i];
     gam[i] = static_cast<unsigned char>((static_cast<unsigned>(trow[R_GAMMA + (i >> 2)]) >> (8 * (i & 3))) & 255u);
   }
-  __syncthreads();
+  ts::build_byte_tables(a.mean, a.sd, t);                // ends in the barrier that row[] and gam[] need too
   const bool with_gamma = (row[R_FLAGS] & TS_AUGMENT_GAMMA) != 0;
   const bool with_ops = static_cast<unsigned>(row[R_ORDER]) != 0x04040404u;
   int m = 0;
@@ -289,7 +247,6 @@ __global__ void __launch_bounds__(kThreads) augment_apply_kernel(AugArgs a, int 
   const int oy = min(max(row[R_CH], 0), a.Hs - a.H), ox = min(max(row[R_CW], 0), a.Ws - a.W);   // clamped, never read out of bounds
   const int n_rect = min(max(row[R_NRECT], 0), TS_AUGMENT_MAX_RECTS);
   const unsigned seed_lo = static_cast<unsigned>(row[R_SEED]), seed_hi = static_cast<unsigned>(row[R_SEED + 1]);
-  const float mean[3] = {a.m0, a.m1, a.m2}, sd[3] = {a.s0, a.s1, a.s2};
   const int per_row = (a.W + 3) >> 2;
   for (int it = blockIdx.x * kThreads + threadIdx.x; it < items; it += gridDim.x * kThreads) {
     const int y = it / per_row, x0 = (it - y * per_row) * 4;
@@ -300,14 +257,7 @@ __global__ void __launch_bounds__(kThreads) augment_apply_kernel(AugArgs a, int 
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const float q[4] = {t.v[px[0][c]], t.v[px[1][c]], t.v[px[2][c]], t.v[px[3][c]]};
-        float* o = color + static_cast<size_t>(b) * a.color_stride + (static_cast<size_t>(c) * a.H + y) * a.W + x0;
-        if (nv == 4 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-          *reinterpret_cast<float4*>(o) = make_float4(q[0], q[1], q[2], q[3]);
-        } else {
-#pragma unroll
-          for (int v = 0; v < 4; ++v)
-            if (v < nv) o[v] = q[v];
-        }
+        store4(color + static_cast<size_t>(b) * a.color_stride + (static_cast<size_t>(c) * a.H + y) * a.W + x0, nv, q);
       }
     }
     if (aug == nullptr) continue;
@@ -329,7 +279,7 @@ __global__ void __launch_bounds__(kThreads) augment_apply_kernel(AugArgs a, int 
         const unsigned ry = static_cast<unsigned>(y - row[R_RECT + 4 * k]), rx = static_cast<unsigned>(x0 + v - row[R_RECT + 4 * k + 1]);
 #pragma unroll
         for (int c = 0; c < 3; ++c)
-          q[c][v] = __fdiv_rn(__fsub_rn(noise_at(seed_lo, seed_hi, rx, ry, c, k), mean[c]), sd[c]);
+          q[c][v] = __fdiv_rn(__fsub_rn(noise_at(seed_lo, seed_hi, rx, ry, c, k), a.mean[c]), a.sd[c]);
       } else {
         int r = px[v][0], g = px[v][1], bl = px[v][2];
         if (with_ops) chain(row, 4, m, r, g, bl);
@@ -340,16 +290,8 @@ __global__ void __launch_bounds__(kThreads) augment_apply_kernel(AugArgs a, int 
       }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float* o = aug + static_cast<size_t>(b) * a.aug_stride + (static_cast<size_t>(c) * a.H + y) * a.W + x0;
-      if (nv == 4 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-        *reinterpret_cast<float4*>(o) = make_float4(q[c][0], q[c][1], q[c][2], q[c][3]);
-      } else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-          if (v < nv) o[v] = q[c][v];
-      }
-    }
+    for (int c = 0; c < 3; ++c)
+      store4(aug + static_cast<size_t>(b) * a.aug_stride + (static_cast<size_t>(c) * a.H + y) * a.W + x0, nv, q[c]);
   }
 }
 
@@ -364,32 +306,13 @@ __global__ void __launch_bounds__(kThreads) disp_u16_window_kernel(const unsigne
   for (int it = blockIdx.x * kThreads + threadIdx.x; it < items; it += gridDim.x * kThreads) {
     const int y = it / per_row, x0 = (it - y * per_row) * 4;
     const int nv = min(4, W - x0);
-    const unsigned short* p = raw + (static_cast<size_t>(b) * Hs + y + oy) * Ws + x0 + ox;
-    unsigned r[4] = {0u, 0u, 0u, 0u};
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 7u) == 0) {
-      const uint2 w = *reinterpret_cast<const uint2*>(p);
-      r[0] = w.x & 65535u; r[1] = w.x >> 16; r[2] = w.y & 65535u; r[3] = w.y >> 16;
-    } else {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        if (v < nv) r[v] = p[v];
-    }
     const size_t o = (static_cast<size_t>(b) * H + y) * W + x0;
-    float* d = disp + o;
-    const float q[4] = {r[0] > 0u ? __fdiv_rn(static_cast<float>(r[0]), scale) : 0.f, r[1] > 0u ? __fdiv_rn(static_cast<float>(r[1]), scale) : 0.f,
-                        r[2] > 0u ? __fdiv_rn(static_cast<float>(r[2]), scale) : 0.f, r[3] > 0u ? __fdiv_rn(static_cast<float>(r[3]), scale) : 0.f};
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(d) & 15u) == 0) {
-      *reinterpret_cast<float4*>(d) = make_float4(q[0], q[1], q[2], q[3]);
-    } else {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        if (v < nv) d[v] = q[v];
-    }
-    if (valid != nullptr) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        if (v < nv) valid[o + v] = r[v] > 0u ? 1 : 0;
-    }
+    unsigned r[4];
+    float q[4];
+    ts::load_u16_quad(raw + (static_cast<size_t>(b) * Hs + y + oy) * Ws + x0 + ox, nv, r);
+    ts::decode_u16_quad(r, scale, q);
+    store4(disp + o, nv, q);
+    if (valid != nullptr) ts::store_valid4(valid + o, nv, r);
   }
 }
 
@@ -398,12 +321,6 @@ int parts_for(int Hs, int Ws) {
   long long p = (pixels + kStatPixels - 1) / kStatPixels;
   if (p > kMaxParts) p = kMaxParts;
   return static_cast<int>(p < 1 ? 1 : p);
-}
-
-int blocks_x(int items) {
-  int nb = (items + kThreads - 1) / kThreads;
-  if (nb > kMaxBlocksX) nb = kMaxBlocksX;
-  return nb < 1 ? 1 : nb;
 }
 
 }  // namespace
@@ -417,27 +334,19 @@ extern "C" int ts_frames_augment_fwd(const void* left, const void* right, int B,
                                      float mean2, float std0, float std1, float std2, int H, int W, const int* table, float* color_l,
                                      float* color_r, long long color_stride, float* color_aug_l, float* color_aug_r,
                                      long long color_aug_stride, void* workspace, size_t workspace_bytes, void* stream) {
-  TS_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "frames_augment: bad size (B %d, source %dx%d, window %dx%d)", B,
-             Hs, Ws, H, W);
-  TS_REQUIRE((flags & ~TS_PREPARE_CHW) == 0, TS_ERR_SHAPE, "frames_augment: unknown flags %d", flags);
-  TS_REQUIRE_PTR(left); TS_REQUIRE_PTR(table); TS_REQUIRE_PTR(workspace);
-  TS_REQUIRE(color_l || color_r || color_aug_l || color_aug_r, TS_ERR_NULL, "frames_augment: no output selected");
-  TS_REQUIRE(right != nullptr || (color_r == nullptr && color_aug_r == nullptr), TS_ERR_NULL,
-             "frames_augment: an output of the right eye without a right image");
-  TS_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, TS_ERR_SHAPE, "frames_augment: a zero std");
+  if (int rc = ts::frames_check_args("frames_augment", "window", B, Hs, Ws, H, W, flags,
+                                     {{"left", left}, {"table", table}, {"workspace", workspace}}, right, color_l, color_r, color_aug_l,
+                                     color_aug_r, std0, std1, std2))
+    return rc;
   TS_REQUIRE(H <= Hs && W <= Ws, TS_ERR_SHAPE, "frames_augment: a %dx%d window does not fit a %dx%d image", H, W, Hs, Ws);
   const int N = right != nullptr ? 2 * B : B;
   TS_REQUIRE(N <= 65535, TS_ERR_SHAPE, "frames_augment: a batch of %d", B);
   TS_REQUIRE(static_cast<long long>(N) * Hs * Ws <= INT_MAX / 4, TS_ERR_SHAPE, "frames_augment: more than 2^29-1 pixels");
   TS_REQUIRE(workspace_bytes >= ts_frames_augment_workspace_bytes(B, Hs, Ws), TS_ERR_SHAPE, "frames_augment: workspace of %zu bytes, %zu needed",
              workspace_bytes, ts_frames_augment_workspace_bytes(B, Hs, Ws));
-  if (color_l || color_r)
-    TS_REQUIRE(color_stride >= 3LL * H * W, TS_ERR_SHAPE, "frames_augment: color_stride %lld below 3 x %d x %d", color_stride, H, W);
-  if (color_aug_l || color_aug_r)
-    TS_REQUIRE(color_aug_stride >= 3LL * H * W, TS_ERR_SHAPE, "frames_augment: color_aug_stride %lld below 3 x %d x %d", color_aug_stride, H, W);
-  for (const void* p : {static_cast<const void*>(color_l), static_cast<const void*>(color_r), static_cast<const void*>(color_aug_l),
-                        static_cast<const void*>(color_aug_r), static_cast<const void*>(table)})
-    TS_REQUIRE((reinterpret_cast<uintptr_t>(p) & 3u) == 0, TS_ERR_ALIGN, "frames_augment: a 4-byte pointer is not 4-byte aligned");
+  if (int rc = ts::frames_check_outputs("frames_augment", H, W, H, W, color_l, color_r, color_stride, color_aug_l, color_aug_r,
+                                        color_aug_stride, table))
+    return rc;
   TS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, TS_ERR_ALIGN, "frames_augment: workspace not 8-byte aligned");
 
   AugArgs a{};
@@ -446,7 +355,7 @@ extern "C" int ts_frames_augment_fwd(const void* left, const void* right, int B,
   a.color_l = color_l; a.color_r = color_r; a.aug_l = color_aug_l; a.aug_r = color_aug_r;
   a.color_stride = color_stride; a.aug_stride = color_aug_stride;
   a.B = B; a.N = N; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.P = parts_for(Hs, Ws);
-  a.m0 = mean0; a.m1 = mean1; a.m2 = mean2; a.s0 = std0; a.s1 = std1; a.s2 = std2;
+  a.mean[0] = mean0; a.mean[1] = mean1; a.mean[2] = mean2; a.sd[0] = std0; a.sd[1] = std1; a.sd[2] = std2;
   const bool chw = (flags & TS_PREPARE_CHW) != 0;
   const hipStream_t st = ts::as_stream(stream);
   if (chw) hipLaunchKernelGGL(augment_stats_kernel<true>, dim3(a.P, N), dim3(kThreads), 0, st, a);
@@ -454,7 +363,7 @@ extern "C" int ts_frames_augment_fwd(const void* left, const void* right, int B,
   const int rc = ts::launched("augment_stats_kernel");
   if (rc != TS_OK) return rc;
   const int items = H * ((W + 3) / 4);
-  const dim3 grid(blocks_x(items), N);
+  const dim3 grid(ts::grid_blocks(items, kThreads, kMaxBlocksX), N);
   if (chw) hipLaunchKernelGGL(augment_apply_kernel<true>, grid, dim3(kThreads), 0, st, a, items);
   else hipLaunchKernelGGL(augment_apply_kernel<false>, grid, dim3(kThreads), 0, st, a, items);
   return ts::launched("augment_apply_kernel");
@@ -472,7 +381,7 @@ extern "C" int ts_disp_u16_window_fwd(const void* raw, int B, int Hs, int Ws, in
   TS_REQUIRE((reinterpret_cast<uintptr_t>(disp) & 3u) == 0 && (reinterpret_cast<uintptr_t>(table) & 3u) == 0, TS_ERR_ALIGN,
              "disp_u16_window: disp / table not 4-byte aligned");
   const int items = H * ((W + 3) / 4);
-  hipLaunchKernelGGL(disp_u16_window_kernel, dim3(blocks_x(items), B), dim3(kThreads), 0, ts::as_stream(stream),
+  hipLaunchKernelGGL(disp_u16_window_kernel, dim3(ts::grid_blocks(items, kThreads, kMaxBlocksX), B), dim3(kThreads), 0, ts::as_stream(stream),
                      static_cast<const unsigned short*>(raw), table, Hs, Ws, H, W, scale, disp, static_cast<unsigned char*>(valid), items);
   return ts::launched("disp_u16_window_kernel");
 }

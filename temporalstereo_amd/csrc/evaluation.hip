@@ -17,8 +17,10 @@
 //                         level x split the integer counts and the fp64 sum of |e|.  Per-workgroup partials, no atomics.
 //   disp_metrics_finish   one workgroup adds the partials in a fixed order (counts exact, fp64 sums deterministic) and writes
 //                         out[level][split][5] = {1px, 2px, 3px, 5px, epe}, split = all / occ / noc.
+// Row loads and grid sizes: frame_io.hpp; the wave butterflies: reduce.hpp (both shared with render.hip).
 #include "bilinear.hpp"
-#include "ts_common.hpp"
+#include "frame_io.hpp"
+#include "reduce.hpp"
 
 #include <climits>
 
@@ -41,11 +43,7 @@ struct Levels {
 };
 
 // metrics workgroups for n ground-truth pixels: ~1024 pixels each, at most 4 per CU (a grid-stride loop takes the rest)
-int metric_blocks(long long n) {
-  long long nb = (n + 4 * kThreads - 1) / (4 * kThreads);
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  return static_cast<int>(nb < 1 ? 1 : nb);
-}
+int metric_blocks(long long n) { return ts::grid_blocks(n, 4 * kThreads, kMaxBlocks); }
 
 // value of gt_right at the tap (xx, yy) of grid_sample's zero padding: 0 outside the map
 __device__ __forceinline__ float tap(const float* __restrict__ gr, int Hg, int Wg, float xx, float yy) {
@@ -72,11 +70,36 @@ __device__ __forceinline__ bool occluded(const float* __restrict__ gr, int Hg, i
   return fabsf(__fsub_rn(r, g)) > 1.f || fabsf(r) < 1e-6f;
 }
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
+// Workgroup totals of one lane's kInts counts and kDoubles sums: shuffle trees per wave, then lane v (kInts + v) adds the four
+// waves of count (sum) v in the fixed order ((w0 + w1) + w2) + w3 into ti[v] (td[v]) -- the fp64 totals are reproducible.
+// Only the slots of levels < NL and splits < S are read; the others are literal zeros.
+template <int NL, int S>
+__device__ __forceinline__ void block_totals(const int (&ci)[kInts], const double (&cd)[kDoubles], int* ti, double* td) {
+  __shared__ int si[kThreads / ts::kWave][kInts];
+  __shared__ double sd[kThreads / ts::kWave][kDoubles];
+  const int wave = threadIdx.x / ts::kWave, lane = threadIdx.x & (ts::kWave - 1);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  for (int s = 0; s < kSplits; ++s) {
+    const int a = s < S ? ts::wave_sum(ci[s]) : 0;
+    if (lane == 0) si[wave][s] = a;
+  }
+#pragma unroll
+  for (int l = 0; l < kMaxLevels; ++l)
+#pragma unroll
+    for (int s = 0; s < kSplits; ++s) {
+      const bool used = l < NL && s < S;
+#pragma unroll
+      for (int k = 0; k < kThr; ++k) {
+        const int a = used ? ts::wave_sum(ci[cnt_idx(l, s, k)]) : 0;
+        if (lane == 0) si[wave][cnt_idx(l, s, k)] = a;
+      }
+      const double d = used ? ts::wave_sum(cd[l * kSplits + s]) : 0.0;
+      if (lane == 0) sd[wave][l * kSplits + s] = d;
+    }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < kInts) ti[t] = si[0][t] + si[1][t] + si[2][t] + si[3][t];
+  else if (t < kInts + kDoubles) td[t - kInts] = ((sd[0][t - kInts] + sd[1][t - kInts]) + sd[2][t - kInts]) + sd[3][t - kInts];
 }
 
 // NL levels, OCC: gt_right given (three splits, else only `all`), V pixels per lane (4: row-aligned float4 loads)
@@ -85,19 +108,12 @@ __global__ void __launch_bounds__(kThreads)
 disp_metrics_kernel(Levels lv, const float* __restrict__ gt, const float* __restrict__ gtr, int B, int Hg, int Wg, float lb,
                     float ub, int flags, double* __restrict__ psum, int* __restrict__ pcnt) {
   constexpr int S = OCC ? kSplits : 1;
-  int nv[S];
-  int cnt[NL][S][kThr];
-  double sum[NL][S];
+  int ci[kInts];                                      // N per split, then the counts per level x split x threshold
+  double cd[kDoubles];                                // sum |e| per level x split
 #pragma unroll
-  for (int s = 0; s < S; ++s) {
-    nv[s] = 0;
+  for (int v = 0; v < kInts; ++v) ci[v] = 0;
 #pragma unroll
-    for (int l = 0; l < NL; ++l) {
-      sum[l][s] = 0.0;
-#pragma unroll
-      for (int k = 0; k < kThr; ++k) cnt[l][s][k] = 0;
-    }
-  }
+  for (int v = 0; v < kDoubles; ++v) cd[v] = 0.0;
   const bool use_lb = (flags & 1) != 0, use_ub = (flags & 2) != 0;
   const long long HW = static_cast<long long>(Hg) * Wg;
   const long long items = static_cast<long long>(B) * HW / V;
@@ -108,21 +124,11 @@ disp_metrics_kernel(Levels lv, const float* __restrict__ gt, const float* __rest
     const long long t = i / Wg;
     const int y = static_cast<int>(t % Hg), b = static_cast<int>(t / Hg);
     float g[V], e[NL][V];
-    if constexpr (V == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(gt + i);
-      g[0] = q.x; g[1] = q.y; g[2] = q.z; g[3] = q.w;
-    } else {
-      g[0] = gt[i];
-    }
+    ts::load_row<V>(gt + i, g);
 #pragma unroll
     for (int l = 0; l < NL; ++l) {
       if (lv.h[l] == Hg && lv.w[l] == Wg) {
-        if constexpr (V == 4) {
-          const float4 q = *reinterpret_cast<const float4*>(lv.est[l] + i);
-          e[l][0] = q.x; e[l][1] = q.y; e[l][2] = q.z; e[l][3] = q.w;
-        } else {
-          e[l][0] = lv.est[l][i];
-        }
+        ts::load_row<V>(lv.est[l] + i, e[l]);
       } else {
         const float* p = lv.est[l] + static_cast<size_t>(b) * lv.h[l] * lv.w[l];
 #pragma unroll
@@ -138,54 +144,25 @@ disp_metrics_kernel(Levels lv, const float* __restrict__ gt, const float* __rest
         const bool in = s == 0 || (s == 1 ? occ : !occ);
         const float gs = in ? g[v] : g[v] * 0.f;             // gt * m of eval.py:91-101 (NaN / inf stay non-finite)
         if ((!use_lb || gs > lb) && (!use_ub || gs < ub)) {
-          ++nv[s];
+          ++ci[s];
 #pragma unroll
           for (int l = 0; l < NL; ++l) {
             const float a = fabsf(gs - (in ? e[l][v] : e[l][v] * 0.f));
-            cnt[l][s][0] += a > 1.f;
-            cnt[l][s][1] += a > 2.f;
-            cnt[l][s][2] += a > 3.f;
-            cnt[l][s][3] += a > 5.f;
-            sum[l][s] += static_cast<double>(a);
+            ci[cnt_idx(l, s, 0)] += a > 1.f;
+            ci[cnt_idx(l, s, 1)] += a > 2.f;
+            ci[cnt_idx(l, s, 2)] += a > 3.f;
+            ci[cnt_idx(l, s, 3)] += a > 5.f;
+            cd[l * kSplits + s] += static_cast<double>(a);
           }
         }
       }
     }
   }
-  // workgroup sums: shuffle trees per wave, then the four waves in order (fixed order: the fp64 partial is reproducible)
-  __shared__ int si[kThreads / 64][kInts];
-  __shared__ double sd[kThreads / 64][kDoubles];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int s = 0; s < kSplits; ++s) {
-    const int a = s < S ? wave_sum(nv[s < S ? s : 0]) : 0;
-    if (lane == 0) si[wave][s] = a;
-  }
-#pragma unroll
-  for (int l = 0; l < kMaxLevels; ++l)
-#pragma unroll
-    for (int s = 0; s < kSplits; ++s) {
-      const bool used = l < NL && s < S;
-      const int lu = l < NL ? l : 0, su = s < S ? s : 0;
-#pragma unroll
-      for (int k = 0; k < kThr; ++k) {
-        const int a = used ? wave_sum(cnt[lu][su][k]) : 0;
-        if (lane == 0) si[wave][cnt_idx(l, s, k)] = a;
-      }
-      const double d = used ? wave_sum(sum[lu][su]) : 0.0;
-      if (lane == 0) sd[wave][l * kSplits + s] = d;
-    }
-  __syncthreads();
-  const int tid = threadIdx.x;
-  if (tid < kInts) pcnt[static_cast<size_t>(blockIdx.x) * kInts + tid] = si[0][tid] + si[1][tid] + si[2][tid] + si[3][tid];
-  else if (tid < kInts + kDoubles) {
-    const int j = tid - kInts;
-    psum[static_cast<size_t>(blockIdx.x) * kDoubles + j] = ((sd[0][j] + sd[1][j]) + sd[2][j]) + sd[3][j];
-  }
+  block_totals<NL, S>(ci, cd, pcnt + static_cast<size_t>(blockIdx.x) * kInts, psum + static_cast<size_t>(blockIdx.x) * kDoubles);
 }
 
 // one workgroup: lane t adds the partials t, t+256, ... of every value (all loads independent: one memory latency per 256
-// partials, not one per value), then shuffle trees and the four waves in order -- a fixed order, so the fp64 sums are reproducible.
+// partials, not one per value), then the workgroup totals in their fixed order, so the fp64 sums are reproducible.
 // out[l][s][k] in the reference's fp32 order: (float)count / (float)N * 100 and (float)(sum / N); 0 when N < 1.
 __global__ void __launch_bounds__(kThreads)
 disp_metrics_finish_kernel(const double* __restrict__ psum, const int* __restrict__ pcnt, int nb, int n_est, int splits,
@@ -202,26 +179,11 @@ disp_metrics_finish_kernel(const double* __restrict__ psum, const int* __restric
 #pragma unroll
     for (int v = 0; v < kDoubles; ++v) cd[v] += psum[static_cast<size_t>(i) * kDoubles + v];
   }
-  __shared__ int si[kThreads / 64][kInts];
-  __shared__ double sd[kThreads / 64][kDoubles];
   __shared__ int ti[kInts];
   __shared__ double td[kDoubles];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int v = 0; v < kInts; ++v) {
-    const int a = wave_sum(ci[v]);
-    if (lane == 0) si[wave][v] = a;
-  }
-#pragma unroll
-  for (int v = 0; v < kDoubles; ++v) {
-    const double a = wave_sum(cd[v]);
-    if (lane == 0) sd[wave][v] = a;
-  }
+  block_totals<kMaxLevels, kSplits>(ci, cd, ti, td);
   __syncthreads();
   const int t = threadIdx.x;
-  if (t < kInts) ti[t] = si[0][t] + si[1][t] + si[2][t] + si[3][t];
-  else if (t < kInts + kDoubles) td[t - kInts] = ((sd[0][t - kInts] + sd[1][t - kInts]) + sd[2][t - kInts]) + sd[3][t - kInts];
-  __syncthreads();
   if (t < n_est * kSplits * 5) {
     const int l = t / (kSplits * 5), s = (t / 5) % kSplits, k = t % 5;
     const int N = ti[s];

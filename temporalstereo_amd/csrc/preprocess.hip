@@ -23,8 +23,9 @@
 // intrinsics_pyramid_kernel  one lane per (image, scale): the general 4x4 inverse by cofactors in fp64, rounded once to fp32 (the
 //                        structural zeros of an intrinsics matrix come out as exact zeros: every term holds a zero factor).
 // disp_u16_decode_kernel four pixels per lane: raw / scale where raw > 0, else 0; optionally the mask raw > 0 as bytes.
+// The tables, the quad loads / stores and the 16-bit decode are those of frame_io.hpp, shared with augment.hip.
 #include "bilinear.hpp"
-#include "ts_common.hpp"
+#include "frame_io.hpp"
 
 #include <climits>
 
@@ -33,7 +34,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = ts::kNumCU * 8;
 
-constexpr int F_CHW = TS_PREPARE_CHW, F_ALL = TS_PREPARE_CHW;
+constexpr int F_CHW = TS_PREPARE_CHW;
 
 struct PrepArgs {
   const unsigned char* src_l;   // [B,Hs,Ws,3] or [B,3,Hs,Ws]
@@ -45,74 +46,17 @@ struct PrepArgs {
   float* aug_r;
   long long color_stride, aug_stride;
   int B, N, Hs, Ws, H, W;
-  float m0, m1, m2, s0, s1, s2;
+  float mean[3], sd[3];
   float sh, sw;
 };
 
-struct Tables {
-  float v[256];                 // byte / 255
-  float n[3][256];              // (v - mean[c]) / std[c]
-};
-
-__device__ __forceinline__ void build_tables(const PrepArgs& a, Tables& t) {
-  const int i = threadIdx.x;    // kThreads == 256: one byte value per lane
-  const float v = __fdiv_rn(static_cast<float>(i), 255.f);
-  t.v[i] = v;
-  t.n[0][i] = __fdiv_rn(__fsub_rn(v, a.m0), a.s0);
-  t.n[1][i] = __fdiv_rn(__fsub_rn(v, a.m1), a.s1);
-  t.n[2][i] = __fdiv_rn(__fsub_rn(v, a.m2), a.s2);
-  __syncthreads();
-}
-
-// up to four values of row `p` (nv of them inside the row): one 16-byte store where the address allows
-__device__ __forceinline__ void store4(float* p, int nv, const float (&q)[4]) {
-  if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
-    *reinterpret_cast<float4*>(p) = make_float4(q[0], q[1], q[2], q[3]);
-  } else {
-#pragma unroll
-    for (int v = 0; v < 4; ++v)
-      if (v < nv) p[v] = q[v];
-  }
-}
-
-// the bytes of nv <= 4 adjacent pixels of row ys from column xs of image b: px[v][c]
-template <bool CHW>
-__device__ __forceinline__ void load_quad(const unsigned char* __restrict__ src, int b, int Hs, int Ws, int ys, int xs, int nv,
-                                          unsigned (&px)[4][3]) {
-#pragma unroll
-  for (int v = 0; v < 4; ++v) px[v][0] = px[v][1] = px[v][2] = 0u;
-  if constexpr (!CHW) {
-    const unsigned char* p = src + ((static_cast<size_t>(b) * Hs + ys) * Ws + xs) * 3;
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-      const unsigned* d = reinterpret_cast<const unsigned*>(p);
-      const unsigned w[3] = {d[0], d[1], d[2]};
-#pragma unroll
-      for (int k = 0; k < 12; ++k) px[k / 3][k % 3] = (w[k / 4] >> (8 * (k % 4))) & 255u;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k / 3 < nv) px[k / 3][k % 3] = p[k];
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const unsigned char* p = src + ((static_cast<size_t>(b) * 3 + c) * Hs + ys) * Ws + xs;
-      if (nv == 4 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0) {
-        const unsigned w = *reinterpret_cast<const unsigned*>(p);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) px[v][c] = (w >> (8 * v)) & 255u;
-      } else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-          if (v < nv) px[v][c] = p[v];
-      }
-    }
-  }
-}
+using ts::ByteTables;
+using ts::load_quad;
+using ts::store4;
 
 // one item of the copy form: four pixels of row y of an [Ho, Wo] window whose origin in the source is (oy, ox)
 template <bool CHW>
-__device__ __forceinline__ void copy_item(const PrepArgs& a, const Tables& t, long long it, int Ho, int Wo, bool with_aug) {
+__device__ __forceinline__ void copy_item(const PrepArgs& a, const ByteTables& t, long long it, int Ho, int Wo, bool with_aug) {
   const int per_row = (Wo + 3) >> 2;
   const int x0 = static_cast<int>(it % per_row) * 4;
   const long long r = it / per_row;
@@ -151,7 +95,7 @@ __device__ __forceinline__ unsigned src_byte(const unsigned char* __restrict__ s
 
 // one item of the resize form: four pixels of row y of color_aug [H, W]; the expressions of ts::rescaled on the normalised values
 template <bool CHW>
-__device__ __forceinline__ void resize_item(const PrepArgs& a, const Tables& t, long long it) {
+__device__ __forceinline__ void resize_item(const PrepArgs& a, const ByteTables& t, long long it) {
   const int per_row = (a.W + 3) >> 2;
   const int x0 = static_cast<int>(it % per_row) * 4;
   const long long r = it / per_row;
@@ -191,8 +135,8 @@ __device__ __forceinline__ void resize_item(const PrepArgs& a, const Tables& t, 
 // RESIZE true:  the first aug_items items are color_aug [H, W], the rest color [Hs, Ws].
 template <bool CHW, bool RESIZE>
 __global__ void __launch_bounds__(kThreads) frames_prepare_kernel(PrepArgs a, long long aug_items, long long items) {
-  __shared__ Tables t;
-  build_tables(a, t);
+  __shared__ ByteTables t;
+  ts::build_byte_tables(a.mean, a.sd, t);
   for (long long it = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; it < items;
        it += static_cast<long long>(gridDim.x) * kThreads) {
     if constexpr (RESIZE) {
@@ -247,41 +191,17 @@ __global__ void __launch_bounds__(64) intrinsics_pyramid_kernel(const T* __restr
 __global__ void __launch_bounds__(kThreads) disp_u16_decode_kernel(const unsigned short* __restrict__ raw, long long n, float scale,
                                                                    float* __restrict__ disp, unsigned char* __restrict__ valid) {
   const long long quads = (n + 3) >> 2;
-  const bool in8 = (reinterpret_cast<uintptr_t>(raw) & 7u) == 0, out4 = valid == nullptr || (reinterpret_cast<uintptr_t>(valid) & 3u) == 0;
   for (long long it = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; it < quads;
        it += static_cast<long long>(gridDim.x) * kThreads) {
     const long long i0 = it * 4;
     const int nv = static_cast<int>(n - i0 < 4 ? n - i0 : 4);
-    unsigned r[4] = {0u, 0u, 0u, 0u};
-    if (nv == 4 && in8) {
-      const uint2 w = *reinterpret_cast<const uint2*>(raw + i0);
-      r[0] = w.x & 65535u; r[1] = w.x >> 16; r[2] = w.y & 65535u; r[3] = w.y >> 16;
-    } else {
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        if (v < nv) r[v] = raw[i0 + v];
-    }
+    unsigned r[4];
     float q[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) q[v] = r[v] > 0u ? __fdiv_rn(static_cast<float>(r[v]), scale) : 0.f;
+    ts::load_u16_quad(raw + i0, nv, r);
+    ts::decode_u16_quad(r, scale, q);
     store4(disp + i0, nv, q);
-    if (valid != nullptr) {
-      if (nv == 4 && out4) {
-        *reinterpret_cast<unsigned*>(valid + i0) = (r[0] > 0u ? 1u : 0u) | (r[1] > 0u ? 1u << 8 : 0u) | (r[2] > 0u ? 1u << 16 : 0u) |
-                                                   (r[3] > 0u ? 1u << 24 : 0u);
-      } else {
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-          if (v < nv) valid[i0 + v] = r[v] > 0u ? 1 : 0;
-      }
-    }
+    if (valid != nullptr) ts::store_valid4(valid + i0, nv, r);
   }
-}
-
-int blocks_for(long long items) {
-  long long nb = (items + kThreads - 1) / kThreads;
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  return static_cast<int>(nb < 1 ? 1 : nb);
 }
 
 }  // namespace
@@ -290,14 +210,9 @@ extern "C" int ts_frames_prepare_fwd(const void* left, const void* right, int B,
                                      float mean2, float std0, float std1, float std2, int H, int W, const int* crop, float* color_l,
                                      float* color_r, long long color_stride, float* color_aug_l, float* color_aug_r,
                                      long long color_aug_stride, void* stream) {
-  TS_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "frames_prepare: bad size (B %d, source %dx%d, target %dx%d)", B,
-             Hs, Ws, H, W);
-  TS_REQUIRE((flags & ~F_ALL) == 0, TS_ERR_SHAPE, "frames_prepare: unknown flags %d", flags);
-  TS_REQUIRE_PTR(left);
-  TS_REQUIRE(color_l || color_r || color_aug_l || color_aug_r, TS_ERR_NULL, "frames_prepare: no output selected");
-  TS_REQUIRE(right != nullptr || (color_r == nullptr && color_aug_r == nullptr), TS_ERR_NULL,
-             "frames_prepare: an output of the right eye without a right image");
-  TS_REQUIRE(std0 != 0.f && std1 != 0.f && std2 != 0.f, TS_ERR_SHAPE, "frames_prepare: a zero std");
+  if (int rc = ts::frames_check_args("frames_prepare", "target", B, Hs, Ws, H, W, flags, {{"left", left}}, right, color_l, color_r,
+                                     color_aug_l, color_aug_r, std0, std1, std2))
+    return rc;
   const int N = right != nullptr ? 2 * B : B;
   const bool resize = crop == nullptr && (H != Hs || W != Ws);
   if (crop != nullptr)
@@ -306,14 +221,9 @@ extern "C" int ts_frames_prepare_fwd(const void* left, const void* right, int B,
                                                                                          : static_cast<long long>(H) * W;
   TS_REQUIRE(static_cast<long long>(N) * big <= INT_MAX / 4, TS_ERR_SHAPE, "frames_prepare: more than 2^29-1 pixels");
   const int Hc = resize ? Hs : H, Wc = resize ? Ws : W;
-  if (color_l || color_r)
-    TS_REQUIRE(color_stride >= 3LL * Hc * Wc, TS_ERR_SHAPE, "frames_prepare: color_stride %lld below 3 x %d x %d", color_stride, Hc, Wc);
-  if (color_aug_l || color_aug_r)
-    TS_REQUIRE(color_aug_stride >= 3LL * H * W, TS_ERR_SHAPE, "frames_prepare: color_aug_stride %lld below 3 x %d x %d",
-               color_aug_stride, H, W);
-  for (const void* p : {static_cast<const void*>(color_l), static_cast<const void*>(color_r), static_cast<const void*>(color_aug_l),
-                        static_cast<const void*>(color_aug_r), static_cast<const void*>(crop)})
-    TS_REQUIRE((reinterpret_cast<uintptr_t>(p) & 3u) == 0, TS_ERR_ALIGN, "frames_prepare: a 4-byte pointer is not 4-byte aligned");
+  if (int rc = ts::frames_check_outputs("frames_prepare", Hc, Wc, H, W, color_l, color_r, color_stride, color_aug_l, color_aug_r,
+                                        color_aug_stride, crop))
+    return rc;
 
   PrepArgs a{};
   a.src_l = static_cast<const unsigned char*>(left); a.src_r = static_cast<const unsigned char*>(right);
@@ -321,7 +231,7 @@ extern "C" int ts_frames_prepare_fwd(const void* left, const void* right, int B,
   a.color_l = color_l; a.color_r = color_r; a.aug_l = color_aug_l; a.aug_r = color_aug_r;
   a.color_stride = color_stride; a.aug_stride = color_aug_stride;
   a.B = B; a.N = N; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W;
-  a.m0 = mean0; a.m1 = mean1; a.m2 = mean2; a.s0 = std0; a.s1 = std1; a.s2 = std2;
+  a.mean[0] = mean0; a.mean[1] = mean1; a.mean[2] = mean2; a.sd[0] = std0; a.sd[1] = std1; a.sd[2] = std2;
   a.sh = ts::ac_scale(Hs, H); a.sw = ts::ac_scale(Ws, W);
   const bool chw = (flags & F_CHW) != 0;
   const hipStream_t st = ts::as_stream(stream);
@@ -329,11 +239,11 @@ extern "C" int ts_frames_prepare_fwd(const void* left, const void* right, int B,
   if (resize) {
     if (!(color_aug_l || color_aug_r)) aug_items = 0;
     items = aug_items + ((color_l || color_r) ? static_cast<long long>(N) * Hs * ((Ws + 3) / 4) : 0);
-    const int nb = blocks_for(items);
+    const int nb = ts::grid_blocks(items, kThreads, kMaxBlocks);
     if (chw) hipLaunchKernelGGL((frames_prepare_kernel<true, true>), dim3(nb), dim3(kThreads), 0, st, a, aug_items, items);
     else hipLaunchKernelGGL((frames_prepare_kernel<false, true>), dim3(nb), dim3(kThreads), 0, st, a, aug_items, items);
   } else {
-    const int nb = blocks_for(items);
+    const int nb = ts::grid_blocks(items, kThreads, kMaxBlocks);
     if (chw) hipLaunchKernelGGL((frames_prepare_kernel<true, false>), dim3(nb), dim3(kThreads), 0, st, a, aug_items, items);
     else hipLaunchKernelGGL((frames_prepare_kernel<false, false>), dim3(nb), dim3(kThreads), 0, st, a, aug_items, items);
   }
@@ -366,7 +276,7 @@ extern "C" int ts_disp_u16_decode_fwd(const void* raw, int B, int H, int W, floa
   TS_REQUIRE((reinterpret_cast<uintptr_t>(raw) & 1u) == 0, TS_ERR_ALIGN, "disp_u16_decode: raw not 2-byte aligned");
   TS_REQUIRE((reinterpret_cast<uintptr_t>(disp) & 3u) == 0, TS_ERR_ALIGN, "disp_u16_decode: disp not 4-byte aligned");
   const long long n = static_cast<long long>(B) * H * W;
-  hipLaunchKernelGGL(disp_u16_decode_kernel, dim3(blocks_for((n + 3) / 4)), dim3(kThreads), 0, ts::as_stream(stream),
+  hipLaunchKernelGGL(disp_u16_decode_kernel, dim3(ts::grid_blocks((n + 3) / 4, kThreads, kMaxBlocks)), dim3(kThreads), 0, ts::as_stream(stream),
                      static_cast<const unsigned short*>(raw), n, scale, disp, static_cast<unsigned char*>(valid));
   return ts::launched("disp_u16_decode_kernel");
 }

@@ -28,8 +28,10 @@
 //                        the rescale is evaluated again in registers, every selected output is written with vector stores
 //                        (fp32 HWC: three float4; uint8 HWC: three dwords; CHW: one float4 / dword per channel; 16-bit: 8 bytes).
 //                        The legend rows H .. H+49 depend on the width only and are items of the same grid.
+// Row loads and grid sizes: frame_io.hpp; the wave butterflies: reduce.hpp (both shared with evaluation.hip).
 #include "bilinear.hpp"
-#include "ts_common.hpp"
+#include "frame_io.hpp"
+#include "reduce.hpp"
 
 #include <climits>
 #include <cmath>
@@ -73,42 +75,13 @@ struct RenderArgs {
   int flags;
 };
 
-__device__ __forceinline__ float nan_max(float a, float b) {          // np.max: a NaN anywhere makes the maximum NaN
-  return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b);
-}
-
-__device__ __forceinline__ float wave_nan_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using ts::nan_max;
 
 // V estimates of row y starting at column x0 of image b: read at full size, or rescaled in registers
 template <int V>
 __device__ __forceinline__ void load_est(const RenderArgs& a, int b, int y, int x0, float (&e)[V]) {
   if (a.h == a.Hg && a.w == a.Wg) {
-    const float* p = a.est + (static_cast<size_t>(b) * a.Hg + y) * a.Wg + x0;
-    if constexpr (V == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(p);
-      e[0] = q.x; e[1] = q.y; e[2] = q.z; e[3] = q.w;
-    } else {
-      e[0] = p[0];
-    }
+    ts::load_row<V>(a.est + (static_cast<size_t>(b) * a.Hg + y) * a.Wg + x0, e);
   } else {
     const float* p = a.est + static_cast<size_t>(b) * a.h * a.w;
 #pragma unroll
@@ -116,33 +89,77 @@ __device__ __forceinline__ void load_est(const RenderArgs& a, int b, int y, int 
   }
 }
 
-template <int V>
-__device__ __forceinline__ void load_gt(const RenderArgs& a, int b, int y, int x0, float (&g)[V]) {
-  const float* p = a.gt + (static_cast<size_t>(b) * a.Hg + y) * a.Wg + x0;
-  if constexpr (V == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    g[0] = q.x; g[1] = q.y; g[2] = q.z; g[3] = q.w;
-  } else {
-    g[0] = p[0];
-  }
-}
-
 // error_map of disp_err_to_colorbar (:182-183): |est - gt| * valid, literally (a non-finite estimate on an invalid pixel gives NaN)
 __device__ __forceinline__ float bar_error(float e, float g) { return __fmul_rn(fabsf(__fsub_rn(e, g)), g > 0.f ? 1.f : 0.f); }
 
 // ---------------------------------------------------------------------------------------------------------------- statistics
+// what one lane, and then one workgroup, knows of an image: kPartial values in the layout of `partial`
+struct RangeStats {
+  float m3[3];                                    // NaN-propagating maxima of the estimate, the ground truth and the error
+  float mn[kVariants], mx[kVariants];             // minimum / maximum of the error inside each range
+  int cnt[kVariants];
+
+  __device__ __forceinline__ void init() {
+    m3[0] = m3[1] = m3[2] = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < kVariants; ++k) {
+      mn[k] = INFINITY; mx[k] = -INFINITY; cnt[k] = 0;
+    }
+  }
+
+  // one error value into the ranges that hold it
+  __device__ __forceinline__ void fold(float r) {
+    float lo = 0.f;
+#pragma unroll
+    for (int k = 0; k < kVariants; ++k) {
+      const float hi = k < kRanges ? kBreak[k] : INFINITY;
+      if (k == kRanges) lo = kBreak[kRanges - 2];                     // the second variant of the last range starts at 16 too
+      if (r > lo && r <= hi) {
+        mn[k] = fminf(mn[k], r);
+        mx[k] = fmaxf(mx[k], r);
+        ++cnt[k];
+      }
+      lo = hi;
+    }
+  }
+
+  // over the workgroup: shuffle trees per wave, then lane t < kPartial combines the four waves by kind into out[t]
+  __device__ __forceinline__ void block_reduce(float* out) const {
+    __shared__ float sf[kThreads / ts::kWave][kPartial];
+    const int wave = threadIdx.x / ts::kWave, lane = threadIdx.x & (ts::kWave - 1);
+    const float me = ts::wave_nan_max(m3[0]), mg = ts::wave_nan_max(m3[1]), mr = ts::wave_nan_max(m3[2]);
+    if (lane == 0) {
+      sf[wave][0] = me; sf[wave][1] = mg; sf[wave][2] = mr;
+    }
+#pragma unroll
+    for (int k = 0; k < kVariants; ++k) {
+      const float lo = ts::wave_min(mn[k]), hi = ts::wave_max(mx[k]);
+      const int c = ts::wave_sum(cnt[k]);
+      if (lane == 0) {
+        sf[wave][3 + k] = lo;
+        sf[wave][3 + kVariants + k] = hi;
+        sf[wave][3 + 2 * kVariants + k] = __int_as_float(c);
+      }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < kPartial) {
+      float r;
+      if (t < 3) r = nan_max(nan_max(sf[0][t], sf[1][t]), nan_max(sf[2][t], sf[3][t]));
+      else if (t < 3 + kVariants) r = fminf(fminf(sf[0][t], sf[1][t]), fminf(sf[2][t], sf[3][t]));
+      else if (t < 3 + 2 * kVariants) r = fmaxf(fmaxf(sf[0][t], sf[1][t]), fmaxf(sf[2][t], sf[3][t]));
+      else r = __int_as_float(__float_as_int(sf[0][t]) + __float_as_int(sf[1][t]) + __float_as_int(sf[2][t]) + __float_as_int(sf[3][t]));
+      out[t] = r;
+    }
+  }
+};
+
 // grid (workgroups per image, B).  partial [B][gridDim.x][kPartial] (counts as int bits)
 template <int V>
 __global__ void __launch_bounds__(kThreads) render_stats_kernel(RenderArgs a, float* __restrict__ partial) {
   const int b = blockIdx.y;
-  const float ninf = -INFINITY, pinf = INFINITY;
-  float me = ninf, mg = ninf, mr = ninf;
-  float mn[kVariants], mx[kVariants];
-  int cnt[kVariants];
-#pragma unroll
-  for (int k = 0; k < kVariants; ++k) {
-    mn[k] = pinf; mx[k] = ninf; cnt[k] = 0;
-  }
+  RangeStats s;
+  s.init();
   const int items = a.Hg * (a.Wg / V);          // V == 4 only when Wg % 4 == 0
   const int per_row = a.Wg / V;
   for (int it = blockIdx.x * kThreads + threadIdx.x; it < items; it += gridDim.x * kThreads) {
@@ -150,107 +167,40 @@ __global__ void __launch_bounds__(kThreads) render_stats_kernel(RenderArgs a, fl
     float e[V], g[V];
     load_est<V>(a, b, y, x0, e);
 #pragma unroll
-    for (int v = 0; v < V; ++v) me = nan_max(me, e[v]);
+    for (int v = 0; v < V; ++v) s.m3[0] = nan_max(s.m3[0], e[v]);
     if (a.gt != nullptr) {
-      load_gt<V>(a, b, y, x0, g);
+      ts::load_row<V>(a.gt + (static_cast<size_t>(b) * a.Hg + y) * a.Wg + x0, g);
 #pragma unroll
       for (int v = 0; v < V; ++v) {
-        mg = nan_max(mg, g[v]);
+        s.m3[1] = nan_max(s.m3[1], g[v]);
         const float r = bar_error(e[v], g[v]);
-        mr = nan_max(mr, r);
-        float lo = 0.f;
-#pragma unroll
-        for (int k = 0; k < kVariants; ++k) {
-          const float hi = k < kRanges ? kBreak[k] : pinf;
-          if (k == kRanges) lo = kBreak[kRanges - 2];                 // the second variant of the last range starts at 16 too
-          if (r > lo && r <= hi) {
-            mn[k] = fminf(mn[k], r);
-            mx[k] = fmaxf(mx[k], r);
-            ++cnt[k];
-          }
-          lo = hi;
-        }
+        s.m3[2] = nan_max(s.m3[2], r);
+        s.fold(r);
       }
     }
   }
-  __shared__ float sf[kThreads / 64][kPartial];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  me = wave_nan_max(me); mg = wave_nan_max(mg); mr = wave_nan_max(mr);
-  if (lane == 0) {
-    sf[wave][0] = me; sf[wave][1] = mg; sf[wave][2] = mr;
-  }
-#pragma unroll
-  for (int k = 0; k < kVariants; ++k) {
-    const float lo = wave_min(mn[k]), hi = wave_max(mx[k]);
-    const int c = wave_sum(cnt[k]);
-    if (lane == 0) {
-      sf[wave][3 + k] = lo;
-      sf[wave][3 + kVariants + k] = hi;
-      sf[wave][3 + 2 * kVariants + k] = __int_as_float(c);
-    }
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t < kPartial) {
-    float r;
-    if (t < 3) r = nan_max(nan_max(sf[0][t], sf[1][t]), nan_max(sf[2][t], sf[3][t]));
-    else if (t < 3 + kVariants) r = fminf(fminf(sf[0][t], sf[1][t]), fminf(sf[2][t], sf[3][t]));
-    else if (t < 3 + 2 * kVariants) r = fmaxf(fmaxf(sf[0][t], sf[1][t]), fmaxf(sf[2][t], sf[3][t]));
-    else r = __int_as_float(__float_as_int(sf[0][t]) + __float_as_int(sf[1][t]) + __float_as_int(sf[2][t]) + __float_as_int(sf[3][t]));
-    partial[(static_cast<size_t>(b) * gridDim.x + blockIdx.x) * kPartial + t] = r;
-  }
+  s.block_reduce(partial + (static_cast<size_t>(b) * gridDim.x + blockIdx.x) * kPartial);
 }
 
 // one workgroup per image: lane t takes the partials t, t+256, ..., then shuffle trees and the four waves in order
 __global__ void __launch_bounds__(kThreads) render_stats_finish_kernel(const float* __restrict__ partial, int nb, float* __restrict__ stats) {
   const int b = blockIdx.x;
-  const float ninf = -INFINITY, pinf = INFINITY;
-  float m3[3] = {ninf, ninf, ninf};
-  float mn[kVariants], mx[kVariants];
-  int cnt[kVariants];
-#pragma unroll
-  for (int k = 0; k < kVariants; ++k) {
-    mn[k] = pinf; mx[k] = ninf; cnt[k] = 0;
-  }
+  RangeStats s;
+  s.init();
   for (int i = threadIdx.x; i < nb; i += kThreads) {
     const float* p = partial + (static_cast<size_t>(b) * nb + i) * kPartial;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) m3[k] = nan_max(m3[k], p[k]);
+    for (int k = 0; k < 3; ++k) s.m3[k] = nan_max(s.m3[k], p[k]);
 #pragma unroll
     for (int k = 0; k < kVariants; ++k) {
-      mn[k] = fminf(mn[k], p[3 + k]);
-      mx[k] = fmaxf(mx[k], p[3 + kVariants + k]);
-      cnt[k] += __float_as_int(p[3 + 2 * kVariants + k]);
+      s.mn[k] = fminf(s.mn[k], p[3 + k]);
+      s.mx[k] = fmaxf(s.mx[k], p[3 + kVariants + k]);
+      s.cnt[k] += __float_as_int(p[3 + 2 * kVariants + k]);
     }
   }
-  __shared__ float sf[kThreads / 64][kPartial];
   __shared__ float tot[kPartial];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float r = wave_nan_max(m3[k]);
-    if (lane == 0) sf[wave][k] = r;
-  }
-#pragma unroll
-  for (int k = 0; k < kVariants; ++k) {
-    const float lo = wave_min(mn[k]), hi = wave_max(mx[k]);
-    const int c = wave_sum(cnt[k]);
-    if (lane == 0) {
-      sf[wave][3 + k] = lo;
-      sf[wave][3 + kVariants + k] = hi;
-      sf[wave][3 + 2 * kVariants + k] = __int_as_float(c);
-    }
-  }
-  __syncthreads();
+  s.block_reduce(tot);
   const int t = threadIdx.x;
-  if (t < kPartial) {
-    float r;
-    if (t < 3) r = nan_max(nan_max(sf[0][t], sf[1][t]), nan_max(sf[2][t], sf[3][t]));
-    else if (t < 3 + kVariants) r = fminf(fminf(sf[0][t], sf[1][t]), fminf(sf[2][t], sf[3][t]));
-    else if (t < 3 + 2 * kVariants) r = fmaxf(fmaxf(sf[0][t], sf[1][t]), fmaxf(sf[2][t], sf[3][t]));
-    else r = __int_as_float(__float_as_int(sf[0][t]) + __float_as_int(sf[1][t]) + __float_as_int(sf[2][t]) + __float_as_int(sf[3][t]));
-    tot[t] = r;
-  }
   __syncthreads();
   if (t < kStats) {
     const float maxerr = tot[2];
@@ -455,7 +405,7 @@ __global__ void __launch_bounds__(kThreads) render_color_kernel(RenderArgs a) {
     float e[V], g[V];
     load_est<V>(a, b, y, x0, e);
     if (a.gt != nullptr) {
-      load_gt<V>(a, b, y, x0, g);
+      ts::load_row<V>(a.gt + (static_cast<size_t>(b) * a.Hg + y) * a.Wg + x0, g);
     } else {
 #pragma unroll
       for (int v = 0; v < V; ++v) g[v] = 0.f;
@@ -504,19 +454,9 @@ __global__ void __launch_bounds__(kThreads) render_color_kernel(RenderArgs a) {
   }
 }
 
-int blocks_for(long long items, int cap) {
-  long long nb = (items + kThreads - 1) / kThreads;
-  if (nb > cap) nb = cap;
-  return static_cast<int>(nb < 1 ? 1 : nb);
-}
-
 // statistics workgroups per image: ~1024 pixels each, the whole grid at most 4 per CU
 int stats_blocks(int B, int Hg, int Wg) {
-  const long long n = static_cast<long long>(Hg) * Wg;
-  long long nb = (n + 4 * kThreads - 1) / (4 * kThreads);
-  const long long cap = (ts::kNumCU * 4 + B - 1) / B;
-  if (nb > cap) nb = cap;
-  return static_cast<int>(nb < 1 ? 1 : nb);
+  return ts::grid_blocks(static_cast<long long>(Hg) * Wg, 4 * kThreads, (ts::kNumCU * 4 + B - 1) / B);
 }
 
 }  // namespace
@@ -590,7 +530,7 @@ extern "C" int ts_disp_render_fwd(const float* est, const float* gt, const float
   }
   const int rows = Hg + (((flags & F_ERR_JET) && (flags & F_BAR)) ? kBarRows : 0);
   const long long items = static_cast<long long>(B) * rows * (Wg / (vec ? 4 : 1));
-  const int nb = blocks_for(items, kMaxBlocks);
+  const int nb = ts::grid_blocks(items, kThreads, kMaxBlocks);
   if (vec) {
     if (u8) hipLaunchKernelGGL((render_color_kernel<4, true>), dim3(nb), dim3(kThreads), 0, st, a);
     else hipLaunchKernelGGL((render_color_kernel<4, false>), dim3(nb), dim3(kThreads), 0, st, a);

@@ -37,74 +37,12 @@ import math
 import torch
 
 from . import _lib
+from ._frameio import _batch_dict, _color_outputs, _frames, _gt_rows, _on_gpu, _three, _u16_map
 from .functional import _stream
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)       # base.py:41
 IMAGENET_STD = (0.229, 0.224, 0.225)
 CHW = 1                                     # TS_PREPARE_CHW (include/ts_hip.h)
-_U16 = getattr(torch, "uint16", None)
-
-
-def _on_gpu(what, *tensors):
-    dev = None
-    for t in tensors:
-        if t is None:
-            continue
-        if not torch.is_tensor(t):
-            raise TypeError("%s: expected a tensor, got %s" % (what, type(t).__name__))
-        if not t.is_cuda:
-            raise RuntimeError("temporalstereo_amd ops run on the GPU only (got a %s tensor of shape %s); "
-                               "there is deliberately no CPU fallback" % (t.device, tuple(t.shape)))
-        if dev is not None and t.device != dev:
-            raise RuntimeError("%s: tensors on %s and %s" % (what, dev, t.device))
-        dev = t.device
-    if dev is not None and dev.index != torch.cuda.current_device():
-        raise RuntimeError("%s: tensors on %s while the current device is cuda:%d" % (what, dev, torch.cuda.current_device()))
-    return dev
-
-
-def _frames(what, left, right, layout):
-    """uint8 images, one or a batch, of one shape -> (left, right, B, Hs, Ws, batched)"""
-    if layout not in ('HWC', 'CHW'):
-        raise ValueError("layout must be 'HWC' or 'CHW' (got %r)" % (layout,))
-    for t in (left, right):
-        if t is None:
-            continue
-        if not torch.is_tensor(t):
-            raise TypeError("%s: expected a uint8 tensor, got %s" % (what, type(t).__name__))
-        if t.dtype != torch.uint8:
-            raise TypeError("%s: frames must be uint8 (got %s of shape %s)" % (what, t.dtype, tuple(t.shape)))
-        if t.dim() not in (3, 4):
-            raise ValueError("%s: a frame is [H,W,3] / [B,H,W,3] (HWC) or [3,H,W] / [B,3,H,W] (CHW), got shape %s" % (what, tuple(t.shape)))
-        if t.shape[-1 if layout == 'HWC' else -3] != 3:
-            raise ValueError("%s: three channels expected in layout %s, got shape %s" % (what, layout, tuple(t.shape)))
-        if t.numel() == 0:
-            raise ValueError("%s: empty batch of shape %s" % (what, tuple(t.shape)))
-    if right is not None and tuple(right.shape) != tuple(left.shape):
-        raise ValueError("%s: left has shape %s, right %s" % (what, tuple(left.shape), tuple(right.shape)))
-    _on_gpu(what, left, right)
-    batched = left.dim() == 4
-    B = left.shape[0] if batched else 1
-    Hs, Ws = (left.shape[-3], left.shape[-2]) if layout == 'HWC' else (left.shape[-2], left.shape[-1])
-    return _lib.contiguous(left), (None if right is None else _lib.contiguous(right)), B, Hs, Ws, batched
-
-
-def _three(name, v):
-    v = tuple(float(x) for x in v)
-    if len(v) != 3:
-        raise ValueError("%s must hold three numbers (got %d)" % (name, len(v)))
-    return v
-
-
-def _out_tensor(what, t, shape, dev):
-    if t.dtype != torch.float32 or not t.is_cuda or t.device != dev:
-        raise TypeError("%s: out must be fp32 on %s (got %s on %s)" % (what, dev, t.dtype, t.device))
-    if tuple(t.shape) != shape:
-        raise ValueError("%s: out has shape %s, %s expected" % (what, tuple(t.shape), shape))
-    _, _, H, W = shape
-    if t.stride(3) != 1 or t.stride(2) != W or t.stride(1) != H * W or (shape[0] > 1 and t.stride(0) < 3 * H * W):
-        raise ValueError("%s: an image of out must be dense (strides %s of shape %s); only the batch stride is free" % (what, t.stride(), shape))
-    return t.stride(0) if shape[0] > 1 else 3 * H * W
 
 
 def prepare_frames(left, right=None, size=None, crop=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, layout='HWC', color=True, out=None):
@@ -151,25 +89,8 @@ def prepare_frames(left, right=None, size=None, crop=None, mean=IMAGENET_MEAN, s
             crop_t = torch.tensor(rows, dtype=torch.int32, device=dev)
     resize = crop_t is None and (H, W) != (Hs, Ws)
     Hc, Wc = (Hs, Ws) if resize else (H, W)
-    res = {}
     sides = ('l', 'r') if right is not None else ('l',)
-    aug_shape = (B, 3, H, W)
-    if out is not None:
-        outs = tuple(out) if isinstance(out, (tuple, list)) else (out,)
-        if len(outs) != len(sides):
-            raise ValueError("%s: %d out tensors for %d eyes" % (what, len(outs), len(sides)))
-        strides = {_out_tensor(what, t, aug_shape, dev) for t in outs}
-        if len(strides) != 1:
-            raise ValueError("%s: the out tensors must share one batch stride (got %s)" % (what, sorted(strides)))
-        aug_stride = strides.pop()
-    else:
-        outs = tuple(torch.empty(aug_shape, device=dev, dtype=torch.float32) for _ in sides)
-        aug_stride = 3 * H * W
-    for s, t in zip(sides, outs):
-        res['color_aug_' + s] = t
-    if color:
-        for s in sides:
-            res['color_' + s] = torch.empty((B, 3, Hc, Wc), device=dev, dtype=torch.float32)
+    res, aug_stride = _color_outputs(what, sides, B, H, W, (Hc, Wc), out, color, dev)
     _lib.check(_lib.lib().ts_frames_prepare_fwd(
         _lib.ptr(left), _lib.ptr(right), B, Hs, Ws, CHW if layout == 'CHW' else 0, *mean, *std, H, W, _lib.ptr(crop_t),
         _lib.ptr(res.get('color_l')), _lib.ptr(res.get('color_r')), 3 * Hc * Wc,
@@ -213,22 +134,7 @@ def disp_from_uint16(raw, scale=256.0, with_valid=False):
     raw > 0 (exact for scale 256), 0 elsewhere; with_valid also returns the mask raw > 0 (bool, same shape).
     raw: torch.uint16; or torch.int16, whose bits are REINTERPRETED as unsigned (-1 is 65535); or torch.int32, whose low 16 bits
     are taken (a cast on the device; not while a launch plan is being recorded)."""
-    what = "disp_from_uint16"
-    _on_gpu(what, raw)
-    if raw.dtype == torch.int32:
-        if _lib.recording():
-            raise RuntimeError("%s: an int32 map needs a cast that a launch plan would not replay; hand over 16-bit storage" % what)
-        raw = raw.to(torch.int16)
-    elif raw.dtype != torch.int16 and (_U16 is None or raw.dtype != _U16):
-        raise TypeError("%s: raw must be uint16, int16 (reinterpreted) or int32 (got %s of shape %s)" % (what, raw.dtype, tuple(raw.shape)))
-    if raw.dim() not in (2, 3, 4) or (raw.dim() == 4 and raw.shape[1] != 1) or raw.numel() == 0:
-        raise ValueError("%s: raw must be a non-empty [H,W], [B,H,W] or [B,1,H,W] map (got %s)" % (what, tuple(raw.shape)))
-    if not float(scale) > 0:
-        raise ValueError("%s: scale %r" % (what, scale))
-    batched = raw.dim() > 2
-    B = raw.shape[0] if batched else 1
-    H, W = raw.shape[-2:]
-    r = _lib.contiguous(raw)
+    r, (B, H, W, batched) = _u16_map("disp_from_uint16", raw, scale)
     disp = torch.empty((B, 1, H, W), device=r.device, dtype=torch.float32)
     valid = torch.empty((B, 1, H, W), device=r.device, dtype=torch.uint8) if with_valid else None
     _lib.check(_lib.lib().ts_disp_u16_decode_fwd(_lib.ptr(r), B, H, W, float(scale), _lib.ptr(disp), _lib.ptr(valid), _stream()),
@@ -256,35 +162,8 @@ def prepare_batch(left, right, K_norm, baseline, size, timestamp=0, disp_gt_raw=
         raise ValueError("%s: the network's input size is needed" % what)
     size = tuple(int(v) for v in size)
     fr = prepare_frames(left, right, size=size, crop=crop, mean=mean, std=std, layout=layout, color=True, out=out)
-    batched = fr['color_aug_l'].dim() == 4
-    if not batched:
-        fr = {k: v.unsqueeze(0) for k, v in fr.items()}
-    B = fr['color_aug_l'].shape[0]
-    dev = fr['color_aug_l'].device
-    t = timestamp
-    batch = {('color', t, 'l'): fr['color_l'], ('color', t, 'r'): fr['color_r'],
-             ('color_aug', t, 'l'): fr['color_aug_l'], ('color_aug', t, 'r'): fr['color_aug_r']}
     S = default_num_scales(size) if num_scales is None else int(num_scales)
-    _on_gpu(what, K_norm)
-    kn = K_norm if K_norm.dim() == 3 else K_norm.unsqueeze(0)
-    if kn.shape[0] not in (1, B):
-        raise ValueError("%s: K_norm of shape %s for a batch of %d" % (what, tuple(K_norm.shape), B))
-    K, inv = intrinsics_pyramid(kn, size if k_size is None else k_size, S)
-    if K.shape[0] != B:
-        K, inv = K.expand(B, S, 4, 4), inv.expand(B, S, 4, 4)
-    for s in range(S):
-        batch[('K', s)] = K[:, s]
-        batch[('inv_K', s)] = inv[:, s]
-    if torch.is_tensor(baseline):
-        _on_gpu(what, baseline)
-        if baseline.numel() != B:
-            raise ValueError("%s: baseline of shape %s for a batch of %d" % (what, tuple(baseline.shape), B))
-        batch['baseline'] = baseline.to(torch.float32).reshape(B, 1, 1, 1)
-    else:
-        batch['baseline'] = torch.full((B, 1, 1, 1), float(baseline), device=dev, dtype=torch.float32)
+    batch = _batch_dict(what, fr, K_norm, size if k_size is None else k_size, S, baseline, timestamp)
     if disp_gt_raw is not None:
-        g = disp_gt_raw if disp_gt_raw.dim() > 2 else disp_gt_raw.unsqueeze(0)
-        if g.shape[0] != B:
-            raise ValueError("%s: disp_gt_raw of shape %s for a batch of %d" % (what, tuple(disp_gt_raw.shape), B))
-        batch[('disp_gt', t, 'l')] = disp_from_uint16(g, gt_scale)
+        batch[('disp_gt', timestamp, 'l')] = disp_from_uint16(_gt_rows(what, disp_gt_raw, batch), gt_scale)
     return batch
