@@ -66,6 +66,44 @@ int ts_block_cost_sampled_corr_fwd(const float* left, const float* right, const 
                                    void* workspace, int B, int C, int H, int W, int D, int scales,
                                    void* stream);
 
+/* Split-input forms: an input whose channels [0, Csplit) live in one allocation and [Csplit, C) in another is read in place
+ * instead of being concatenated first.  Each base has its own batch stride (and, for the convolutions, channel stride) in elements
+ * and is addressed through a buffer descriptor of its own extent.  Same kernels, same chunk order, same arithmetic: the results are
+ * bit-identical to the plain entry on the concatenation.  Csplit must be a multiple of 32 (the widest K chunk a kernel stages, so no
+ * chunk straddles the seam) with 0 < Csplit < C; anything else is TS_ERR_UNSUPPORTED, and the *_split_supported queries answer
+ * beforehand (1 = the split entry takes the shape).
+ *   ts_block_cost_sampled_corr_split_fwd  ts_block_cost_sampled_corr_fwd with left = [left | left2], right = [right | right2];
+ *                                         planes are dense ([B][.][H][W]), the four batch strides are free
+ *   ts_conv3d_hw_split_fwd                ts_conv3d_hw_fwd, not the transposed form; a split-K launch needs slices of whole
+ *                                         32-channel chunks (ts_conv3d_hw_split_supported assumes the workspace is handed over)
+ *   ts_conv3d_d_split_fwd                 ts_conv3d_d_fwd
+ *   ts_conv3d_hw_x6_split_fwd             ts_conv3d_hw_x6_fwd (either of its kernels) */
+int ts_block_cost_corr_split_supported(int C, int Csplit);
+int ts_block_cost_sampled_corr_split_fwd(const float* left, const float* left2, const float* right, const float* right2,
+                                         const float* disp, float* out, void* workspace, int B, int C, int Csplit, int H, int W,
+                                         int D, int scales, long long left_bstride, long long left2_bstride,
+                                         long long right_bstride, long long right2_bstride, void* stream);
+int ts_conv3d_hw_split_supported(int B, int Cin, int Csplit, int Cout, int D, int H, int W, int stride, int dilation,
+                                 int transposed);
+int ts_conv3d_hw_split_fwd(const float* x, const float* x2, const float* w_t, const float* scale, const float* shift, float* y,
+                           int B, int Cin, int Csplit, int Cout, int D, int H, int W, int stride, int dilation,
+                           int transposed, int act, float act_param,
+                           long long in_bstride, long long in_cstride, long long in2_bstride, long long in2_cstride,
+                           long long out_bstride, long long out_cstride, const float* addend, long long addend_bstride,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int ts_conv3d_d_split_supported(int Cin, int Csplit);
+int ts_conv3d_d_split_fwd(const float* x, const float* x2, const float* w_t, const float* scale, const float* shift, float* y,
+                          int B, int Cin, int Csplit, int Cout, int Din, int H, int W, int k, int stride, int dilation,
+                          int padding, int transposed, int act, float act_param,
+                          long long in_bstride, long long in_cstride, long long in2_bstride, long long in2_cstride,
+                          long long out_bstride, long long out_cstride, void* stream);
+int ts_conv3d_hw_x6_split_supported(int Cin, int Csplit, int Cout, int W, int dilation);
+int ts_conv3d_hw_x6_split_fwd(const float* x, const float* x2, const void* w6, const float* scale, const float* shift, float* y,
+                              int B, int Cin, int Csplit, int Cout, int D, int H, int W, int dilation, int act, float act_param,
+                              long long in_bstride, long long in_cstride, long long in2_bstride, long long in2_cstride,
+                              long long out_bstride, long long out_cstride, const float* addend, long long addend_bstride,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Dense siblings of block_cost (forward only): any number of candidates D >= 2, C % 8 == 0.
  *   cat_fms  aggregation/utils/cat_fms.py:5-36   out [B,2C,D,H,W] = cat[left repeated over D, warped right]
  *   dif_fms  aggregation/utils/dif_fms.py:5-44   out [B, C,D,H,W] = |left - warped right|, elements whose warped

@@ -28,6 +28,16 @@ SIGNATURES = {
     "ts_block_cost_sampled_fwd": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_ptr] + [c_int] * 6 + [c_ptr]),
     "ts_block_cost_sampled_warped_fwd": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_ptr] + [c_int] * 6 + [c_ptr]),
     "ts_block_cost_sampled_corr_fwd": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_ptr] + [c_int] * 6 + [c_ptr]),
+    "ts_block_cost_corr_split_supported": (c_int, [c_int] * 2),
+    "ts_block_cost_sampled_corr_split_fwd": (c_int, [c_f32p] * 6 + [c_ptr] + [c_int] * 7 + [ctypes.c_longlong] * 4 + [c_ptr]),
+    "ts_conv3d_hw_split_supported": (c_int, [c_int] * 10),
+    "ts_conv3d_hw_split_fwd": (c_int, [c_f32p] * 6 + [c_int] * 11 + [c_float] + [ctypes.c_longlong] * 6 +
+                               [c_f32p, ctypes.c_longlong, c_ptr, c_size, c_ptr]),
+    "ts_conv3d_d_split_supported": (c_int, [c_int] * 2),
+    "ts_conv3d_d_split_fwd": (c_int, [c_f32p] * 6 + [c_int] * 13 + [c_float] + [ctypes.c_longlong] * 6 + [c_ptr]),
+    "ts_conv3d_hw_x6_split_supported": (c_int, [c_int] * 5),
+    "ts_conv3d_hw_x6_split_fwd": (c_int, [c_f32p, c_f32p, c_ptr, c_f32p, c_f32p, c_f32p] + [c_int] * 9 + [c_float] + [ctypes.c_longlong] * 6 +
+                                  [c_f32p, ctypes.c_longlong, c_ptr, c_size, c_ptr]),
     "ts_conv3d_hw_warp_workspace_bytes": (c_size, [c_int] * 5),
     "ts_conv3d_hw_warp_fwd": (c_int, [c_f32p] * 8 + [c_int] * 8 + [c_float] + [ctypes.c_longlong] * 5 + [c_ptr, c_size, c_ptr]),
     "ts_cat_fms_fwd": (c_int, [c_f32p] * 4 + [c_int] * 5 + [c_ptr]),
@@ -167,6 +177,7 @@ SIGNATURES = {
 
 # entry points that only answer a question (nothing is enqueued): never part of a recorded plan
 _QUERIES = frozenset(n for n in SIGNATURES if n.endswith("_bytes") or n.startswith("ts_plan_") or
+                     n.endswith("_split_supported") or
                      n in ("ts_version", "ts_last_error_string", "ts_conv_cout_pad", "ts_conv3d_hw_x6_supported", "ts_conv3d_hw_x6s_supported", "ts_peer_max_floats", "ts_peer_max_ranks",
                            "ts_peer_alloc", "ts_peer_open", "ts_peer_close", "ts_peer_free", "ts_peer_status", "ts_peer_status_async",
                            "ts_peer_set_timeout_ms", "ts_peer_reset", "ts_bn_set_small_elems",

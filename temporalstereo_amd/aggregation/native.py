@@ -363,6 +363,9 @@ def _strides5(t):
     return t.stride(0), t.stride(1)
 
 
+Split = TF.Split        # an input whose channels live in two allocations (functional.py)
+
+
 # TS_CONV_X6=0: every (1,3,3) convolution on the f32-input MFMA kernel (A/B measurements, bit-exact fp32 products)
 X6 = os.environ.get("TS_CONV_X6", "1") != "0"
 # Grids below this many x6 workgroups stay on the f32 kernel (with its split-K) -- unless the x6 kernel splits the reduction itself
@@ -427,8 +430,17 @@ def conv_hw(x, f, stride=1, dilation=1, transposed=False, out=None, act=None, ac
     """x [B,Cin,D,H,W] -> [B,Cout,D,Ho,Wo].  addend [B,Cout,1,Ho,Wo]: added to every depth plane's raw sum.
     second: another tensor of x's shape with B == 1 -- the two are convolved as ONE batch of two (the batch stride
     handed to the kernel is simply the distance between the two allocations), without stacking them first.
-    out_second: with `second`, the second batch element's output goes to this separate tensor (`out` holds the first)."""
+    out_second: with `second`, the second batch element's output goes to this separate tensor (`out` holds the first).
+    x may be a Split: stride-1 layers only, same kernels and dispatch as on the concatenation."""
+    split = None
+    if isinstance(x, Split):
+        if second is not None or transposed or stride != 1:
+            raise ValueError("conv_hw(Split): stride-1, not transposed, no `second`")
+        x, split = x.a, x.b
     B, Cin, D, H, W = x.shape
+    if split is not None:
+        Cs, Cin = Cin, Cin + split.shape[1]
+        i2b, i2c = _strides5(split)
     if second is not None:
         if B != 1 or second.shape != x.shape or _strides5(second)[1] != _strides5(x)[1]:
             raise ValueError("conv_hw(second=...): two tensors of one shape and channel stride with batch 1")
@@ -473,6 +485,13 @@ def conv_hw(x, f, stride=1, dilation=1, transposed=False, out=None, act=None, ac
         # small grids stay on the f32 kernel (64-pixel tiles, its own split-K) unless the reduction is long enough for the x6 kernel's
         # split-K (wsb6 > 0) -- also where the f32 kernel would not split: 32 -> 32 on 3 x 34 x 60 is 6.2 us there against 15.7 us on x6
         ws6 = torch.empty(wsb6, device=x.device, dtype=torch.uint8) if wsb6 else None
+        if split is not None:
+            rc = L.ts_conv3d_hw_x6_split_fwd(_lib.ptr(x), _lib.ptr(split), _lib.ptr(x6_weights(f)), _lib.ptr(f.scale), _lib.ptr(f.shift),
+                                             _lib.ptr(out), B, Cin, Cs, f.cout, D, H, W, dilation, f.act if act is None else act,
+                                             float(act_param), ib, ic, i2b, i2c, ob, oc, _lib.ptr(addend),
+                                             addend.stride(0) if addend is not None else 0, _lib.ptr(ws6), wsb6, _stream())
+            _lib.check(rc, "ts_conv3d_hw_x6_split_fwd")
+            return out
         rc = L.ts_conv3d_hw_x6_fwd(_lib.ptr(x), _lib.ptr(x6_weights(f)), _lib.ptr(f.scale), _lib.ptr(f.shift), _lib.ptr(out),
                                    B, Cin, f.cout, D, H, W, dilation, f.act if act is None else act, float(act_param),
                                    ib, ic, ob, oc, _lib.ptr(addend), addend.stride(0) if addend is not None else 0, _lib.ptr(ws6), wsb6,
@@ -480,6 +499,13 @@ def conv_hw(x, f, stride=1, dilation=1, transposed=False, out=None, act=None, ac
         _lib.check(rc, "ts_conv3d_hw_x6_fwd")
         return out
     ws = torch.empty(wsb, device=x.device, dtype=torch.uint8) if wsb else None
+    if split is not None:
+        rc = L.ts_conv3d_hw_split_fwd(_lib.ptr(x), _lib.ptr(split), _lib.ptr(f.w), _lib.ptr(f.scale), _lib.ptr(f.shift), _lib.ptr(out),
+                                      B, Cin, Cs, f.cout, D, H, W, stride, dilation, 0, f.act if act is None else act,
+                                      float(act_param), ib, ic, i2b, i2c, ob, oc, _lib.ptr(addend),
+                                      addend.stride(0) if addend is not None else 0, _lib.ptr(ws), wsb, _stream())
+        _lib.check(rc, "ts_conv3d_hw_split_fwd")
+        return out
     rc = L.ts_conv3d_hw_fwd(_lib.ptr(x), _lib.ptr(f.w), _lib.ptr(f.scale), _lib.ptr(f.shift), _lib.ptr(out),
                             B, Cin, f.cout, D, H, W, stride, dilation, int(transposed),
                             f.act if act is None else act, float(act_param), ib, ic, ob, oc,
@@ -489,14 +515,27 @@ def conv_hw(x, f, stride=1, dilation=1, transposed=False, out=None, act=None, ac
 
 
 def conv_d(x, f, k, stride=1, dilation=1, padding=0, transposed=False, out=None, act=None, act_param=0.0):
-    """x [B,Cin,Din,H,W] -> [B,Cout,Dout,H,W]."""
+    """x [B,Cin,Din,H,W] (or a Split of it) -> [B,Cout,Dout,H,W]."""
+    split = None
+    if isinstance(x, Split):
+        x, split = x.a, x.b
     B, Cin, Din, H, W = x.shape
+    if split is not None:
+        Cs, Cin = Cin, Cin + split.shape[1]
+        i2b, i2c = _strides5(split)
     assert Cin == f.cin, (Cin, f.cin)
     Dout = 2 * Din if transposed else (Din + 2 * padding - dilation * (k - 1) - 1) // stride + 1
     if out is None:
         out = torch.empty((B, f.cout, Dout, H, W), device=x.device, dtype=torch.float32)
     ib, ic = _strides5(x)
     ob, oc = _strides5(out)
+    if split is not None:
+        rc = _lib.lib().ts_conv3d_d_split_fwd(_lib.ptr(x), _lib.ptr(split), _lib.ptr(f.w), _lib.ptr(f.scale), _lib.ptr(f.shift),
+                                              _lib.ptr(out), B, Cin, Cs, f.cout, Din, H, W, k, stride, dilation, padding,
+                                              int(transposed), f.act if act is None else act, float(act_param),
+                                              ib, ic, i2b, i2c, ob, oc, _stream())
+        _lib.check(rc, "ts_conv3d_d_split_fwd")
+        return out
     rc = _lib.lib().ts_conv3d_d_fwd(_lib.ptr(x), _lib.ptr(f.w), _lib.ptr(f.scale), _lib.ptr(f.shift), _lib.ptr(out),
                                     B, Cin, f.cout, Din, H, W, k, stride, dilation, padding, int(transposed),
                                     f.act if act is None else act, float(act_param), ib, ic, ob, oc, _stream())
@@ -507,11 +546,15 @@ def conv_d(x, f, k, stride=1, dilation=1, padding=0, transposed=False, out=None,
 # TS_FUSED_K1=0: the sampled levels build the warped half of their volume and convolve it (rounds 1-3) instead of the
 # pre-contracted form below (A/B measurements; both are held to the same fixtures)
 FUSED_K1 = os.environ.get("TS_FUSED_K1", "1") != "0"
+# TS_SPLIT_INPUT=0: the 1/4 level copies the backbone's features next to the UNet encoder's (two copy_rows launches per pass) and
+# hands its consumers one [feature | spx4] tensor, instead of reading the two allocations in place (Split; A/B measurements, and
+# what NativePrecise falls back to when a *_split_supported query refuses the shape)
+SPLIT_INPUT = os.environ.get("TS_SPLIT_INPUT", "1") != "0"
 
 
 def block_cost_corr(left, right, disp, scales):
     """The correlation blocks of the sampled block_cost alone (functional.block_cost_corr; reached as TF.<name> so that bench.py's
-    K1 probe sees the call)."""
+    K1 probe sees the call).  left / right may be Splits at the same channel."""
     return TF.block_cost_corr(left, right, disp, scales)
 
 
@@ -882,6 +925,25 @@ class NativeFine(_MergingLevel):
         return self.merge_fuse_predict(vol, ds, prev_info, left, resize_memory=False, mask=mask, next_range=next_range)
 
 
+class SplitBoth:
+    """What NativePrecise.unet_encode hands on when the 1/4 level reads its input in place: the backbone's features of the two views
+    and spx4 [2B, Cf, H, W] ([left | right] along the batch axis) -- in the place of the [2B, 2Cf, H, W] tensor `both`."""
+
+    def __init__(self, left, right, spx4):
+        self.left, self.right, self.spx4 = left, right, spx4
+
+    device = property(lambda self: self.spx4.device)
+    shape = property(lambda self: (self.spx4.shape[0], self.left.shape[1] + self.spx4.shape[1]) + tuple(self.spx4.shape[2:]))
+
+    def pair(self):
+        B = self.left.shape[0]
+        return Split(self.left, self.spx4[:B]), Split(self.right, self.spx4[B:])
+
+    def __getitem__(self, idx):
+        """Rows of the [2B, 2Cf, H, W] tensor this stands for (a framework copy: diagnostics, never part of a pass)."""
+        return torch.cat([s.cat() for s in self.pair()], 0)[idx]
+
+
 class NativePrecise(_LevelBase):
     def __init__(self, mod):
         super().__init__(mod)
@@ -923,7 +985,7 @@ class NativePrecise(_LevelBase):
             y = torch.empty((2 * B, e[2].cout, 1, Hy, Wy), device=li.device, dtype=torch.float32)
             conv_hw(s2_left, e[2], st[2], 1, out=y[:B]); conv_hw(s2_right, e[2], st[2], 1, out=y[B:])
             x = y
-        self._c2d(x, e[3], st[3], out=cat4[:, self.in_planes:].unsqueeze(2))
+        self._c2d(x, e[3], st[3], out=(cat4.spx4 if isinstance(cat4, SplitBoth) else cat4[:, self.in_planes:]).unsqueeze(2))
 
     def _deconv(self, x, f, out, out_bstride):
         B, Cin, H, W = x.shape
@@ -945,13 +1007,31 @@ class NativePrecise(_LevelBase):
         both, lterm, st = self.unet_encode(left, right, left_image, right_image)
         return both, (self.unet_decode(st), lterm)
 
+    def split_input_ok(self, B, Cf, H, W):
+        """Whether the four consumers of [feature | spx4] take it as a Split (the *_split_supported queries of include/ts_hip.h)."""
+        L = _lib.lib()
+        if self.in_planes != Cf or self.enc[3].cout != Cf:
+            return False
+        hw = lambda f, dil: L.ts_conv3d_hw_split_supported(B, 2 * Cf, Cf, f.cout, 1, H, W, 1, dil, 0)
+        return bool(L.ts_block_cost_corr_split_supported(2 * Cf, Cf) and hw(self.init0_left, self.init0.dil) and hw(self.fuse[0], 1) and
+                    (not FUSED_K1 or L.ts_conv3d_d_split_supported(2 * Cf, Cf)) and
+                    (not X6 or not L.ts_conv3d_hw_x6_supported(2 * Cf, self.fuse[0].cout, W, 1, 1, 0) or
+                     L.ts_conv3d_hw_x6_split_supported(2 * Cf, Cf, self.fuse[0].cout, W, 1)))
+
     def unet_encode(self, left, right, left_image, right_image):
         """First part of unet_features: the image encoder of both views, the [feature | spx4] concatenation and the first layer's
-        per-pixel terms -- what the 1/4 level's cost volume needs.  Returns (both, lterm, state for unet_decode)."""
+        per-pixel terms -- what the 1/4 level's cost volume needs.  Returns (both, lterm, state for unet_decode).
+        SPLIT_INPUT: the concatenation is never made -- the backbone's features stay where they are, the encoder writes spx4 of both
+        views into one allocation, and the consumers read (feature, spx4) pairs in place."""
         B, Cf, H, W = left.shape
-        both = torch.empty((2 * B, 2 * Cf, H, W), device=left.device, dtype=torch.float32)   # [left | right] x [feat | spx4]
-        lcat, rcat = both[:B], both[B:]
-        copy_rows(left, lcat[:, :Cf]); copy_rows(right, rcat[:, :Cf])
+        if SPLIT_INPUT and FUSED_K1 and self.split_input_ok(B, Cf, H, W):
+            left, right = _lib.contiguous(left), _lib.contiguous(right)
+            both = SplitBoth(left, right, torch.empty((2 * B, Cf, H, W), device=left.device, dtype=torch.float32))
+            lcat, rcat = both.pair()
+        else:
+            both = torch.empty((2 * B, 2 * Cf, H, W), device=left.device, dtype=torch.float32)   # [left | right] x [feat | spx4]
+            lcat, rcat = both[:B], both[B:]
+            copy_rows(left, lcat[:, :Cf]); copy_rows(right, rcat[:, :Cf])
         C32, C2 = self.deconv4.cout, self.enc[1].cout
         cat2 = torch.empty((B, C32 + C2, 2 * H, 2 * W), device=left.device, dtype=torch.float32)      # [deconv4 | s2 of the left view]
         self.encode(left_image, right_image, both, cat2[:, C32:].unsqueeze(2))
@@ -971,7 +1051,7 @@ class NativePrecise(_LevelBase):
     def early(self, both, lterm, ds):
         """Cost volume + first layer + init3d of the 1/4 level (precise.py:88-93)."""
         B = both.shape[0] // 2
-        lcat, rcat = both[:B], both[B:]
+        lcat, rcat = both.pair() if isinstance(both, SplitBoth) else (both[:B], both[B:])
         lt, rt = lterm
         if rt is not None:
             return self.init3d_from(self.first_layer_fused(lcat, rcat, ds, lt, rt))

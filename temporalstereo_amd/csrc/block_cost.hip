@@ -40,7 +40,22 @@ struct Shape {
   int nbxp;       // nbx padded so that a wavefront does not straddle candidates (when cheap)
   int Wq, Wqp;    // quarter-row length and its padded LDS stride
   float rh1, rw1, rh2, rw2;  // align_corners scales (in-1)/(out-1) of the two pooled maps
+  // split input (ts_block_cost_sampled_corr_split_fwd): channels [0, csplit) of a map come from the pointer the kernel is handed,
+  // channels [csplit, C) from L2 / R2; every base is [B][.][H][W] with dense planes and a batch stride of its own (elements).
+  // csplit == C: one base per map.  A channel group of 8 never straddles the seam (csplit % 8 == 0).
+  int csplit;
+  const float* L2;
+  const float* R2;
+  long long lbs, lbs2, rbs, rbs2;
 };
+
+// first plane of channel group g of batch item b of a (possibly split) map: one uniform choice per workgroup
+__device__ __forceinline__ const float* group_base(const float* A, const float* A2, long long bs, long long bs2, int csplit, int b,
+                                                   int g, size_t HW) {
+  const int c = g * 8;
+  return c < csplit ? A + static_cast<long long>(b) * bs + static_cast<size_t>(c) * HW
+                    : A2 + static_cast<long long>(b) * bs2 + static_cast<size_t>(c - csplit) * HW;
+}
 
 template <bool VEC>
 __device__ __forceinline__ float4 ld4(const float* __restrict__ row, int x, int W) {
@@ -162,8 +177,8 @@ block_cost_main(const float* __restrict__ L, const float* __restrict__ R,
   const int y0 = by * TR;
   const int H = s.H, W = s.W, D = s.D, C = s.C;
   const size_t HW = static_cast<size_t>(H) * W;
-  const float* Lg = L + (static_cast<size_t>(b) * C + g * GRP) * HW;
-  const float* Rg = R + (static_cast<size_t>(b) * C + g * GRP) * HW;
+  const float* Lg = group_base(L, s.L2, s.lbs, s.lbs2, s.csplit, b, g, HW);
+  const float* Rg = group_base(R, s.R2, s.rbs, s.rbs2, s.csplit, b, g, HW);
   const int Wl = 4 * s.Wq;                                    // LDS row length of the left rows
   float* ldsL = lds + static_cast<size_t>(GRP) * TR * 4 * s.Wqp;   // [c][r & 1][Wl]
 
@@ -424,8 +439,8 @@ block_cost_fast(const float* __restrict__ L, const float* __restrict__ R,
   const int y0 = by * TR;
   const int H = s.H, W = s.W, D = s.D, C = s.C;
   const unsigned HW = static_cast<unsigned>(H) * W;
-  const float* Lg = L + (static_cast<size_t>(b) * C + g * GRP) * HW;
-  const float* Rg = R + (static_cast<size_t>(b) * C + g * GRP) * HW;
+  const float* Lg = group_base(L, s.L2, s.lbs, s.lbs2, s.csplit, b, g, HW);
+  const float* Rg = group_base(R, s.R2, s.rbs, s.rbs2, s.csplit, b, g, HW);
   const int Wq = s.Wq, Wqp = s.Wqp, Wl = 4 * s.Wq;
   float4* ldsR4 = reinterpret_cast<float4*>(lds);                       // [2][TR][4][Wqp]
   // left rows: two at a time with rows 2,3 carried in registers (NP <= 3: what every shipped geometry uses), or --
@@ -659,8 +674,9 @@ block_cost_corr_rows(const float* __restrict__ L, const float* __restrict__ R, c
   const int tid = threadIdx.x, nthr = blockDim.x;
   constexpr unsigned OOR = 0x3ffffff0u;
   const unsigned dHW = static_cast<unsigned>(D) * HW;
-  const __amdgpu_buffer_rsrc_t lrs = make_rsrc(L + (static_cast<size_t>(b) * C + g * GRP) * HW, static_cast<unsigned>(GRP) * HW * 4u);
-  const __amdgpu_buffer_rsrc_t rrs = make_rsrc(R + (static_cast<size_t>(b) * C + g * GRP) * HW, static_cast<unsigned>(GRP) * HW * 4u);
+  // (each group's eight planes behind a descriptor of their own: a split map's two bases never share one)
+  const __amdgpu_buffer_rsrc_t lrs = make_rsrc(group_base(L, s.L2, s.lbs, s.lbs2, s.csplit, b, g, HW), static_cast<unsigned>(GRP) * HW * 4u);
+  const __amdgpu_buffer_rsrc_t rrs = make_rsrc(group_base(R, s.R2, s.rbs, s.rbs2, s.csplit, b, g, HW), static_cast<unsigned>(GRP) * HW * 4u);
   const __amdgpu_buffer_rsrc_t drs = make_rsrc(disp + static_cast<size_t>(b) * dHW, dHW * 4u);
   const __amdgpu_buffer_rsrc_t orsrc = make_rsrc(out + static_cast<size_t>(b) * s.Ctot * dHW, static_cast<unsigned>(s.Ctot) * dHW * 4u);
 
@@ -1200,6 +1216,8 @@ int make_shape(Shape& s, bool sampled, int B, int C, int H, int W, int D, int sc
   s.G = C / GRP;
   s.omit_ref = sampled ? omit_ref : 0;
   s.tch = s.omit_ref ? 0 : C;
+  s.csplit = C; s.L2 = s.R2 = nullptr;
+  s.lbs = s.lbs2 = s.rbs = s.rbs2 = static_cast<long long>(C) * H * W;
   s.mainC = (sampled && !omit_ref) ? 2 * C : (s.omit_ref == 2 ? 0 : C);
   s.Ctot = s.mainC + scales * s.G;
   s.H1 = H / 2; s.W1 = W / 2; s.H2 = H / 4; s.W2 = W / 4;
@@ -1225,19 +1243,33 @@ size_t pooled_bytes(const Shape& s, int lvl) {
   return ts::round_up(n * sizeof(float), 256);
 }
 
+// second bases of a split input (launch_fwd): channels [csplit, C) of the two maps, and the four batch strides
+struct SplitMaps {
+  const float* left2;
+  const float* right2;
+  int csplit;
+  long long lbs, lbs2, rbs, rbs2;
+};
+
 template <bool SAMPLED>
 int launch_fwd(const float* left, const float* right, const float* disp, float* out, void* workspace,
-               int B, int C, int H, int W, int D, int scales, void* stream, int omit_ref = 0) {
+               int B, int C, int H, int W, int D, int scales, void* stream, int omit_ref = 0, const SplitMaps* split = nullptr) {
   Shape s;
   if (int rc = make_shape(s, SAMPLED, B, C, H, W, D, scales, omit_ref)) return rc;
   TS_REQUIRE_PTR(left); TS_REQUIRE_PTR(right); TS_REQUIRE_PTR(out);
+  if (split) {
+    s.csplit = split->csplit; s.L2 = split->left2; s.R2 = split->right2;
+    s.lbs = split->lbs; s.lbs2 = split->lbs2; s.rbs = split->rbs; s.rbs2 = split->rbs2;
+  }
   if (SAMPLED) TS_REQUIRE_PTR(disp);
   if (scales > 1) TS_REQUIRE_PTR(workspace);
   float* P1 = reinterpret_cast<float*>(workspace);
   float* P2 = scales > 1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + pooled_bytes(s, 1)) : nullptr;
 
   const bool vec = (W % 4 == 0) && ts::aligned16(left) && ts::aligned16(right) && ts::aligned16(out) &&
-                   (!SAMPLED || ts::aligned16(disp));
+                   (!SAMPLED || ts::aligned16(disp)) &&
+                   (!split || (ts::aligned16(split->left2) && ts::aligned16(split->right2) &&
+                               (split->lbs | split->lbs2 | split->rbs | split->rbs2) % 4 == 0));
   const int nitems = s.nbxp * D;
   // one pass when the row of items fits a workgroup, otherwise an even split over the fewest passes
   const int passes = (nitems + 511) / 512;
@@ -2128,6 +2160,28 @@ extern "C" int ts_block_cost_sampled_corr_fwd(const float* left, const float* ri
                                               void* workspace, int B, int C, int H, int W, int D, int scales,
                                               void* stream) {
   return launch_fwd<true>(left, right, disp, out, workspace, B, C, H, W, D, scales, stream, 2);
+}
+
+// Split-input form of ts_block_cost_sampled_corr_fwd: channels [0, Csplit) of the left / right map are read from `left` / `right`,
+// channels [Csplit, C) from `left2` / `right2` -- the same launches, the same arithmetic in the same order, without the concatenation
+// ever being made.  Every base is [B][.][H][W] with dense planes and its own batch stride (elements).
+extern "C" int ts_block_cost_corr_split_supported(int C, int Csplit) {
+  return C > 0 && C % GRP == 0 && Csplit > 0 && Csplit < C && Csplit % 32 == 0;
+}
+
+extern "C" int ts_block_cost_sampled_corr_split_fwd(const float* left, const float* left2, const float* right, const float* right2,
+                                                    const float* disp, float* out, void* workspace, int B, int C, int Csplit, int H,
+                                                    int W, int D, int scales, long long left_bstride, long long left2_bstride,
+                                                    long long right_bstride, long long right2_bstride, void* stream) {
+  TS_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && D > 0, TS_ERR_SHAPE, "block_cost_corr_split: non-positive size");
+  TS_REQUIRE(ts_block_cost_corr_split_supported(C, Csplit), TS_ERR_UNSUPPORTED,
+             "block_cost_corr_split: Csplit=%d must be a multiple of 32 inside (0, C=%d)", Csplit, C);
+  TS_REQUIRE_PTR(left2); TS_REQUIRE_PTR(right2);
+  const long long hw = static_cast<long long>(H) * W;
+  TS_REQUIRE(left_bstride >= Csplit * hw && right_bstride >= Csplit * hw && left2_bstride >= (C - Csplit) * hw &&
+             right2_bstride >= (C - Csplit) * hw, TS_ERR_SHAPE, "block_cost_corr_split: a batch stride is shorter than its channels");
+  const SplitMaps sm{left2, right2, Csplit, left_bstride, left2_bstride, right_bstride, right2_bstride};
+  return launch_fwd<true>(left, right, disp, out, workspace, B, C, H, W, D, scales, stream, 2, &sm);
 }
 
 namespace {

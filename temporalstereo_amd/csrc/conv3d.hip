@@ -218,8 +218,9 @@ ig_conv_kernel(const float* __restrict__ x, const float* __restrict__ w, const f
     wl[q] = v < WV ? r * WP + co4 * 4 : KTW * NC * WP;
   }
   const __amdgpu_buffer_rsrc_t xr = ig_rsrc(x + static_cast<long long>(b) * p.in_bstride, p.in_bytes);   // signed: the batch stride may be the distance between two allocations
+  const __amdgpu_buffer_rsrc_t xr2 = ig_rsrc(p.x2 + static_cast<long long>(b) * p.in2_bstride, p.in2_bytes);   // split input: a descriptor of its own, sized to its own allocation
   const __amdgpu_buffer_rsrc_t wr = ig_rsrc(w, p.w_bytes);
-  const unsigned cstride_b = static_cast<unsigned>(p.in_cstride) * 4u;
+  const unsigned cstride_b = static_cast<unsigned>(p.in_cstride) * 4u, cstride2_b = static_cast<unsigned>(p.in2_cstride) * 4u;
   const unsigned wstride_b = static_cast<unsigned>(KT * p.coutp) * 4u;
 
   // ---- per-lane fragment bases ----------------------------------------------------------------
@@ -274,26 +275,27 @@ ig_conv_kernel(const float* __restrict__ x, const float* __restrict__ w, const f
   const int wave_u = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));   // uniform: the channel offsets stay scalar
   auto fetch = [&](auto set, int c0) {
     constexpr int S = decltype(set)::value;
+    const ChunkBase cbs = chunk_base(c0, p.csplit, xr, xr2, cstride_b, cstride2_b);       // the chunk's side of a split input's seam
     if constexpr (VD64) {
 #pragma unroll
       for (int i = 0; i < NI64; ++i) {
-        const unsigned chb = static_cast<unsigned>(min(c0 + ch64[i], p.Cin - 1)) * cstride_b;
-        rin64[S][i] = __builtin_amdgcn_raw_buffer_load_b128(xr, go64[i] == kOOB ? kOOB : go64[i] + chb, 0, 0);
+        const unsigned chb = static_cast<unsigned>(min(c0 + ch64[i], p.Cin - 1) - cbs.c_first) * cbs.cstride_b;
+        rin64[S][i] = __builtin_amdgcn_raw_buffer_load_b128(cbs.rsrc, go64[i] == kOOB ? kOOB : go64[i] + chb, 0, 0);
       }
     } else if constexpr (VD) {
 #pragma unroll
       for (int ic = 0; ic < NCQ; ++ic) {
-        const unsigned so = static_cast<unsigned>(min(c0 + wave_u + 4 * ic, p.Cin - 1)) * cstride_b;
+        const unsigned so = static_cast<unsigned>(min(c0 + wave_u + 4 * ic, p.Cin - 1) - cbs.c_first) * cbs.cstride_b;
 #pragma unroll
-        for (int t = 0; t < NTR; ++t) rin4[S][ic][t] = __builtin_amdgcn_raw_buffer_load_b128(xr, goff[t], so, 0);
+        for (int t = 0; t < NTR; ++t) rin4[S][ic][t] = __builtin_amdgcn_raw_buffer_load_b128(cbs.rsrc, goff[t], so, 0);
       }
     } else {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       // channels past the slice re-read the last real one; their weights are zero
-      const unsigned so = static_cast<unsigned>(min(c0 + c, p.Cin - 1)) * cstride_b;
+      const unsigned so = static_cast<unsigned>(min(c0 + c, p.Cin - 1) - cbs.c_first) * cbs.cstride_b;
 #pragma unroll
-      for (int i = 0; i < RQ; ++i) rin[S][c][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(xr, goff[i], so, 0));
+      for (int i = 0; i < RQ; ++i) rin[S][c][i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(cbs.rsrc, goff[i], so, 0));
     }
     }
     const unsigned wso = static_cast<unsigned>(c0) * wstride_b;
@@ -619,7 +621,7 @@ ig_conv_x6_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, con
   const int co0 = cog * COB;
   const int ty0 = (tile / p.tiles_x) * TR, tx0 = (tile % p.tiles_x) * 32;
   const unsigned HW = static_cast<unsigned>(p.H) * p.W;
-  const unsigned cstride_b = static_cast<unsigned>(p.in_cstride) * 4u;
+  const unsigned cstride_b = static_cast<unsigned>(p.in_cstride) * 4u, cstride2_b = static_cast<unsigned>(p.in2_cstride) * 4u;
 
   const bool stager = threadIdx.x < SPC * SLOTS;
   const int spart = static_cast<int>(threadIdx.x) / SLOTS;                    // which 16 / SPC channels of the chunk this thread stages
@@ -645,6 +647,7 @@ ig_conv_x6_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, con
     wl[q] = v < WV ? v : WV;
   }
   const __amdgpu_buffer_rsrc_t xr = ig_rsrc(x + static_cast<long long>(b) * p.in_bstride, p.in_bytes);
+  const __amdgpu_buffer_rsrc_t xr2 = ig_rsrc(p.x2 + static_cast<long long>(b) * p.in2_bstride, p.in2_bytes);   // split input: its own descriptor and extent
   const __amdgpu_buffer_rsrc_t wr = ig_rsrc(w6, p.w_bytes);
   const unsigned wchunk_b = static_cast<unsigned>(3 * X6_SLOTS * 2 * p.coutp) * 16u;
 
@@ -675,11 +678,12 @@ ig_conv_x6_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, con
   v4f rin[NCH];
   u32x4 rw[RWN];
   auto fetch = [&](int c0) {
+    const ChunkBase cbs = chunk_base(c0, p.csplit, xr, xr2, cstride_b, cstride2_b);       // the chunk's side of a split input's seam
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       // channels past Cin re-read the last real one; their weights are zero
-      const unsigned co = static_cast<unsigned>(min(c0 + spart * NCH + c, p.Cin - 1)) * cstride_b;
-      rin[c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xr, goff == kOOB ? kOOB : goff + co, 0, 0));
+      const unsigned co = static_cast<unsigned>(min(c0 + spart * NCH + c, p.Cin - 1) - cbs.c_first) * cbs.cstride_b;
+      rin[c] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(cbs.rsrc, goff == kOOB ? kOOB : goff + co, 0, 0));
     }
     const unsigned wso = static_cast<unsigned>(c0 / X6_NC) * wchunk_b;
 #pragma unroll
@@ -1021,6 +1025,26 @@ bool ig_extent(IG& p, int KT) {
   if (in_b >= 0x7fffffffull || w_b >= 0x7fffffffull || p.in_cstride < 0) return false;
   p.in_bytes = static_cast<unsigned>(in_b); p.w_bytes = static_cast<unsigned>(w_b);
   p.out_bytes = p.part_bytes = 0;             // set by ig_out_extent once the output geometry is known
+  p.x2 = nullptr; p.csplit = 0x7fffffff; p.in2_bstride = p.in2_cstride = 0; p.in2_bytes = 0;      // one base (ig_split replaces these)
+  return true;
+}
+
+// Second base of a split input (the *_split_fwd entries): channels [csplit, Cin) of x with their own strides.
+struct SplitIn {
+  const float* x2;
+  int csplit;
+  long long bstride, cstride;
+};
+// Csplit is a multiple of the widest K chunk any instantiation stages (32), so no chunk straddles the seam
+bool split_point_ok(int Cin, int Csplit) { return Csplit > 0 && Csplit < Cin && Csplit % 32 == 0; }
+// after ig_extent: x's descriptor shrinks to its csplit channels, x2 gets a descriptor over its Cin - csplit; false = an extent is out of range
+bool ig_split(IG& p, const SplitIn& sp) {
+  const unsigned long long plane = static_cast<unsigned long long>(p.D) * p.H * p.W;
+  const unsigned long long b1 = (static_cast<unsigned long long>(sp.csplit - 1) * p.in_cstride + plane) * 4ull;
+  const unsigned long long b2 = (static_cast<unsigned long long>(p.Cin - sp.csplit - 1) * sp.cstride + plane) * 4ull;
+  if (b1 >= 0x7fffffffull || b2 >= 0x7fffffffull || sp.cstride < 0) return false;
+  p.in_bytes = static_cast<unsigned>(b1);
+  p.x2 = sp.x2; p.csplit = sp.csplit; p.in2_bstride = sp.bstride; p.in2_cstride = sp.cstride; p.in2_bytes = static_cast<unsigned>(b2);
   return true;
 }
 
@@ -1412,7 +1436,7 @@ int conv_hw_impl(const float* x, const float* w_t, const float* scale, const flo
                  long long in_bstride, long long in_cstride, long long out_bstride,
                  long long out_cstride, const float* addend, long long addend_bstride,
                  void* workspace, size_t workspace_bytes, int out_h, int out_w, void* stream,
-                 long long addend_cstride = 0, long long addend_dstride = 0) {
+                 long long addend_cstride = 0, long long addend_dstride = 0, const SplitIn* sp = nullptr) {
   TS_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "conv3d_hw: non-positive size");
   TS_REQUIRE(stride == 1 || stride == 2, TS_ERR_UNSUPPORTED, "conv3d_hw: stride must be 1 or 2");
   TS_REQUIRE(dilation == 1 || dilation == 2, TS_ERR_UNSUPPORTED, "conv3d_hw: dilation must be 1 or 2");
@@ -1434,6 +1458,12 @@ int conv_hw_impl(const float* x, const float* w_t, const float* scale, const flo
   p.add_dstride = addend_dstride;
   TS_REQUIRE(!(addend && transposed), TS_ERR_UNSUPPORTED, "conv3d_hw: no addend in the transposed form");
   TS_REQUIRE(ig_extent(p, 9), TS_ERR_UNSUPPORTED, "conv3d_hw: a batch element of x spans 2 GiB or more");
+  if (sp) {
+    TS_REQUIRE_PTR(sp->x2);
+    TS_REQUIRE(!transposed && split_point_ok(Cin, sp->csplit), TS_ERR_UNSUPPORTED,
+               "conv3d_hw_split: Csplit=%d must be a multiple of 32 inside (0, Cin=%d), not the transposed form", sp->csplit, Cin);
+    TS_REQUIRE(ig_split(p, *sp), TS_ERR_UNSUPPORTED, "conv3d_hw_split: a batch element of x2 spans 2 GiB or more");
+  }
   if (transposed) {
     p.Ho = out_h ? out_h : 2 * H; p.Wo = out_w ? out_w : 2 * W;
     TS_REQUIRE(p.Ho >= 2 * H - 1 && p.Ho <= 2 * H && p.Wo >= 2 * W - 1 && p.Wo <= 2 * W, TS_ERR_SHAPE,
@@ -1452,6 +1482,8 @@ int conv_hw_impl(const float* x, const float* w_t, const float* scale, const flo
     p.ksplit = ksplit;
     p.kspan = ((Cin + ksplit - 1) / ksplit + 7) / 8 * 8;
     p.partial = reinterpret_cast<float*>(workspace);
+    // a slice starts a chunk sequence of its own: the seam stays on a chunk boundary only if the slices are whole 32-channel chunks
+    TS_REQUIRE(!sp || p.kspan % 32 == 0, TS_ERR_UNSUPPORTED, "conv3d_hw_split: split-K slices of %d channels cut the seam's chunk", p.kspan);
   }
   int rc;
   if (stride == 2) rc = launch_ig<MODE_HW, 9, 2, 1>(x, w_t, scale, shift, y, p, B, tiles, D, st);
@@ -1646,11 +1678,12 @@ extern "C" int ts_conv3d_hw_x6_weight_split_from(const float* w, void* w6, int C
   return ts::launched("weight_split6_kernel");
 }
 
-extern "C" int ts_conv3d_hw_x6_fwd(const float* x, const void* w6, const float* scale, const float* shift, float* y,
-                                   int B, int Cin, int Cout, int D, int H, int W, int dilation, int act, float act_param,
-                                   long long in_bstride, long long in_cstride, long long out_bstride,
-                                   long long out_cstride, const float* addend, long long addend_bstride,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+int conv_hw_x6_impl(const float* x, const void* w6, const float* scale, const float* shift, float* y,
+                    int B, int Cin, int Cout, int D, int H, int W, int dilation, int act, float act_param,
+                    long long in_bstride, long long in_cstride, long long out_bstride,
+                    long long out_cstride, const float* addend, long long addend_bstride,
+                    void* workspace, size_t workspace_bytes, void* stream, const SplitIn* sp) {
   TS_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "conv3d_hw_x6: non-positive size");
   TS_REQUIRE(ts_conv3d_hw_x6_supported(Cin, Cout, W, 1, dilation, 0), TS_ERR_UNSUPPORTED,
              "conv3d_hw_x6: needs Cin >= 16, 8 < Cout <= 512, W %% 4 == 0, dilation 1 | 2 (Cin=%d Cout=%d W=%d dilation=%d)", Cin, Cout,
@@ -1667,6 +1700,12 @@ extern "C" int ts_conv3d_hw_x6_fwd(const float* x, const void* w6, const float* 
   p.ksplit = 1; p.kspan = (Cin + X6_NC - 1) / X6_NC * X6_NC; p.partial = nullptr; p.B = B; p.xcd = !no_xcd;
   p.addend = addend; p.add_bstride = addend_bstride; p.add_cstride = static_cast<long long>(H) * W; p.add_dstride = 0;
   TS_REQUIRE(ig_extent(p, 9), TS_ERR_UNSUPPORTED, "conv3d_hw_x6: a batch element of x spans 2 GiB or more");
+  if (sp) {      // both x6 kernels walk 16-channel chunks from channel 0 (their split-K slices are whole chunks): the seam is a chunk boundary
+    TS_REQUIRE_PTR(sp->x2);
+    TS_REQUIRE(split_point_ok(Cin, sp->csplit), TS_ERR_UNSUPPORTED, "conv3d_hw_x6_split: Csplit=%d must be a multiple of 32 inside (0, Cin=%d)",
+               sp->csplit, Cin);
+    TS_REQUIRE(ig_split(p, *sp), TS_ERR_UNSUPPORTED, "conv3d_hw_x6_split: a batch element of x2 spans 2 GiB or more");
+  }
   const size_t wb = x6_weight_bytes(Cin, Cout);
   TS_REQUIRE(wb < 0x7fffffffull, TS_ERR_UNSUPPORTED, "conv3d_hw_x6: weight array too large");
   p.w_bytes = static_cast<unsigned>(wb);
@@ -1710,6 +1749,7 @@ extern "C" int ts_conv3d_hw_x6_fwd(const float* x, const void* w6, const float* 
     q.Cin = Cin; q.Cout = Cout; q.coutp = p.coutp; q.B = B; q.D = D; q.H = H; q.W = W; q.act = act; q.act_param = act_param;
     q.in_bstride = in_bstride; q.in_cstride = in_cstride; q.out_bstride = out_bstride; q.out_cstride = out_cstride;
     q.in_bytes = p.in_bytes; q.w_bytes = p.w_bytes; q.out_bytes = p.out_bytes;
+    q.x2 = p.x2; q.csplit = p.csplit; q.in2_bstride = p.in2_bstride; q.in2_cstride = p.in2_cstride; q.in2_bytes = p.in2_bytes;
     q.addend = addend; q.add_bstride = addend_bstride; q.add_cstride = p.add_cstride; q.xcd = p.xcd; q.tiles_x = 0; q.co_groups = 0;
     const int nchunk = (Cin + X6_NC - 1) / X6_NC;
     q.ksplit = 1; q.kspan = nchunk; q.partial = nullptr; q.part_bytes = 0;
@@ -1757,6 +1797,33 @@ extern "C" int ts_conv3d_hw_x6_fwd(const float* x, const void* w6, const float* 
                      B, Cout, plane, ksplit, act, act_param, out_bstride, out_cstride, addend, addend_bstride, static_cast<long long>(H) * W);
   return ts::launched("conv_splitk_finish");
 }
+}  // namespace
+
+extern "C" int ts_conv3d_hw_x6_fwd(const float* x, const void* w6, const float* scale, const float* shift, float* y,
+                                   int B, int Cin, int Cout, int D, int H, int W, int dilation, int act, float act_param,
+                                   long long in_bstride, long long in_cstride, long long out_bstride,
+                                   long long out_cstride, const float* addend, long long addend_bstride,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  return conv_hw_x6_impl(x, w6, scale, shift, y, B, Cin, Cout, D, H, W, dilation, act, act_param, in_bstride, in_cstride, out_bstride,
+                         out_cstride, addend, addend_bstride, workspace, workspace_bytes, stream, nullptr);
+}
+
+// Split-input form of ts_conv3d_hw_x6_fwd: input channels [0, Csplit) from x, [Csplit, Cin) from x2 (its own batch / channel strides,
+// its own buffer descriptor: a halo offset reads zero from either, never the neighbouring allocation).  Same kernel choice, same
+// chunk order: bit-identical to ts_conv3d_hw_x6_fwd on the concatenation.
+extern "C" int ts_conv3d_hw_x6_split_supported(int Cin, int Csplit, int Cout, int W, int dilation) {
+  return ts_conv3d_hw_x6_supported(Cin, Cout, W, 1, dilation, 0) && split_point_ok(Cin, Csplit);
+}
+
+extern "C" int ts_conv3d_hw_x6_split_fwd(const float* x, const float* x2, const void* w6, const float* scale, const float* shift, float* y,
+                                         int B, int Cin, int Csplit, int Cout, int D, int H, int W, int dilation, int act, float act_param,
+                                         long long in_bstride, long long in_cstride, long long in2_bstride, long long in2_cstride,
+                                         long long out_bstride, long long out_cstride, const float* addend, long long addend_bstride,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  const SplitIn sp{x2, Csplit, in2_bstride, in2_cstride};
+  return conv_hw_x6_impl(x, w6, scale, shift, y, B, Cin, Cout, D, H, W, dilation, act, act_param, in_bstride, in_cstride, out_bstride,
+                         out_cstride, addend, addend_bstride, workspace, workspace_bytes, stream, &sp);
+}
 
 extern "C" int ts_conv3d_hw_fwd(const float* x, const float* w_t, const float* scale, const float* shift, float* y,
                                 int B, int Cin, int Cout, int D, int H, int W, int stride, int dilation,
@@ -1767,6 +1834,31 @@ extern "C" int ts_conv3d_hw_fwd(const float* x, const float* w_t, const float* s
   return conv_hw_impl(x, w_t, scale, shift, y, B, Cin, Cout, D, H, W, stride, dilation, transposed, act, act_param,
                       in_bstride, in_cstride, out_bstride, out_cstride, addend, addend_bstride, workspace, workspace_bytes,
                       0, 0, stream);
+}
+
+// Split-input form of ts_conv3d_hw_fwd: input channels [0, Csplit) from x, [Csplit, Cin) from x2 (its own batch / channel strides).
+// The same kernels, the same chunk order: the result is bit-identical to ts_conv3d_hw_fwd on the concatenation.  Refused
+// (TS_ERR_UNSUPPORTED): a Csplit that is not a multiple of 32 inside (0, Cin), the transposed form, and a split-K launch whose slices
+// are not whole 32-channel chunks -- ts_conv3d_hw_split_supported answers for a shape, assuming the workspace
+// ts_conv3d_hw_workspace_bytes names is handed over.
+extern "C" int ts_conv3d_hw_split_supported(int B, int Cin, int Csplit, int Cout, int D, int H, int W, int stride, int dilation,
+                                            int transposed) {
+  if (B <= 0 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0 || transposed || !split_point_ok(Cin, Csplit)) return 0;
+  if (!(stride == 1 || stride == 2) || !(dilation == 1 || dilation == 2) || (stride == 2 && dilation == 2)) return 0;
+  const int ks = conv_hw_ksplit(B, Cin, Cout, D, (H - 1) / stride + 1, (W - 1) / stride + 1, stride);
+  return ks == 1 || (((Cin + ks - 1) / ks + 7) / 8 * 8) % 32 == 0;
+}
+
+extern "C" int ts_conv3d_hw_split_fwd(const float* x, const float* x2, const float* w_t, const float* scale, const float* shift, float* y,
+                                      int B, int Cin, int Csplit, int Cout, int D, int H, int W, int stride, int dilation,
+                                      int transposed, int act, float act_param,
+                                      long long in_bstride, long long in_cstride, long long in2_bstride, long long in2_cstride,
+                                      long long out_bstride, long long out_cstride, const float* addend, long long addend_bstride,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  const SplitIn sp{x2, Csplit, in2_bstride, in2_cstride};
+  return conv_hw_impl(x, w_t, scale, shift, y, B, Cin, Cout, D, H, W, stride, dilation, transposed, act, act_param,
+                      in_bstride, in_cstride, out_bstride, out_cstride, addend, addend_bstride, workspace, workspace_bytes,
+                      0, 0, stream, 0, 0, &sp);
 }
 
 // ---- first layer of a sampled level from [corr | Q] (see warp_gather_kernel) ----------------------------------------------
@@ -1863,7 +1955,7 @@ int conv_d_impl(const float* x, const float* w_t, const float* scale, const floa
                 int B, int Cin, int Cout, int Din, int H, int W, int k, int stride, int dilation,
                 int padding, int transposed, int act, float act_param,
                 long long in_bstride, long long in_cstride, long long out_bstride,
-                long long out_cstride, int out_d, void* stream) {
+                long long out_cstride, int out_d, void* stream, const SplitIn* sp = nullptr) {
   TS_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && Din > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "conv3d_d: non-positive size");
   TS_REQUIRE(k == 1 || k == 3 || k == 5, TS_ERR_UNSUPPORTED, "conv3d_d: k must be 1, 3 or 5");
   TS_REQUIRE(stride >= 1 && stride <= 2 && dilation >= 1 && padding >= 0, TS_ERR_UNSUPPORTED, "conv3d_d: bad stride/dilation/padding");
@@ -1884,6 +1976,12 @@ int conv_d_impl(const float* x, const float* w_t, const float* scale, const floa
   p.tiles_x = 1; p.co_groups = 1; p.ksplit = 1; p.kspan = Cin; p.partial = nullptr;
   p.addend = nullptr; p.add_bstride = 0; p.add_cstride = 0; p.add_dstride = 0;
   TS_REQUIRE(ig_extent(p, k), TS_ERR_UNSUPPORTED, "conv3d_d: a batch element of x spans 2 GiB or more");
+  if (sp) {
+    TS_REQUIRE_PTR(sp->x2);
+    TS_REQUIRE(split_point_ok(Cin, sp->csplit), TS_ERR_UNSUPPORTED, "conv3d_d_split: Csplit=%d must be a multiple of 32 inside (0, Cin=%d)",
+               sp->csplit, Cin);
+    TS_REQUIRE(ig_split(p, *sp), TS_ERR_UNSUPPORTED, "conv3d_d_split: a batch element of x2 spans 2 GiB or more");
+  }
   const int tiles = (H * W + 255) / 256;
   if (k == 1) return launch_ig<MODE_D, 1, 1, 1>(x, w_t, scale, shift, y, p, B, tiles, Dout, st);
   if (k == 3) return launch_ig<MODE_D, 3, 1, 1>(x, w_t, scale, shift, y, p, B, tiles, Dout, st);
@@ -1898,6 +1996,20 @@ extern "C" int ts_conv3d_d_fwd(const float* x, const float* w_t, const float* sc
                                long long out_cstride, void* stream) {
   return conv_d_impl(x, w_t, scale, shift, y, B, Cin, Cout, Din, H, W, k, stride, dilation, padding, transposed, act,
                      act_param, in_bstride, in_cstride, out_bstride, out_cstride, 0, stream);
+}
+
+// Split-input form of ts_conv3d_d_fwd: input channels [0, Csplit) from x, [Csplit, Cin) from x2 (its own batch / channel strides).
+// The same kernels, the same chunk order: the result is bit-identical to ts_conv3d_d_fwd on the concatenation.
+extern "C" int ts_conv3d_d_split_supported(int Cin, int Csplit) { return split_point_ok(Cin, Csplit); }
+
+extern "C" int ts_conv3d_d_split_fwd(const float* x, const float* x2, const float* w_t, const float* scale, const float* shift, float* y,
+                                     int B, int Cin, int Csplit, int Cout, int Din, int H, int W, int k, int stride, int dilation,
+                                     int padding, int transposed, int act, float act_param,
+                                     long long in_bstride, long long in_cstride, long long in2_bstride, long long in2_cstride,
+                                     long long out_bstride, long long out_cstride, void* stream) {
+  const SplitIn sp{x2, Csplit, in2_bstride, in2_cstride};
+  return conv_d_impl(x, w_t, scale, shift, y, B, Cin, Cout, Din, H, W, k, stride, dilation, padding, transposed, act,
+                     act_param, in_bstride, in_cstride, out_bstride, out_cstride, 0, stream, &sp);
 }
 
 // Gradient w.r.t. the input of ts_conv3d_d_fwd (raw convolution).  The geometry arguments describe the

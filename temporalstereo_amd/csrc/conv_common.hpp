@@ -65,7 +65,27 @@ struct IG {
   long long add_bstride;        // add_dstride != 0: one term per depth plane, [B][Cout][D][Ho*Wo] (ts_conv3d_hw_warp_fwd)
   long long add_cstride, add_dstride;
   int xcd;                      // XCD-banded workgroup order (ig_conv_kernel)
+  // split input (the *_split_fwd entries): channels [0, csplit) are read from x, channels [csplit, Cin) from x2, which has its own
+  // batch / channel strides and its own extent.  csplit is a multiple of every K-chunk size (32), so a chunk lies on one side of
+  // the seam and the choice of base is ONE uniform select per chunk.  No second base: x2 == x with x's strides and csplit = INT_MAX.
+  const float* x2;
+  int csplit;
+  long long in2_bstride, in2_cstride;
+  unsigned in2_bytes;
 };
+
+// The base of one K chunk of a (possibly split) input: descriptor, channel stride in bytes and the channel the base starts at --
+// all wave-uniform (chunk index and kernel arguments only), so they stay in scalar registers.
+struct ChunkBase {
+  __amdgpu_buffer_rsrc_t rsrc;
+  unsigned cstride_b;
+  int c_first;
+};
+__device__ __forceinline__ ChunkBase chunk_base(int c0, int csplit, __amdgpu_buffer_rsrc_t r1, __amdgpu_buffer_rsrc_t r2, unsigned cs1,
+                                                unsigned cs2) {
+  const bool second = c0 >= csplit;
+  return ChunkBase{second ? r2 : r1, second ? cs2 : cs1, second ? csplit : 0};
+}
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t ig_rsrc(const void* base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);

@@ -117,7 +117,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
     return t;
   };
   const unsigned HW = static_cast<unsigned>(p.H) * p.W;
-  const unsigned cstride_b = static_cast<unsigned>(p.in_cstride) * 4u;
+  const unsigned cstride_b = static_cast<unsigned>(p.in_cstride) * 4u, cstride2_b = static_cast<unsigned>(p.in2_cstride) * 4u;
 
   // ---- staging deal: thread -> (channel group, row, aligned quad) of the half's (HR + 2) x 40 input tile
   constexpr int SPC = G::SPC, NCH = G::NCH;
@@ -150,21 +150,24 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
   if (wgt) { wgt[0] = __builtin_amdgcn_s_memtime(); wgt[3] = __builtin_amdgcn_s_memrealtime(); }
 
   // the tile whose chunks are being FETCHED (one step ahead of the tile being multiplied)
-  __amdgpu_buffer_rsrc_t xr;
+  // (split input: the second base behind a descriptor of its own, sized to its own allocation; a halo offset is kOOB for both)
+  __amdgpu_buffer_rsrc_t xr, xr2;
   unsigned goff = kOOB;
   auto aim = [&](const XPTile& t) {
     xr = ig_rsrc(x + static_cast<long long>(t.b) * p.in_bstride, p.in_bytes);
+    xr2 = ig_rsrc(p.x2 + static_cast<long long>(t.b) * p.in2_bstride, p.in2_bytes);
     const int gy = t.ty0 - 1 + srow, gx = t.tx0 - 4 + 4 * squad;
     goff = (stager && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W)
         ? (static_cast<unsigned>(t.od) * HW + static_cast<unsigned>(gy) * p.W + gx) * 4u : kOOB;
   };
   v4f rin[NCH];
   auto fetch = [&](int c) {
+    const ChunkBase cbs = chunk_base(c * XP_NC, p.csplit, xr, xr2, cstride_b, cstride2_b);       // the chunk's side of a split input's seam
 #pragma unroll
     for (int e = 0; e < NCH; ++e) {
       // channels past Cin re-read the last real one; their weights are zero
-      const unsigned co = static_cast<unsigned>(min(c * XP_NC + sg * 8 + shalf * 4 + e, p.Cin - 1)) * cstride_b;
-      rin[e] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(xr, (goff == kOOB || (p.dbg & 1)) ? kOOB : goff + co, 0, 0));
+      const unsigned co = static_cast<unsigned>(min(c * XP_NC + sg * 8 + shalf * 4 + e, p.Cin - 1) - cbs.c_first) * cbs.cstride_b;
+      rin[e] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(cbs.rsrc, (goff == kOOB || (p.dbg & 1)) ? kOOB : goff + co, 0, 0));
     }
   };
   // weight DMA: instruction i (0..26) = (part, tap) = (i / 9, i % 9), its 64 lanes = (group, co); wave w of half 1 issues i = w, w + 4, ...

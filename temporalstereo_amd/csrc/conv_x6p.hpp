@@ -17,6 +17,10 @@ struct X6P {
   float* partial;               // [ksplit][B][Cout][D*H*W] raw sums when ksplit > 1
   unsigned part_bytes;          // extent of one (slice, batch) block of the partials
   int tiles_x, co_groups, tiles_pp, total_tiles;       // filled by x6p_launch (tiles per row / per plane / in all)
+  const float* x2;              // split input (conv_common.hpp, IG): channels [csplit, Cin) and their strides / extent
+  int csplit;
+  long long in2_bstride, in2_cstride;
+  unsigned in2_bytes;
   int dbg;                      // experiment switches (TS_X6P_DBG; 0 in production)
   unsigned long long* trace;    // experiment: cycle stamps of workgroup trace_wg (TS_X6P_TRACE), else null
   int trace_wg;

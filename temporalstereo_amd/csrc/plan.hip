@@ -101,6 +101,8 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_block_cost_sampled_warped_bwd),
     TS_PLAN_OP(ts_frames_prepare_fwd),      TS_PLAN_OP(ts_intrinsics_pyramid_fwd),  TS_PLAN_OP(ts_disp_u16_decode_fwd),
     TS_PLAN_OP(ts_frames_augment_fwd),      TS_PLAN_OP(ts_disp_u16_window_fwd),
+    TS_PLAN_OP(ts_block_cost_sampled_corr_split_fwd), TS_PLAN_OP(ts_conv3d_hw_split_fwd),
+    TS_PLAN_OP(ts_conv3d_d_split_fwd),      TS_PLAN_OP(ts_conv3d_hw_x6_split_fwd),
 };
 
 struct Call {

@@ -1472,10 +1472,50 @@ def block_cost_warped_ag(reference_fm, target_fm, disp_sample, block_cost_scale=
     return _BlockCostWarped.apply(reference_fm, target_fm, disp_sample, int(block_cost_scale))
 
 
+class Split:
+    """An input whose channels live in two allocations: `a` holds channels [0, Ca), `b` the rest.  block_cost_corr and the native
+    pipeline's conv_hw / conv_d read it in place through the ts_*_split_fwd entries (include/ts_hip.h) -- bit-identical to the
+    plain entry on torch.cat([a, b], 1).  shape / detach / contiguous / repeat: what a caller that only inspects or keeps its
+    arguments needs; contiguous() and repeat() MAKE the concatenation (a framework copy: diagnostics and measurements, never part
+    of a pass)."""
+    __slots__ = ("a", "b")
+
+    def __init__(self, a, b):
+        if a.shape[0] != b.shape[0] or a.shape[2:] != b.shape[2:]:
+            raise ValueError("Split: the two parts differ outside the channel axis: %r, %r" % (tuple(a.shape), tuple(b.shape)))
+        self.a, self.b = a, b
+
+    device = property(lambda self: self.a.device)
+    shape = property(lambda self: (self.a.shape[0], self.a.shape[1] + self.b.shape[1]) + tuple(self.a.shape[2:]))
+
+    def unsqueeze(self, dim):
+        return Split(self.a.unsqueeze(dim), self.b.unsqueeze(dim))
+
+    def detach(self):
+        return Split(self.a.detach(), self.b.detach())
+
+    def cat(self):
+        return torch.cat([self.a, self.b], 1)
+
+    def contiguous(self):
+        return self.cat()
+
+    def repeat(self, *sizes):
+        return self.cat().repeat(*sizes)
+
+
 def block_cost_corr(reference_fm, target_fm, disp_sample, block_cost_scale=3):
     """Inference form of the sampled block_cost WITHOUT its 2C main channels: the correlation blocks alone,
     [B, scales*C/8, D, H, W] = block_cost(...)[:, 2C:].  No autograd.  The consumer is ts_conv3d_hw_warp_fwd, which takes the
-    warped half of the volume in pre-contracted form (include/ts_hip.h)."""
+    warped half of the volume in pre-contracted form (include/ts_hip.h).
+    The two maps may be Splits at the same channel: the result is that of their concatenations, which are never made
+    (ts_block_cost_sampled_corr_split_fwd); dense planes, any batch stride."""
+    if isinstance(reference_fm, Split) or isinstance(target_fm, Split):
+        if not (isinstance(reference_fm, Split) and isinstance(target_fm, Split)) or reference_fm.a.shape[1] != target_fm.a.shape[1]:
+            raise ValueError("block_cost_corr: both maps split at the same channel, or neither")
+        _require_gpu(reference_fm.a, target_fm.a, disp_sample)
+        return _block_cost_corr_split(reference_fm.a, reference_fm.b, target_fm.a, target_fm.b, _lib.contiguous(disp_sample),
+                                      block_cost_scale)
     _require_gpu(reference_fm, target_fm, disp_sample)
     left, right, disp = _lib.contiguous(reference_fm), _lib.contiguous(target_fm), _lib.contiguous(disp_sample)
     B, C, H, W = left.shape
@@ -1491,6 +1531,27 @@ def block_cost_corr(reference_fm, target_fm, disp_sample, block_cost_scale=3):
                                                 _lib.ptr(ws), B, C, H, W, D, block_cost_scale, _stream())
     rc = launch() if _k1_probe is None else _k1_probe((B, C, H, W, D, "corr"), launch)
     _lib.check(rc, "ts_block_cost_sampled_corr_fwd")
+    return out
+
+
+def _block_cost_corr_split(left, left2, right, right2, disp, scales):
+    _require_gpu(left2, right2)
+    B, Cs, H, W = left.shape
+    C = Cs + left2.shape[1]
+    D = disp.shape[1]
+    for t, c in ((left, Cs), (right, Cs), (left2, C - Cs), (right2, C - Cs)):
+        if tuple(t.shape) != (B, c, H, W) or t.stride(3) != 1 or t.stride(2) != W or t.stride(1) != H * W:
+            raise ValueError("block_cost_corr: split maps need one geometry and dense planes, got %r strides %r" % (tuple(t.shape), t.stride()))
+    L = _lib.lib()
+    out = torch.empty((B, scales * (C // 8), D, H, W), device=left.device, dtype=torch.float32)
+    ws = torch.empty(max(_q("ts_block_cost_workspace_bytes", B, C, H, W, D, scales), 256), device=left.device, dtype=torch.uint8)
+
+    def launch():
+        return L.ts_block_cost_sampled_corr_split_fwd(_lib.ptr(left), _lib.ptr(left2), _lib.ptr(right), _lib.ptr(right2), _lib.ptr(disp),
+                                                      _lib.ptr(out), _lib.ptr(ws), B, C, Cs, H, W, D, scales, left.stride(0),
+                                                      left2.stride(0), right.stride(0), right2.stride(0), _stream())
+    rc = launch() if _k1_probe is None else _k1_probe((B, C, H, W, D, "corr"), launch)
+    _lib.check(rc, "ts_block_cost_sampled_corr_split_fwd")
     return out
 
 
