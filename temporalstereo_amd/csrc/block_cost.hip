@@ -5,22 +5,24 @@
 // group correlation :66-81).  Where the reference materialises the shifted/warped right volume
 // twice, pools it three times and concatenates, this is ONE streaming pass:
 //
-//   kernel A  (block_cost_main):  workgroup = (4 feature rows) x (one group of 8 channels) x all
-//       candidates.  The 8x4 right-feature rows are staged once into LDS in a 4-way
-//       de-interleaved layout (element x lives at [x&3][x>>2]) so that a wavefront whose lanes
-//       own 4 consecutive pixels each gathers conflict-free; each lane owns a 4x4 pixel block of
-//       one candidate, emits the main channels and the scale-0 group correlation with 16-byte
-//       coalesced stores, and reduces the 2x2 / 4x4 pooled differences of its own block in
-//       registers (no cross-lane traffic) into two tiny pooled maps.
-//   kernel B  (block_cost_upsample): bilinear (align_corners) expansion of the pooled maps into
-//       the scale-1/2 channel blocks, again 16 bytes per lane.
+//   the volume pass:  workgroup = (4 feature rows) x (one group of 8 channels) x all candidates.  It emits
+//       the main channels and the scale-0 group correlation with 16-byte coalesced stores and
+//       reduces the 2x2 / 4x4 pooled differences of every 4x4 pixel block (no cross-workgroup
+//       traffic) into two tiny pooled maps.  One of three kernels, chosen by shape (launch_fwd):
+//         block_cost_corr_rows  the correlation blocks alone on aligned maps of up to 512 columns (what
+//                               the pipeline launches): a lane per block ROW, candidates as a loop;
+//         block_cost_fast       rows that fit LDS and one (candidate, block) item per thread: both
+//                               maps staged, the right rows channel-packed for the gather;
+//         block_cost_main       everything else (rows too wide for LDS, or more than one pass of
+//                               items): both maps through L1/L2, a loop over items.
+//   block_cost_upsample_rows:  bilinear (align_corners) expansion of the pooled maps into the
+//       scale-1/2 channel blocks, again 16 bytes per lane.
 //
 // HBM-bound: algorithmic bytes = inputs once + output once; the only
 // extra traffic is the pooled maps (< 2 % of the output).  There is no inter-workgroup reuse, so
 // no XCD-aware block remap is needed here (cdna guide T1: 0 % on ops without shared panels).
-#include <cstdlib>
-
 #include "ts_common.hpp"
+#include "warp.hpp"
 
 namespace {
 
@@ -100,39 +102,33 @@ __device__ __forceinline__ void unpack(const float4 v, float (&a)[4]) { a[0] = v
 __device__ __forceinline__ float4 pack(const float (&a)[4]) { return make_float4(a[0], a[1], a[2], a[3]); }
 
 
-// Source taps of one output pixel: the two neighbouring right-feature columns (as LDS or row
-// offsets) and their weights (0 outside the row == zeros padding).
-template <bool SAMPLED, bool STAGE>
-__device__ __forceinline__ void tap(int x, int d, float dispv, int W, float Wm1, int Wqp,
-                                    int& o0, int& o1, float& w0, float& w1) {
-  int xi;
-  float f = 0.f;
+// Source column and fraction of one output pixel: a floor away from its tap position (ts::source_position, warp.hpp: computed
+// once per (candidate, pixel) where a kernel needs it more than once), or the integer shift d.
+template <bool SAMPLED>
+__device__ __forceinline__ void column_of(int x, int d, float pos, int& xi, float& f) {
   if constexpr (SAMPLED) {
-    // same float sequence as the reference: normalise to [-1,1] (inverse_warp_3d.py:41-47)
-    // and back (grid_sampler align_corners), so the tap position rounds identically
-    const float xs = static_cast<float>(x) + (-dispv);
-    const float gx = (xs / Wm1 * 2.f) - 1.f;
-    float ix = ((gx + 1.f) / 2.f) * Wm1;
-    ix = fminf(fmaxf(ix, -2.f), static_cast<float>(W) + 1.f);   // keeps int conversion defined
-    const float fl = floorf(ix);
-    f = ix - fl;
+    const float fl = floorf(pos);
+    f = pos - fl;
     xi = static_cast<int>(fl);
   } else {
     xi = x - d;
+    f = 0.f;
   }
+}
+
+// Source taps of one output pixel: the two neighbouring right-feature columns (as row offsets)
+// and their weights (0 outside the row == zeros padding).
+template <bool SAMPLED>
+__device__ __forceinline__ void tap(int x, int d, float dispv, int W, float Wm1, int& o0, int& o1, float& w0, float& w1) {
+  int xi;
+  float f;
+  column_of<SAMPLED>(x, d, ts::source_position(x, dispv, W, Wm1), xi, f);
   const bool v0 = (xi >= 0) & (xi < W);
   const bool v1 = (xi + 1 >= 0) & (xi + 1 < W);
   w0 = v0 ? (1.f - f) : 0.f;
   w1 = v1 ? f : 0.f;
-  const int i0 = min(max(xi, 0), W - 1);
-  const int i1 = min(max(xi + 1, 0), W - 1);
-  if constexpr (STAGE) {
-    o0 = (i0 & 3) * Wqp + (i0 >> 2);
-    o1 = (i1 & 3) * Wqp + (i1 >> 2);
-  } else {
-    o0 = i0;
-    o1 = i1;
-  }
+  o0 = min(max(xi, 0), W - 1);
+  o1 = min(max(xi + 1, 0), W - 1);
 }
 
 // cooperative copy of the 8x4 right-feature rows of this workgroup into LDS, de-interleaved
@@ -155,76 +151,32 @@ __device__ __forceinline__ void stage_right_rows(float* lds, const float* __rest
   __syncthreads();
 }
 
+// The fallback of the volume pass: rows too wide for LDS staging, or more than one pass of items per workgroup (many candidates).
+// Nothing is staged: both maps are read through L1/L2 (a right row is re-read by every candidate, a left row by every item of its
+// block column), and a thread loops over the (candidate, 4x4 block) items of its workgroup.  Per item it is block_cost_fast's
+// arithmetic: the main channels and the scale-0 correlation leave as 16-byte stores, the 2x2 / 4x4 pooled differences of the block
+// are reduced in registers.  No shipped geometry runs it.
 // SAMPLED: per-pixel fractional candidates (block_cost.py:47-58); else integer shift d (:34-45).
 // VEC:     W % 4 == 0 and 16-byte aligned bases -> float4 traffic.
-// STAGE:   the workgroup's feature rows live in LDS: all 8x4 right rows (de-interleaved for the
-//          gather) and the left rows two at a time (linear, read back with ds_read_b128; rows 2-3
-//          are fetched into registers during the prologue and swapped in at half time).  After the
-//          prologue the only vector-memory traffic of a wave is its store stream plus one
-//          prefetched candidate row, so a wave never waits on its own stores (vmcnt is in-order and
-//          counts stores on CDNA4).  ~47 KiB at W=240 -> three workgroups per CU, so the 544
-//          workgroups of the 136x240 level are co-resident in a single round.
-//          Rows too wide for that (or needing more than one pass of items) read both maps
-//          through L1/L2 instead.
-// NP:      left float4 values each thread carries across the first half (STAGE only).
-template <bool SAMPLED, bool VEC, bool STAGE, int NP>
+template <bool SAMPLED, bool VEC>
 __global__ void __launch_bounds__(512)
 block_cost_main(const float* __restrict__ L, const float* __restrict__ R,
                 const float* __restrict__ disp, float* __restrict__ out,
                 float* __restrict__ P1, float* __restrict__ P2, const Shape s) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
   const int by = blockIdx.x, g = blockIdx.y, b = blockIdx.z;
   const int y0 = by * TR;
-  const int H = s.H, W = s.W, D = s.D, C = s.C;
+  const int H = s.H, W = s.W, D = s.D;
   const size_t HW = static_cast<size_t>(H) * W;
   const float* Lg = group_base(L, s.L2, s.lbs, s.lbs2, s.csplit, b, g, HW);
   const float* Rg = group_base(R, s.R2, s.rbs, s.rbs2, s.csplit, b, g, HW);
-  const int Wl = 4 * s.Wq;                                    // LDS row length of the left rows
-  float* ldsL = lds + static_cast<size_t>(GRP) * TR * 4 * s.Wqp;   // [c][r & 1][Wl]
-
-  float4 lpre[NP];   // left rows 2,3 in flight across the first half
-  if constexpr (STAGE) {
-    const int n = GRP * TR * s.Wq;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const int j = i % s.Wq, cr = i / s.Wq;
-      const int r = cr & (TR - 1), c = cr >> 2;
-      const int y = y0 + r;
-      float4 rv = make_float4(0.f, 0.f, 0.f, 0.f), lv = rv;
-      if (y < H) {
-        const size_t off = static_cast<size_t>(c) * HW + static_cast<size_t>(y) * W;
-        rv = ld4<VEC>(Rg + off, 4 * j, W);
-        if (r < 2) lv = ld4<VEC>(Lg + off, 4 * j, W);
-      }
-      float* dst = lds + static_cast<size_t>(cr) * 4 * s.Wqp + j;
-      dst[0] = rv.x;
-      dst[s.Wqp] = rv.y;
-      dst[2 * s.Wqp] = rv.z;
-      dst[3 * s.Wqp] = rv.w;
-      if (r < 2) *reinterpret_cast<float4*>(ldsL + static_cast<size_t>(c * 2 + r) * Wl + 4 * j) = lv;
-    }
-    const int n2 = GRP * 2 * s.Wq;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int i = threadIdx.x + p * blockDim.x;
-      lpre[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (i < n2) {
-        const int j = i % s.Wq, cr = i / s.Wq;          // cr = c*2 + (r-2)
-        const int y = y0 + 2 + (cr & 1);
-        if (y < H) lpre[p] = ld4<VEC>(Lg + static_cast<size_t>(cr >> 1) * HW + static_cast<size_t>(y) * W, 4 * j, W);
-      }
-    }
-    __syncthreads();
-  }
 
   const float Wm1 = static_cast<float>(W - 1);
   const int nitems = s.nbxp * D;
-  // STAGE runs exactly one item per thread (the host guarantees nitems <= blockDim) so that the
-  // half-time barrier is uniform; the fallback loops.
-  for (int item = threadIdx.x; item < (STAGE ? blockDim.x : nitems); item += blockDim.x) {
+  for (int item = threadIdx.x; item < static_cast<unsigned>(nitems); item += blockDim.x) {   // compared in blockDim.x's type
     const int d = item / s.nbxp;
     const int bx = item - d * s.nbxp;
     const bool live = (item < nitems) && (bx < s.nbx);
-    if (!STAGE && !live) continue;
+    if (!live) continue;
     const int x4 = bx * 4;
     float* plane0 = out + (static_cast<size_t>(b) * s.Ctot * D + (live ? d : 0)) * HW;  // channel 0, candidate d
     const size_t cstride = static_cast<size_t>(D) * HW;                                 // one channel
@@ -244,21 +196,6 @@ block_cost_main(const float* __restrict__ L, const float* __restrict__ R,
 #pragma unroll 1
     for (int r = 0; r < TR; ++r) {
       const int y = y0 + r;
-      if constexpr (STAGE) {
-        if (r == 2) {   // swap left rows 2,3 into the LDS slots of rows 0,1
-          __syncthreads();
-          const int n2 = GRP * 2 * s.Wq;
-#pragma unroll
-          for (int p = 0; p < NP; ++p) {
-            const int i = threadIdx.x + p * blockDim.x;
-            if (i < n2) {
-              const int j = i % s.Wq, cr = i / s.Wq;
-              *reinterpret_cast<float4*>(ldsL + static_cast<size_t>(cr) * Wl + 4 * j) = lpre[p];
-            }
-          }
-          __syncthreads();
-        }
-      }
       if (y < H && live) {
         float dv[4];
         unpack(dnext, dv);
@@ -269,20 +206,13 @@ block_cost_main(const float* __restrict__ L, const float* __restrict__ R,
         float w0[4], w1[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          tap<SAMPLED, STAGE>(x4 + k, d, dv[k], W, Wm1, s.Wqp, o0[k], o1[k], w0[k], w1[k]);
+          tap<SAMPLED>(x4 + k, d, dv[k], W, Wm1, o0[k], o1[k], w0[k], w1[k]);
         float g0[4] = {0.f, 0.f, 0.f, 0.f};
         const size_t rowoff = static_cast<size_t>(y) * W;
 #pragma unroll
         for (int c = 0; c < GRP; ++c) {
-          float4 lv4;
-          const float* src;
-          if constexpr (STAGE) {
-            lv4 = *reinterpret_cast<const float4*>(ldsL + static_cast<size_t>(c * 2 + (r & 1)) * Wl + x4);
-            src = lds + static_cast<size_t>(c * TR + r) * 4 * s.Wqp;
-          } else {
-            lv4 = ld4<VEC>(Lg + c * HW + rowoff, x4, W);
-            src = Rg + c * HW + rowoff;
-          }
+          const float4 lv4 = ld4<VEC>(Lg + c * HW + rowoff, x4, W);
+          const float* src = Rg + c * HW + rowoff;
           float lv[4], tv[4], ev[4];
           unpack(lv4, lv);
 #pragma unroll
@@ -403,20 +333,7 @@ template <bool SAMPLED>
 __device__ __forceinline__ void tap4(int x, int d, float dispv, int W, float Wm1, int Wq, int Wqp,
                                      unsigned& packed, float& f) {
   int xi;
-  f = 0.f;
-  if constexpr (SAMPLED) {
-    // same float sequence as the reference: normalise to [-1,1] (inverse_warp_3d.py:41-47)
-    // and back (grid_sampler align_corners), so the tap position rounds identically
-    const float xs = static_cast<float>(x) + (-dispv);
-    const float gx = (xs / Wm1 * 2.f) - 1.f;
-    float ix = ((gx + 1.f) / 2.f) * Wm1;
-    ix = fminf(fmaxf(ix, -2.f), static_cast<float>(W) + 1.f);   // keeps int conversion defined
-    const float fl = floorf(ix);
-    f = ix - fl;
-    xi = static_cast<int>(fl);
-  } else {
-    xi = x - d;
-  }
+  column_of<SAMPLED>(x, d, ts::source_position(x, dispv, W, Wm1), xi, f);
   const unsigned a0 = (xi >= 0 && xi < W) ? static_cast<unsigned>((xi & 3) * Wqp + (xi >> 2)) : static_cast<unsigned>(Wq);
   const int xj = xi + 1;
   const unsigned a1 = (xj >= 0 && xj < W) ? static_cast<unsigned>((xj & 3) * Wqp + (xj >> 2)) : static_cast<unsigned>(Wq);
@@ -788,82 +705,6 @@ block_cost_corr_rows(const float* __restrict__ L, const float* __restrict__ R, c
   }
 }
 
-// trilinear(align_corners=True) expansion of the pooled maps (block_cost.py:74); the D axis maps
-// to itself, so it is a per-candidate bilinear interpolation, done separably: a workgroup owns a
-// band of RB output rows of one (b, g, d) plane, first interpolates the few pooled rows the band
-// touches along W into LDS (coalesced reads of the tiny pooled maps), then blends pairs of those
-// rows along H with ds_read_b128 and streams 16-byte stores.
-template <bool VEC, int RB>
-__global__ void __launch_bounds__(256)
-block_cost_upsample(const float* __restrict__ P1, const float* __restrict__ P2,
-                    float* __restrict__ out, const Shape s) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int NR1 = RB / 2 + 2, NR2 = RB / 4 + 2;     // pooled rows a band can touch per level
-  const int Wl = 4 * s.nbx;
-  const int band = blockIdx.x, plane = blockIdx.y + blockIdx.z * gridDim.y;
-  if (plane >= s.B * s.G * s.D) return;
-  const int d = plane % s.D;
-  const int bg = plane / s.D;
-  const int g = bg % s.G, b = bg / s.G;
-  const int yfirst = band * RB;
-  const int ylast = min(yfirst + RB, s.H) - 1;
-  const size_t HW = static_cast<size_t>(s.H) * s.W;
-
-  int lo[3];
-#pragma unroll
-  for (int lvl = 1; lvl <= 2; ++lvl) {
-    if (lvl >= s.scales) break;
-    const float* P = (lvl == 1) ? P1 : P2;
-    const int Hs = (lvl == 1) ? s.H1 : s.H2, Ws = (lvl == 1) ? s.W1 : s.W2;
-    const float rh = (lvl == 1) ? s.rh1 : s.rh2, rw = (lvl == 1) ? s.rw1 : s.rw2;
-    const int nr = (lvl == 1) ? NR1 : NR2;
-    float* buf = lds + (lvl == 1 ? 0 : NR1 * Wl);
-    lo[lvl] = static_cast<int>(rh * static_cast<float>(yfirst));
-    const int hi = min(static_cast<int>(rh * static_cast<float>(ylast)) + 1, Hs - 1);
-    const float* Pp = P + static_cast<size_t>(plane) * Hs * Ws;
-    for (int i = threadIdx.x; i < nr * Wl; i += blockDim.x) {
-      const int rr = i / Wl, x = i - rr * Wl;
-      const int srow = lo[lvl] + rr;
-      float v = 0.f;
-      if (srow <= hi && x < s.W) {
-        const float wr = rw * static_cast<float>(x);
-        const int w1 = static_cast<int>(wr);
-        const int wp = (w1 < Ws - 1) ? 1 : 0;
-        const float wl = wr - static_cast<float>(w1);
-        const float* row = Pp + static_cast<size_t>(srow) * Ws;
-        v = (1.f - wl) * row[w1] + wl * row[w1 + wp];
-      }
-      buf[i] = v;
-    }
-  }
-  __syncthreads();
-
-  const int nrows = ylast - yfirst + 1;
-  for (int item = threadIdx.x; item < nrows * s.nbx; item += blockDim.x) {
-    const int r = item / s.nbx;
-    const int x4 = (item - r * s.nbx) * 4;
-    const int y = yfirst + r;
-#pragma unroll
-    for (int lvl = 1; lvl <= 2; ++lvl) {
-      if (lvl >= s.scales) break;
-      const int Hs = (lvl == 1) ? s.H1 : s.H2;
-      const float rh = (lvl == 1) ? s.rh1 : s.rh2;
-      const float* buf = lds + (lvl == 1 ? 0 : NR1 * Wl);
-      const float hr = rh * static_cast<float>(y);
-      const int h1 = static_cast<int>(hr);
-      const int hp = (h1 < Hs - 1) ? 1 : 0;
-      const float hl = hr - static_cast<float>(h1);
-      const float4 a = *reinterpret_cast<const float4*>(buf + (h1 - lo[lvl]) * Wl + x4);
-      const float4 c = *reinterpret_cast<const float4*>(buf + (h1 + hp - lo[lvl]) * Wl + x4);
-      const float4 v = make_float4((1.f - hl) * a.x + hl * c.x, (1.f - hl) * a.y + hl * c.y,
-                                   (1.f - hl) * a.z + hl * c.z, (1.f - hl) * a.w + hl * c.w);
-      float* pl = out + ((static_cast<size_t>(b) * s.Ctot + s.mainC + lvl * s.G + g) * s.D + d) * HW +
-                  static_cast<size_t>(y) * s.W;
-      st4<VEC>(pl, x4, s.W, v);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Dense siblings of block_cost: cat_fms / dif_fms over ANY number of candidates
 // (the literal shift-and-correlate over D = 48..192).  Same staging as the fast path -- TRD right rows of an
@@ -1033,93 +874,21 @@ dense_warp_kernel(const float* __restrict__ L, const float* __restrict__ R, cons
   }
 }
 
-// Direct form of the same expansion: one lane per float4 of output of BOTH levels, no LDS, no barrier.
-// The pooled maps are tiny (a plane of level 1 is H/2 x W/2) and live in L2, four output pixels touch at
-// most 4 (level 1) / 3 (level 2) pooled cells per row, so a lane issues 14 independent clamped loads up
-// front and two 16-byte stores: a single memory round trip instead of load -> LDS -> barrier -> blend.
+// trilinear(align_corners=True) expansion of the pooled maps (block_cost.py:74) into the scale-1/2 channel blocks; the D axis maps
+// to itself, so it is a per-candidate bilinear interpolation.  No LDS, no barrier: one lane per float4 column of UP_RB output rows
+// of one (b, g, d) plane, both levels.  The pooled rows such a run touches (at most UP_RB/2+2 of level 1, UP_RB/4+2 of level 2) are
+// fetched ONCE and interpolated along W once per pooled row; per output row what is left is the choice of its two pooled rows
+// (compare-selects: no dynamic register indexing) and the H-lerp: along W first, then along H.
+// UP_RB = 4, measured at the 1/4 level: 2 rows per lane 9.9 us, 4 rows 7.6 us, 8 rows 8.9 us (too few lanes).
+// Planes are folded over grid y and z (launch_fwd), so the plane count is not bounded by a grid dimension.
+constexpr int UP_RB = 4;
+
 template <bool VEC>
 __global__ void __launch_bounds__(256)
-block_cost_upsample_direct(const float* __restrict__ P1, const float* __restrict__ P2,
-                           float* __restrict__ out, const Shape s) {
-  constexpr int RPT = 2;                      // output rows per lane: halves the wave count (one resident round at config-2 sizes)
-  const int plane = blockIdx.y;
-  const int d = plane % s.D;
-  const int bg = plane / s.D;
-  const int g = bg % s.G, b = bg / s.G;
-  const size_t HW = static_cast<size_t>(s.H) * s.W;
-  const int item = blockIdx.x * blockDim.x + threadIdx.x;
-  const int rows = (s.H + RPT - 1) / RPT;
-  if (item >= rows * s.nbx) return;
-  const int yb = (item / s.nbx) * RPT;
-  const int x4 = (item - (item / s.nbx) * s.nbx) * 4;
-  float cell[RPT][3][2][4];                   // [row][level][pooled row][cell]
-  int c0[3], hpv[RPT][3];
-  float hlv[RPT][3];
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int y = min(yb + q, s.H - 1);
-#pragma unroll
-    for (int lvl = 1; lvl <= 2; ++lvl) {
-      const bool on = lvl < s.scales;
-      const float* P = (lvl == 1) ? P1 : P2;
-      const int Hs = (lvl == 1) ? s.H1 : s.H2, Ws = (lvl == 1) ? s.W1 : s.W2;
-      const float rh = (lvl == 1) ? s.rh1 : s.rh2, rw = (lvl == 1) ? s.rw1 : s.rw2;
-      const float hr = rh * static_cast<float>(y);
-      const int h1 = min(static_cast<int>(hr), Hs - 1);
-      hpv[q][lvl] = (h1 < Hs - 1) ? 1 : 0;
-      hlv[q][lvl] = hr - static_cast<float>(h1);
-      c0[lvl] = min(static_cast<int>(rw * static_cast<float>(x4)), Ws - 1);
-      const float* Pp = (on ? P : P1) + static_cast<size_t>(on ? plane : 0) * Hs * Ws;
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          cell[q][lvl][r][c] = Pp[static_cast<size_t>(h1 + (r ? hpv[q][lvl] : 0)) * Ws + min(c0[lvl] + c, Ws - 1)];
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < RPT; ++q) {
-    const int y = yb + q;
-    if (y >= s.H) break;
-#pragma unroll
-    for (int lvl = 1; lvl <= 2; ++lvl) {
-      if (lvl >= s.scales) break;
-      const int Ws = (lvl == 1) ? s.W1 : s.W2;
-      const float rw = (lvl == 1) ? s.rw1 : s.rw2;
-      float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float wr = rw * static_cast<float>(min(x4 + k, s.W - 1));
-        const int w1 = static_cast<int>(wr);
-        const int wp = (w1 < Ws - 1) ? 1 : 0;
-        const float wl = wr - static_cast<float>(w1);
-        const int i0 = w1 - c0[lvl], i1 = i0 + wp;        // 0..3 (pooled width is at most half the output's)
-        float a0 = cell[q][lvl][0][0], a1 = a0, b0 = cell[q][lvl][1][0], b1 = b0;
-#pragma unroll
-        for (int c = 1; c < 4; ++c) {
-          a0 = (i0 == c) ? cell[q][lvl][0][c] : a0; a1 = (i1 == c) ? cell[q][lvl][0][c] : a1;
-          b0 = (i0 == c) ? cell[q][lvl][1][c] : b0; b1 = (i1 == c) ? cell[q][lvl][1][c] : b1;
-        }
-        const float top = (1.f - wl) * a0 + wl * a1;      // along W first, then along H (the staged kernel's order)
-        const float bot = (1.f - wl) * b0 + wl * b1;
-        v[k] = (1.f - hlv[q][lvl]) * top + hlv[q][lvl] * bot;
-      }
-      float* pl = out + ((static_cast<size_t>(b) * s.Ctot + s.mainC + lvl * s.G + g) * s.D + d) * HW +
-                  static_cast<size_t>(y) * s.W;
-      st4<VEC>(pl, x4, s.W, make_float4(v[0], v[1], v[2], v[3]));
-    }
-  }
-}
-
-// The same expansion with RB output rows per lane: the pooled rows a run of RB output rows touches (at most RB/2+2 of
-// level 1, RB/4+2 of level 2) are fetched ONCE and interpolated along W once per pooled row instead of twice per output row
-// (an eighth of the loads and of the W-lerps per stored float4 at RB = 8); per output row what is left is the choice of its two
-// pooled rows (compare-selects: no dynamic register indexing) and the H-lerp.  Same arithmetic order, bit-identical values.
-template <bool VEC, int RB>
-__global__ void __launch_bounds__(256)
 block_cost_upsample_rows(const float* __restrict__ P1, const float* __restrict__ P2, float* __restrict__ out, const Shape s) {
-  constexpr int NR1 = RB / 2 + 2, NR2 = RB / 4 + 2;
-  const int plane = blockIdx.y;
+  constexpr int RB = UP_RB, NR1 = RB / 2 + 2, NR2 = RB / 4 + 2;
+  const int plane = blockIdx.y + blockIdx.z * gridDim.y;
+  if (plane >= s.B * s.G * s.D) return;
   const int d = plane % s.D;
   const int bg = plane / s.D;
   const int g = bg % s.G, b = bg / s.G;
@@ -1288,7 +1057,7 @@ int launch_fwd(const float* left, const float* right, const float* disp, float* 
   hipStream_t st = ts::as_stream(stream);
 
   // correlation blocks alone on aligned maps: one lane per block row, candidates as a loop (block_cost_corr_rows)
-  static const bool corr_rows = [] { const char* e = getenv("TS_K1_CORR_ROWS"); return !e || atoi(e) != 0; }();
+  static const bool corr_rows = ts::env_not_zero("TS_K1_CORR_ROWS");
   bool done = false;
   if (SAMPLED && omit_ref == 2 && vec && corr_rows && static_cast<unsigned long long>(s.Ctot) * D * H * W * 4ull < 0xffffff00ull) {
     const int cthreads = static_cast<int>(ts::round_up(static_cast<size_t>(s.nbx) * 4, ts::kWave));
@@ -1304,8 +1073,6 @@ int launch_fwd(const float* left, const float* right, const float* disp, float* 
       done = true;
     }
   }
-  if (done) {
-  } else
 #define TS_LAUNCH_FAST(V, N)                                                                        \
   do {                                                                                               \
     if (SAMPLED && omit_ref == 2)                                                                    \
@@ -1318,56 +1085,25 @@ int launch_fwd(const float* left, const float* right, const float* disp, float* 
       hipLaunchKernelGGL((block_cost_fast<SAMPLED, V, N, true>), grid, dim3(threads), lds_bytes, st, \
                          left, right, disp, out, P1, P2, s);                                         \
   } while (0)
-#define TS_LAUNCH_WIDE(V)                                                                        \
-  hipLaunchKernelGGL((block_cost_main<SAMPLED, V, false, 1>), grid, dim3(threads), 0, st,        \
-                     left, right, disp, out, P1, P2, s)
-  if (stage) {
+  if (done) {   // block_cost_corr_rows has it
+  } else if (stage) {
     if (vec) { if (np <= 2) TS_LAUNCH_FAST(true, 2); else if (np == 3) TS_LAUNCH_FAST(true, 3); else if (np == 4) TS_LAUNCH_FAST(true, 4); else TS_LAUNCH_FAST(true, 8); }
     else { if (np <= 2) TS_LAUNCH_FAST(false, 2); else if (np <= 4) TS_LAUNCH_FAST(false, 4); else TS_LAUNCH_FAST(false, 8); }
   } else {
-    if (vec) TS_LAUNCH_WIDE(true);
-    else TS_LAUNCH_WIDE(false);
+    ts::dispatch_bool(vec, [&](auto V) {
+      hipLaunchKernelGGL((block_cost_main<SAMPLED, V()>), grid, dim3(threads), 0, st, left, right, disp, out, P1, P2, s);
+    });
   }
 #undef TS_LAUNCH_FAST
-#undef TS_LAUNCH_WIDE
   if (int rc = ts::launched("block_cost_main")) return rc;
 
-  // output rows per lane of the expansion: 4 (measured at the 1/4 level: 2 rows 9.9 us, 4 rows 7.6 us, 8 rows 8.9 us -- too few
-  // lanes); TS_K1_UPSAMPLE_ROWS=2|8 for the A/B
-  static const int up_rows = [] { const char* e = getenv("TS_K1_UPSAMPLE_ROWS"); return e ? atoi(e) : 4; }();
-  if (scales > 1 && static_cast<long long>(B) * s.G * D <= 65535 && (up_rows == 4 || up_rows == 8)) {
-    const int rb = up_rows;
-    const dim3 dgrid((((H + rb - 1) / rb) * s.nbx + 255) / 256, B * s.G * D);
-    if (rb == 8) {
-      if (vec) hipLaunchKernelGGL((block_cost_upsample_rows<true, 8>), dgrid, dim3(256), 0, st, P1, P2, out, s);
-      else hipLaunchKernelGGL((block_cost_upsample_rows<false, 8>), dgrid, dim3(256), 0, st, P1, P2, out, s);
-    } else {
-      if (vec) hipLaunchKernelGGL((block_cost_upsample_rows<true, 4>), dgrid, dim3(256), 0, st, P1, P2, out, s);
-      else hipLaunchKernelGGL((block_cost_upsample_rows<false, 4>), dgrid, dim3(256), 0, st, P1, P2, out, s);
-    }
-    if (int rc = ts::launched("block_cost_upsample_rows")) return rc;
-  } else if (scales > 1 && static_cast<long long>(B) * s.G * D <= 65535) {
-    const dim3 dgrid((((H + 1) / 2) * s.nbx + 255) / 256, B * s.G * D);
-    if (vec) hipLaunchKernelGGL(block_cost_upsample_direct<true>, dgrid, dim3(256), 0, st, P1, P2, out, s);
-    else hipLaunchKernelGGL(block_cost_upsample_direct<false>, dgrid, dim3(256), 0, st, P1, P2, out, s);
-    if (int rc = ts::launched("block_cost_upsample_direct")) return rc;
-  } else if (scales > 1) {
+  if (scales > 1) {
+    // a plane per (y, z) of the grid: y alone ends at 65,535 planes
     const int nplanes = B * s.G * D;
     const int gy = nplanes < 32768 ? nplanes : 32768;
-    const int gz = (nplanes + gy - 1) / gy;
-    const int Wl = 4 * s.nbx;
-    // largest row band whose separable intermediate fits 64 KiB of LDS
-    int rb = 16;
-    while (rb > 4 && static_cast<size_t>(rb / 2 + 2 + rb / 4 + 2) * Wl * sizeof(float) > 64 * 1024) rb /= 2;
-    const size_t ulds = static_cast<size_t>(rb / 2 + 2 + rb / 4 + 2) * Wl * sizeof(float);
-    TS_REQUIRE(ulds <= 64 * 1024, TS_ERR_UNSUPPORTED, "block_cost: W=%d too wide for the upsample stage", W);
-    const dim3 ugrid((H + rb - 1) / rb, gy, gz);
-#define TS_LAUNCH_UP(V, RBV) \
-  hipLaunchKernelGGL((block_cost_upsample<V, RBV>), ugrid, dim3(256), ulds, st, P1, P2, out, s)
-    if (vec) { if (rb == 16) TS_LAUNCH_UP(true, 16); else if (rb == 8) TS_LAUNCH_UP(true, 8); else TS_LAUNCH_UP(true, 4); }
-    else { if (rb == 16) TS_LAUNCH_UP(false, 16); else if (rb == 8) TS_LAUNCH_UP(false, 8); else TS_LAUNCH_UP(false, 4); }
-#undef TS_LAUNCH_UP
-    if (int rc = ts::launched("block_cost_upsample")) return rc;
+    const dim3 dgrid((((H + UP_RB - 1) / UP_RB) * s.nbx + 255) / 256, gy, (nplanes + gy - 1) / gy);
+    ts::dispatch_bool(vec, [&](auto V) { hipLaunchKernelGGL(block_cost_upsample_rows<V()>, dgrid, dim3(256), 0, st, P1, P2, out, s); });
+    if (int rc = ts::launched("block_cost_upsample_rows")) return rc;
   }
   return TS_OK;
 }
@@ -1433,44 +1169,6 @@ block_cost_upsample_adjoint(const float* __restrict__ dout, float* __restrict__ 
   }
 }
 
-// source column (clamped to [-2, W+1]) and fraction of one output pixel
-template <bool SAMPLED>
-__device__ __forceinline__ void source_column(int x, int d, float dispv, int W, float Wm1, int& xi, float& f) {
-  if constexpr (SAMPLED) {
-    const float xs = static_cast<float>(x) + (-dispv);
-    const float gx = (xs / Wm1 * 2.f) - 1.f;
-    float ix = ((gx + 1.f) / 2.f) * Wm1;
-    ix = fminf(fmaxf(ix, -2.f), static_cast<float>(W) + 1.f);
-    const float fl = floorf(ix);
-    f = ix - fl;
-    xi = static_cast<int>(fl);
-  } else {
-    xi = x - d;
-    f = 0.f;
-  }
-}
-
-// The same in two steps (round 5): the source POSITION of a pixel (the reference's normalise / un-normalise float sequence with its
-// one true division) depends on (candidate, pixel) only -- block_cost_bwd_tile computes it once per item instead of twice per channel
-// (32 divisions per thread and channel) and keeps it where it kept the candidate's disparity; column and fraction are a floor away.
-__device__ __forceinline__ float source_position(int x, float dispv, int W, float Wm1) {
-  const float xs = static_cast<float>(x) + (-dispv);
-  const float gx = (xs / Wm1 * 2.f) - 1.f;
-  const float ix = ((gx + 1.f) / 2.f) * Wm1;
-  return fminf(fmaxf(ix, -2.f), static_cast<float>(W) + 1.f);
-}
-template <bool SAMPLED>
-__device__ __forceinline__ void column_of(int x, int d, float pos, int& xi, float& f) {
-  if constexpr (SAMPLED) {
-    const float fl = floorf(pos);
-    f = pos - fl;
-    xi = static_cast<int>(fl);
-  } else {
-    xi = x - d;
-    f = 0.f;
-  }
-}
-
 template <bool SAMPLED, bool VEC, bool STAGE>
 __global__ void __launch_bounds__(256)
 block_cost_bwd_main(const float* __restrict__ L, const float* __restrict__ R, const float* __restrict__ disp,
@@ -1509,7 +1207,7 @@ block_cost_bwd_main(const float* __restrict__ L, const float* __restrict__ R, co
       unpack(ld4<VEC>(dplane0 + static_cast<size_t>(s.mainC + g) * cstride + static_cast<size_t>(y) * W, x4, W), dg0[r]);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        source_column<SAMPLED>(x4 + k, d, dv[k], W, Wm1, xi[r][k], fr[r][k]);
+        column_of<SAMPLED>(x4 + k, d, ts::source_position(x4 + k, dv[k], W, Wm1), xi[r][k], fr[r][k]);
         gdacc[r][k] = 0.f;
       }
     }
@@ -1655,7 +1353,7 @@ block_cost_bwd_tile(const float* __restrict__ L, const float* __restrict__ R, co
   const size_t cstride = static_cast<size_t>(D) * HW;
   const size_t pbase = ((static_cast<size_t>(b) * s.G + g) * D + d);
 
-  float dvs[TR][4], gdacc[TR][4];       // the items' tap positions (source_position), column / fraction re-derived per use (registers)
+  float dvs[TR][4], gdacc[TR][4];       // the items' tap positions (ts::source_position), column / fraction re-derived per use (registers)
   float dp1[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
   float dp2 = 0.f;
 #pragma unroll
@@ -1666,7 +1364,7 @@ block_cost_bwd_tile(const float* __restrict__ L, const float* __restrict__ R, co
       unpack(ld4<VEC>(disp + (static_cast<size_t>(b) * D + d) * HW + static_cast<size_t>(y) * W, x4, W), dv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      dvs[r][k] = SAMPLED ? source_position(x4 + k, dv[k], W, Wm1) : 0.f;        // the tap POSITION from here on
+      dvs[r][k] = SAMPLED ? ts::source_position(x4 + k, dv[k], W, Wm1) : 0.f;        // the tap POSITION from here on
       gdacc[r][k] = 0.f;
     }
   }
@@ -1891,7 +1589,7 @@ block_cost_bwd_rows(const float* __restrict__ L, const float* __restrict__ R, co
     int o0[4], o1[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      column_of<true>(x4 + k, d, source_position(x4 + k, dv[k], W, Wm1), a[k], f[k]);
+      column_of<true>(x4 + k, d, ts::source_position(x4 + k, dv[k], W, Wm1), a[k], f[k]);
       const int i0 = min(max(a[k], 0), W - 1), i1 = min(max(a[k] + 1, 0), W - 1);
       o0[k] = (i0 & 3) * s.Wqp + (i0 >> 2);
       o1[k] = (i1 & 3) * s.Wqp + (i1 >> 2);
@@ -2066,7 +1764,7 @@ int launch_bwd(const float* left, const float* right, const float* disp, const f
     const long long total = static_cast<long long>(B) * s.G * D * (static_cast<long long>(s.H1) * s.W1 + (scales > 2 ? s.H2 * s.W2 : 0));
     long long blocks = (total + 255) / 256;
     if (blocks > ts::kNumCU * 16) blocks = ts::kNumCU * 16;
-    static const bool adj_rows = [] { const char* e = getenv("TS_K1_ADJOINT_ROWS"); return !e || atoi(e) != 0; }();
+    static const bool adj_rows = ts::env_not_zero("TS_K1_ADJOINT_ROWS");
     const long long planes = static_cast<long long>(B) * s.G * D;
     const int bands = scales > 2 ? (s.H2 + ADJ_R2 - 1) / ADJ_R2 : (s.H1 + 2 * ADJ_R2 - 1) / (2 * ADJ_R2);
     const size_t alds = (static_cast<size_t>(2) * ADJ_R2 * s.W1 + ADJ_R2 * s.W2) * sizeof(double);
@@ -2092,7 +1790,7 @@ int launch_bwd(const float* left, const float* right, const float* disp, const f
   if (threads > 256) threads = 256;
   const dim3 grid(s.nby, s.G, B);
   {   // sampled path on aligned maps of up to 256 columns: one lane per block row, candidates outside (block_cost_bwd_rows)
-    static const bool rows = [] { const char* e = getenv("TS_K1_BWD_ROWS"); return !e || atoi(e) != 0; }();
+    static const bool rows = ts::env_not_zero("TS_K1_BWD_ROWS");
     const int rthreads = static_cast<int>(ts::round_up(static_cast<size_t>(s.nbx) * 4, ts::kWave));
     const size_t rlds = (static_cast<size_t>(GRP) * TR * 4 * s.Wqp + static_cast<size_t>(GRP) * TR * 4 * s.Wq) * sizeof(float);   // R rows + [GRP/2][TR][Wl] doubles
     if (SAMPLED && rows && vec && rthreads <= 512 && rlds <= 80 * 1024 && (!grad_left || ts::aligned16(grad_left)) &&
@@ -2112,21 +1810,18 @@ int launch_bwd(const float* left, const float* right, const float* disp, const f
     }
   }
   if (tile) {
-    const int tthreads = tile_threads;
-    if (vec) hipLaunchKernelGGL((block_cost_bwd_tile<SAMPLED, true>), grid, dim3(tthreads), tile_lds, st, left, right, disp,
-                                grad_out, dP1, dP2, grad_left, grad_right, grad_disp, s);
-    else hipLaunchKernelGGL((block_cost_bwd_tile<SAMPLED, false>), grid, dim3(tthreads), tile_lds, st, left, right, disp,
-                            grad_out, dP1, dP2, grad_left, grad_right, grad_disp, s);
+    ts::dispatch_bool(vec, [&](auto V) {
+      hipLaunchKernelGGL((block_cost_bwd_tile<SAMPLED, V()>), grid, dim3(tile_threads), tile_lds, st, left, right, disp,
+                         grad_out, dP1, dP2, grad_left, grad_right, grad_disp, s);
+    });
     return ts::launched("block_cost_bwd_tile");
   }
-#define TS_LAUNCH_BWD(V, S)                                                                          \
-  hipLaunchKernelGGL((block_cost_bwd_main<SAMPLED, V, S>), grid, dim3(threads), (S) ? lds_bytes : 0, st, \
-                     left, right, disp, grad_out, dP1, dP2, grad_left, grad_right, grad_disp, s)
-  if (vec && stage) TS_LAUNCH_BWD(true, true);
-  else if (vec) TS_LAUNCH_BWD(true, false);
-  else if (stage) TS_LAUNCH_BWD(false, true);
-  else TS_LAUNCH_BWD(false, false);
-#undef TS_LAUNCH_BWD
+  ts::dispatch_bool(vec, [&](auto V) {
+    ts::dispatch_bool(stage, [&](auto S) {
+      hipLaunchKernelGGL((block_cost_bwd_main<SAMPLED, V(), S()>), grid, dim3(threads), S() ? lds_bytes : 0, st,
+                         left, right, disp, grad_out, dP1, dP2, grad_left, grad_right, grad_disp, s);
+    });
+  });
   return ts::launched("block_cost_bwd_main");
 }
 
@@ -2205,8 +1900,9 @@ int launch_dense(const float* left, const float* right, const float* disp, float
              "cat/dif_fms: one batch element of the volume spans 4 GiB or more");
   const dim3 grid((H + TRD - 1) / TRD, s.G, B);
   hipStream_t st = ts::as_stream(stream);
-  if (vec) hipLaunchKernelGGL((dense_warp_kernel<MODE, true>), grid, dim3(256), lds_bytes, st, left, right, disp, out, maxbits, s);
-  else hipLaunchKernelGGL((dense_warp_kernel<MODE, false>), grid, dim3(256), lds_bytes, st, left, right, disp, out, maxbits, s);
+  ts::dispatch_bool(vec, [&](auto V) {
+    hipLaunchKernelGGL((dense_warp_kernel<MODE, V()>), grid, dim3(256), lds_bytes, st, left, right, disp, out, maxbits, s);
+  });
   return ts::launched("dense_warp_kernel");
 }
 }  // namespace

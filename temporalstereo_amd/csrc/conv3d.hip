@@ -24,6 +24,7 @@
 
 #include "conv_common.hpp"
 #include "conv_x6p.hpp"
+#include "warp.hpp"
 
 namespace {
 
@@ -832,15 +833,15 @@ thread_local int g_chunk_cap = 32;
 // grids below this many workgroups take the two-chunks-in-flight form of the NC = 8 kernel (TS_CONV_PF_MAX_WGS, 0 = never)
 // Environment switches are read by NAMED functions: hipcc 7.2 resolved a third namespace-scope `= [] { ... }()` initialiser of
 // this file to the FIRST such lambda (a bool came out holding 192 -- the default of g_pf_max_wgs -- and tested false).
-const long long g_pf_max_wgs = env_ll("TS_CONV_PF_MAX_WGS", 512);     // measured again with the 64-pixel tiles in place (their grids count four-fold): 256 / 512 / 1024 = 1191 / 1189 / 1176 pairs/s, one pass at a time 846 / 846 / 841
+const long long g_pf_max_wgs = ts::env_ll("TS_CONV_PF_MAX_WGS", 512);     // measured again with the 64-pixel tiles in place (their grids count four-fold): 256 / 512 / 1024 = 1191 / 1189 / 1176 pairs/s, one pass at a time 846 / 846 / 841
 // grids of at most this many 8 x 32 workgroups run the plain (1,3,3) forms on 4 x 16 pixel tiles (launch_ig); measured 0 / 64 / 128 / 256 / 512: 1163 / 1170 / 1174 / 1181 / 1181 pairs/s, one pass at a time 808 / 816 / 823 / 833 / 835
-const long long g_small_hw = env_ll("TS_CONV_HW_SMALL_WGS", 256);
+const long long g_small_hw = ts::env_ll("TS_CONV_HW_SMALL_WGS", 256);
 // small grids of Cout <= 8 layers with 64+ input channels: 4 x 16 tiles (plain form, half of each MFMA idle, no split-K) instead of the
 // row-paired 8 x 32 form -- 64 -> 2 on 14 x 34 x 60 (the coarse prediction heads) 14.1 -> 10.1 us, 128 -> 8 on 136 x 240 20.1 -> 16.5;
 // 32 -> 2 on 7 x 68 x 120 would lose (9.4 -> 10.4)
-const bool g_small_over_pairing = env_ll("TS_CONV_SMALL_OVER_PAIRING", 1) != 0;
+const bool g_small_over_pairing = ts::env_ll("TS_CONV_SMALL_OVER_PAIRING", 1) != 0;
 // TS_CONV_ROW_PAIRING=0 switches the Cout <= 8 row pairing off (A/B measurements)
-const bool g_row_pairing = env_not_zero("TS_CONV_ROW_PAIRING");
+const bool g_row_pairing = ts::env_not_zero("TS_CONV_ROW_PAIRING");
 
 template <int CB, int MODE, int KT, int ST, int DL, int NC, int PR = 0, int PF = 0, int TP = 256>
 int launch_one(const float* x, const float* w, const float* scale, const float* shift, float* y, const IG& p,
@@ -915,12 +916,12 @@ int launch_ig(const float* x, const float* w, const float* scale, const float* s
   while (cb > 1 && tiles * groups(cb) < ts::kNumCU + ts::kNumCU / 2) cb >>= 1;
   p.co_groups = groups(cb);
   p.B = B;
-  static const int xcd = env_not_zero("TS_CONV_XCD") ? 1 : 0;
+  static const int xcd = ts::env_not_zero("TS_CONV_XCD") ? 1 : 0;
   p.xcd = xcd;
   const long long wgs = tiles * p.co_groups;
   if constexpr (MODE == MODE_D) {
     // few dozen workgroups: 64-pixel tiles (Geom, TP) -- four times the workgroups, a quarter of the K loop's matrix and staging work each
-    static const long long small = env_ll("TS_CONV_D_SMALL_WGS", 256);   // measured 0 / 64 / 128 / 256 / 512 / 1024: 1129 / 1156 / 1165 / 1165 / 1162 / 1153 pairs/s, one pass at a time 768 / 795 / 798 / 812 / 811 / 809
+    static const long long small = ts::env_ll("TS_CONV_D_SMALL_WGS", 256);   // measured 0 / 64 / 128 / 256 / 512 / 1024: 1129 / 1156 / 1165 / 1165 / 1162 / 1153 pairs/s, one pass at a time 768 / 795 / 798 / 812 / 811 / 809
     if (wgs <= small && cb == 1) {
       const int gx64 = (p.H * p.W + 63) / 64;
       const dim3 grid64(gx64, grid_y, B * p.co_groups * p.ksplit);
@@ -1330,7 +1331,7 @@ wgrad_finish_many(const WgradFinishDesc* __restrict__ table, int n) {
 // (304 -> 8 on 5 x 136 x 240: 262 -> 214 us with three).  Layers whose workgroups fit once per CU keep two rounds.
 // TS_WGRAD_GROUPS_PER_CU > 0 forces the old rule with that many per CU.
 int wgrad_groups(int ciblocks, size_t lds_bytes) {
-  static const long long per_cu_env = env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
+  static const long long per_cu_env = ts::env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
   if (per_cu_env > 0) return (static_cast<int>(per_cu_env) * ts::kNumCU + ciblocks - 1) / ciblocks;
   int fit = static_cast<int>((160 * 1024) / (lds_bytes ? lds_bytes : 1));
   fit = fit < 1 ? 1 : (fit > 4 ? 4 : fit);
@@ -1339,7 +1340,7 @@ int wgrad_groups(int ciblocks, size_t lds_bytes) {
   return g < 1 ? 1 : g;
 }
 int wgrad_groups_max(int ciblocks) {      // what the workspace is sized for
-  static const long long per_cu_env = env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
+  static const long long per_cu_env = ts::env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
   const int per_cu = per_cu_env > 4 ? static_cast<int>(per_cu_env) : 4;
   return (per_cu * ts::kNumCU + ciblocks - 1) / ciblocks;
 }
@@ -1362,7 +1363,7 @@ int launch_wgrad(const float* x, const float* dy, float* dw, WG p, void* workspa
     p.tiles_per_plane = (p.Ho * p.Wo + 255) / 256;
   }
   p.ntiles = p.B * p.Do * p.tiles_per_plane;
-  static const bool vec_ok = env_not_zero("TS_WGRAD_VEC");
+  static const bool vec_ok = ts::env_not_zero("TS_WGRAD_VEC");
   p.vec = (MODE == MODE_HW && vec_ok && p.W % 4 == 0 && ts::aligned16(x) && p.x_cstride % 4 == 0 && p.x_bstride % 4 == 0) ? 1 : 0;
   const int ciblocks = (p.Cin + 15) / 16;
   const int cob = (p.Cout + 15) / 16, nitems = KT * cob;
@@ -1515,7 +1516,7 @@ int conv_hw_impl(const float* x, const float* w_t, const float* scale, const flo
 //     T = left term + sum_{t=(ky,kx)} lerp(Q[t][co][y+ky-1], (x+kx-1) - disp[d][y+ky-1][x+kx-1])        (zero where the tap's pixel
 // is outside the image: the convolution's zero padding; zero for columns outside the row: the warp's zeros padding), added to
 // the convolution over the correlation channels as a per-depth-plane addend of ig_conv_kernel.
-// The tap arithmetic is block_cost.hip's (the reference's normalise / un-normalise float sequence), so tap positions round identically.
+// The tap position is block_cost.hip's (ts::source_position, warp.hpp), so taps round identically.
 // One lane per output pixel of one candidate; the two columns of a tap are one 8-byte load (dword-aligned buffer load).
 // ------------------------------------------------------------------------------------------------
 
@@ -1562,11 +1563,7 @@ warp_gather_kernel(const float* __restrict__ q, const float* __restrict__ disp, 
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     const int qy = y + (t / 3 - 1) * DL, qx = x + (t % 3 - 1) * DL;
-    // same float sequence as block_cost.hip tap4<true> (inverse_warp_3d.py:41-47 and grid_sample's un-normalisation)
-    const float xs = static_cast<float>(qx) + (-dv[t]);
-    const float gx = (xs / Wm1 * 2.f) - 1.f;
-    float ix = ((gx + 1.f) / 2.f) * Wm1;
-    ix = fminf(fmaxf(ix, -2.f), static_cast<float>(W) + 1.f);
+    const float ix = ts::source_position(qx, dv[t], W, Wm1);     // the tap position block_cost.hip computes
     const float fl = floorf(ix);
     const float f = ix - fl;
     const int xi = static_cast<int>(fl);
@@ -1621,7 +1618,7 @@ namespace {
 // So: only reductions of 16+ chunks (Cin >= 256), as many slices (2 | 4 | 8, two chunks each at least) as keep the grid within the
 // chip's 2 x 256 workgroup slots (+ 1/8).  TS_X6_KSPLIT=1 switches it off, =N forces N slices where the channel count allows.
 int x6_ksplit(int B, int Cin, int Cout, int D, int H, int W) {
-  static const long long forced = env_ll("TS_X6_KSPLIT", 0);
+  static const long long forced = ts::env_ll("TS_X6_KSPLIT", 0);
   const int nchunk = (Cin + X6_NC - 1) / X6_NC;
   const int need = (Cout + 15) / 16, cb = need >= 2 ? 2 : 1;
   const long long wgs = static_cast<long long>((H + 7) / 8) * ((W + 31) / 32) * D * B * ((need + cb - 1) / cb);
@@ -1696,7 +1693,7 @@ int conv_hw_x6_impl(const float* x, const void* w6, const float* scale, const fl
   p.stride = 1; p.dil = dilation; p.pad = dilation; p.k = 3; p.transposed = 0;
   p.act = act; p.act_param = act_param;
   p.in_bstride = in_bstride; p.in_cstride = in_cstride; p.out_bstride = out_bstride; p.out_cstride = out_cstride;
-  static const int no_xcd = env_not_zero("TS_X6_XCD") ? 0 : 1;
+  static const int no_xcd = ts::env_not_zero("TS_X6_XCD") ? 0 : 1;
   p.ksplit = 1; p.kspan = (Cin + X6_NC - 1) / X6_NC * X6_NC; p.partial = nullptr; p.B = B; p.xcd = !no_xcd;
   p.addend = addend; p.add_bstride = addend_bstride; p.add_cstride = static_cast<long long>(H) * W; p.add_dstride = 0;
   TS_REQUIRE(ig_extent(p, 9), TS_ERR_UNSUPPORTED, "conv3d_hw_x6: a batch element of x spans 2 GiB or more");
@@ -1741,9 +1738,9 @@ int conv_hw_x6_impl(const float* x, const void* w6, const float* scale, const fl
   // for unsplit dilation-1 layers with 17+ output channels (its A operand is 32 channels wide) and SiLU / ReLU / no activation, from
   // TS_X6P_MIN_WGS 8 x 32 tiles;
   // TS_X6P=0 keeps every layer on ig_conv_x6_kernel.
-  static const bool x6p_on = env_not_zero("TS_X6P");
-  static const long long x6p_min = env_ll("TS_X6P_MIN_WGS", 128);        // of its 8 x 32 work items: 136 (128 -> 32 on 136 x 240) 29.3 vs 37.5 us, 72 (128 -> 64 on 68 x 120) 27.0 vs 24.7
-  static const bool x6p_split_on = env_not_zero("TS_X6P_KSPLIT");
+  static const bool x6p_on = ts::env_not_zero("TS_X6P");
+  static const long long x6p_min = ts::env_ll("TS_X6P_MIN_WGS", 128);        // of its 8 x 32 work items: 136 (128 -> 32 on 136 x 240) 29.3 vs 37.5 us, 72 (128 -> 64 on 68 x 120) 27.0 vs 24.7
+  static const bool x6p_split_on = ts::env_not_zero("TS_X6P_KSPLIT");
   if (x6p_on && dilation == 1 && Cout > 16 && act <= ACT_RELU) {
     ts::X6P q;
     q.Cin = Cin; q.Cout = Cout; q.coutp = p.coutp; q.B = B; q.D = D; q.H = H; q.W = W; q.act = act; q.act_param = act_param;
@@ -1780,8 +1777,8 @@ int conv_hw_x6_impl(const float* x, const void* w6, const float* scale, const fl
     }
   }
   // grids under 3/4 of a round of 8-row workgroups (2 per CU): 4-row tiles (ig_conv_x6_kernel, TR); TS_X6_TR=8 | 4 forces one form
-  static const long long tr_env = env_ll("TS_X6_TR", 0);
-  static const long long tr4_below = env_ll("TS_X6_TR4_BELOW", 3 * ts::kNumCU / 2);       // measured 384 / 576 / 768 / 1100: 1297 / 1287 / 1286 / 1273 pairs/s with three passes in flight, 934 / 935 / 936 / 942 one at a time
+  static const long long tr_env = ts::env_ll("TS_X6_TR", 0);
+  static const long long tr4_below = ts::env_ll("TS_X6_TR4_BELOW", 3 * ts::kNumCU / 2);       // measured 384 / 576 / 768 / 1100: 1297 / 1287 / 1286 / 1273 pairs/s with three passes in flight, 934 / 935 / 936 / 942 one at a time
   const long long wgs8 = static_cast<long long>(tiles) * D * B * p.co_groups * p.ksplit;
   const bool tr4 = dilation == 1 && (tr_env ? tr_env == 4 : wgs8 < tr4_below);
   if (tr4) {

@@ -1,8 +1,6 @@
 // Device-side pieces shared by the convolution kernels (conv3d.hip, conv_x6s.hip): activation codes, the launch
 // descriptor, buffer-resource helper and the fp32 -> three-bf16 split of the "x6" kernels.
 #pragma once
-#include <cstdlib>
-
 #include "ts_common.hpp"
 
 namespace {
@@ -106,8 +104,5 @@ __device__ __forceinline__ void split6(float a, float b, unsigned& hi, unsigned&
   a -= __uint_as_float(mid << 16); b -= __uint_as_float(mid & 0xffff0000u);
   lo = pack_bf16(a, b);
 }
-
-inline long long env_ll(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
-inline bool env_not_zero(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
 
 }  // namespace

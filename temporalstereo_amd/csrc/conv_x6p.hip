@@ -435,7 +435,7 @@ int x6p_rows(const X6P& p) {
   // of two 8 x 32 ones (less halo, half the weight reads) but quantises worse: 128 -> 32 on 136 x 240 is 72 big tiles (one round at
   // 28 % of the chip, 43.9 us) or 136 small ones (29.3 us); 64 -> 64 on 2 x 136 x 240 is 288 / 544 tiles: 2 x 1 vs 3 x 0.58
   // (tools/exp/x6p_check.py, table in profiles/r06_x6p_layers.txt).  TS_X6P_HR=4 | 8 forces one.
-  static const long long forced = env_ll("TS_X6P_HR", 0);
+  static const long long forced = ts::env_ll("TS_X6P_HR", 0);
   if (forced == 4 || forced == 8) return static_cast<int>(forced);
   const long long r8 = (tiles_of(p, 8) + kNumCU - 1) / kNumCU, r4 = (tiles_of(p, 4) + kNumCU - 1) / kNumCU;
   return 100 * r8 <= 58 * r4 ? 8 : 4;
@@ -446,9 +446,9 @@ long long x6p_grid(const X6P& p) { return tiles_of(p, 4); }
 
 int x6p_launch(const float* x, const void* w6, const float* scale, const float* shift, float* y, X6P p, void* stream) {
   const int hr = x6p_rows(p);
-  static const long long dbg = env_ll("TS_X6P_DBG", 0);
+  static const long long dbg = ts::env_ll("TS_X6P_DBG", 0);
   p.dbg = static_cast<int>(dbg);
-  static const long long trace_wg = env_ll("TS_X6P_TRACE", -1);
+  static const long long trace_wg = ts::env_ll("TS_X6P_TRACE", -1);
   if (trace_wg != -1 && !trace_buf) { (void)hipMalloc(reinterpret_cast<void**>(&trace_buf), kTraceBytes); (void)hipMemset(trace_buf, 0, kTraceBytes); }
   p.trace = trace_buf; p.trace_wg = static_cast<int>(trace_wg);
   p.tiles_x = (p.W + 31) / 32;
@@ -464,12 +464,12 @@ int x6p_launch(const float* x, const void* w6, const float* scale, const float* 
   // Cap 208 of 256: measured 256 / 232 / 224 / 208 / 192 / 176 / 160 / 128 -> 1318 / 1335 / 1322 / 1333 / 1330 / 1313 / 1305 / 1266 pairs/s with
   // three passes in flight, batch 4 1763 / 1804 / 1802 / 1798 / 1810 / 1771 / 1767 / 1742, one pass at a time 961-965 throughout (>= 160): what a
   // pass's throughput follows is CU-time, not this launch's latency, and a workgroup that walks more tiles pays its prologue once.
-  static const long long max_wgs0 = env_ll("TS_X6P_WGS", 208);
+  static const long long max_wgs0 = ts::env_ll("TS_X6P_WGS", 208);
   // ... except a split-K launch of <= 256 items, which runs in ONE round: the coarse level's first layer (352 -> 32 on 12 x 34 x 60: 120
   // tiles x 2 slices) is the longest launch on a pass's critical chain, 66.5 us as 120 workgroups x 2 items, 45.6 as 240 x 1; three
   // passes in flight do not notice (1540-1546 pairs/s either way), one pass at a time gains 1-1.5 % (982 -> 991-997).  The 255-tile
   // layers of the UNet stay under the cap: all of the chip for them costs the pass's other streams more than it saves (972 vs 982-990).
-  static const long long splitk_all = env_ll("TS_X6P_SPLITK_ALL", 1);
+  static const long long splitk_all = ts::env_ll("TS_X6P_SPLITK_ALL", 1);
   const long long max_wgs = (splitk_all && p.ksplit > 1 && total <= 256) ? 256 : max_wgs0;
   int nwg = static_cast<int>(total < max_wgs ? total : max_wgs);
   {

@@ -382,7 +382,7 @@ extern "C" int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float*
   p.in_bstride = in_bstride; p.in_cstride = in_cstride; p.out_bstride = out_bstride; p.out_cstride = out_cstride;
   p.ksplit = 1; p.kspan = Cin; p.partial = nullptr; p.B = B; p.part_bytes = 0;
   p.addend = nullptr; p.add_bstride = p.add_cstride = p.add_dstride = 0;
-  static const int xcd = env_not_zero("TS_X6_XCD") ? 1 : 0;
+  static const int xcd = ts::env_not_zero("TS_X6_XCD") ? 1 : 0;
   p.xcd = xcd;
   {
     const unsigned long long in_b = (static_cast<unsigned long long>(Cin - 1) * in_cstride + static_cast<unsigned long long>(D) * H * W) * 4ull;
@@ -409,7 +409,7 @@ extern "C" int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float*
   // 24 KB of LDS, three per CU) halves the chain.  Measured (tools/x6s_bench.py, 8 -> 4 rows): deconv4 32 -> 32 on 136 x 240 (272
   // workgroups of 8 rows) 21.5 -> 17.8 us, the hourglasses' transposed layers 15.5 -> 10.8 and 19.4 -> 12.1; deconv2 32 -> 9 on 272 x 480
   // (510 workgroups: a full round of the 8-row form) 23.2 -> 24.9, batch 4 flat.  So: 4 rows below 3/4 of a round.  TS_X6S_TR=4 | 8 forces one.
-  static const long long tr_env = env_ll("TS_X6S_TR", 0);
+  static const long long tr_env = ts::env_ll("TS_X6S_TR", 0);
   const long long wgs8 = static_cast<long long>((H + 7) / 8) * p.tiles_x * D * B * p.co_groups;
   const long long tr = tr_env ? tr_env : (wgs8 < 3 * ts::kNumCU / 2 ? 4 : 8);
   if (tr == 4) {

@@ -5,6 +5,8 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <type_traits>
 
 #include "../../include/ts_hip.h"
 
@@ -28,6 +30,17 @@ inline int launched(const char* what) {
   if (e != hipSuccess) return fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
   return TS_OK;
 }
+
+// a runtime bool as a compile-time one: dispatch_bool(vec, [&](auto V) { hipLaunchKernelGGL(kern<V()>, ...); })
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// environment switches (callers read them once, into a `static const`): a number with a default; on unless the value starts with '0'
+inline long long env_ll(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+inline bool env_not_zero(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
 
 constexpr int kWave = 64;       // CDNA4 wavefront
 constexpr int kNumCU = 256;     // MI355X

@@ -76,7 +76,13 @@ SHAPES = [  # B, C, H, W, D  -- levels of the BASELINE configs at reduced batch/
 ]
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+MANY_PLANES = [  # B * C/8 * D = 65,600 planes of the pooled maps, more than one grid dimension holds: the expansion folds them over
+    (4, 128, 4, 8, 1025),    # two.  Aligned.                          (Several passes of items per workgroup: block_cost_main.)
+    (4, 128, 5, 9, 1025),    # ragged: scalar loads and stores, H not a multiple of 4
+]
+
+
+@pytest.mark.parametrize("shape", SHAPES + MANY_PLANES)
 def test_int_path_vs_oracle(shape):
     import temporalstereo_amd as ts
     B, C, H, W, D = shape
