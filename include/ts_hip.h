@@ -404,6 +404,52 @@ int ts_project_to_3d_fwd(const float* depth, const float* K, const float* inv_K,
                          float* triangular_depth, float* optical_flow, unsigned char* flow_mask,
                          int B, int C, int H, int W, int k_dim, int inv_k_dim, float eps, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The 2-D inverse warp (ABI 14).
+ * Replaces inverse_warp()  architecture/modeling/layers/inverse_warp.py:6-77 -- pixel grid, normalisation, the [B,H,W,2] grid
+ * tensor and F.grid_sample(align_corners=True) -- and, in depth mode, the project_to_3d() it calls (:92-178), in ONE launch.
+ *   img [B,C,Hi,Wi]; motion [B,1,H,W] (disparity, depth) or [B,2,H,W] (flow: x then y); out [B,C,H,W].  The image may differ in
+ *   size from the motion map: the reference normalises with H, W and grid_sample un-normalises with Hi, Wi.  All four >= 2.
+ *   mode    TS_WARP_DISPARITY  X = x + m, Y = y
+ *           TS_WARP_FLOW       X = x + m0, Y = y + m1
+ *           TS_WARP_DEPTH      (X, Y) = src_pixel_coord of project_to_3d(motion, K, inv_K, T, eps): K [B,k,k] (k = 3|4),
+ *                              inv_K [B,ik,ik], T [B,4,4], all three required; the arithmetic is ts_project_to_3d_fwd's, bit for bit
+ *   position  gx = (2 X) / (W - 1) - 1, ix = ((gx + 1) / 2) * (Wi - 1), each step rounded as the reference's fp32 run rounds it;
+ *             likewise for y with H, Hi
+ *   pad     TS_WARP_ZEROS taps outside contribute 0; TS_WARP_BORDER position clipped to [0, size - 1]; TS_WARP_REFLECTION
+ *           reflected over [0, size - 1] as often as needed, then clipped
+ *   interp  TS_WARP_BILINEAR; TS_WARP_NEAREST (round half to even); TS_WARP_BICUBIC is TS_ERR_UNSUPPORTED
+ *   The position is clamped to a finite range before any conversion to int: no motion, however large or non-finite, indexes
+ *   outside the image (the value there is unspecified).
+ *   Side outputs of depth mode, each may be NULL (ignored in the other modes): triangular_depth [B,1,H,W], src_pixel_coord
+ *   [B,2,H,W], optical_flow [B,2,H,W], flow_mask [B,1,H,W] (uint8), homo_points_3d [B,4,H*W].
+ * ts_inverse_warp_bwd: grad_out [B,C,H,W].  Either gradient may be NULL, not both.
+ *   grad_img    [B,C,Hi,Wi] is ACCUMULATED with fp32 hardware atomics into what the caller zero-filled: the summation order is not
+ *               deterministic (the contract of ts_softsplat_sum_fwd)
+ *   grad_motion (the motion's shape) is OVERWRITTEN and deterministic: the tap differences reduced over the channels, times
+ *               (Wi - 1) / (W - 1) resp. (Hi - 1) / (H - 1); 0 where TS_WARP_BORDER clipped the position, sign flipped on odd
+ *               reflections, 0 everywhere for TS_WARP_NEAREST; in depth mode through d src_pixel_coord / d depth.  Needs img.
+ *   K, inv_K and T are constants: no gradient reaches them.
+ * Checks, before any launch: sizes (TS_ERR_SHAPE, also any of H, W, Hi, Wi < 2), then codes (TS_ERR_UNSUPPORTED), then pointers
+ * (TS_ERR_NULL, also depth mode without K, inv_K or T).
+ * ---------------------------------------------------------------------------------------- */
+#define TS_WARP_DISPARITY 0
+#define TS_WARP_FLOW 1
+#define TS_WARP_DEPTH 2
+#define TS_WARP_BILINEAR 0
+#define TS_WARP_NEAREST 1
+#define TS_WARP_BICUBIC 2
+#define TS_WARP_ZEROS 0
+#define TS_WARP_BORDER 1
+#define TS_WARP_REFLECTION 2
+int ts_inverse_warp_fwd(const float* img, const float* motion, const float* K, const float* inv_K, const float* T, float* out,
+                        float* triangular_depth, float* src_pixel_coord, float* optical_flow, unsigned char* flow_mask,
+                        float* homo_points_3d, int B, int C, int Hi, int Wi, int H, int W, int mode, int interp, int pad,
+                        int k_dim, int inv_k_dim, float eps, void* stream);
+int ts_inverse_warp_bwd(const float* img, const float* motion, const float* K, const float* inv_K, const float* T,
+                        const float* grad_out, float* grad_img, float* grad_motion, int B, int C, int Hi, int Wi, int H, int W,
+                        int mode, int interp, int pad, int k_dim, int inv_k_dim, float eps, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

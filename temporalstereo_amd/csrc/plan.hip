@@ -103,6 +103,7 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_frames_augment_fwd),      TS_PLAN_OP(ts_disp_u16_window_fwd),
     TS_PLAN_OP(ts_block_cost_sampled_corr_split_fwd), TS_PLAN_OP(ts_conv3d_hw_split_fwd),
     TS_PLAN_OP(ts_conv3d_d_split_fwd),      TS_PLAN_OP(ts_conv3d_hw_x6_split_fwd),
+    TS_PLAN_OP(ts_inverse_warp_fwd),        TS_PLAN_OP(ts_inverse_warp_bwd),
 };
 
 struct Call {

@@ -12,6 +12,7 @@
 // design goal is ONE launch per op with no per-shape recompilation (the reference bakes sizes and
 // strides into NVRTC source, softsplat.py:179-232).  Scatter uses fp32 hardware atomics
 // (global_atomic_add_f32), like the reference's atomicAdd: summation order is not deterministic.
+#include "project.hpp"
 #include "ts_common.hpp"
 
 namespace {
@@ -192,30 +193,14 @@ splat_grad_flow(const float* __restrict__ input, const float* __restrict__ flow,
 }
 
 // ------------------------------------------------------------------------------------------ K2a
-// per pixel and depth plane: X = invK * [u v 1]^T * depth; cam = (K*T)[:3] * [X 1]; inverse_warp.py:119-170
+// per pixel and depth plane: X = invK * [u v 1]^T * depth; cam = (K*T)[:3] * [X 1]; inverse_warp.py:119-170 (project.hpp)
 __global__ void __launch_bounds__(256)
 project_kernel(const float* __restrict__ depth, const float* __restrict__ K, const float* __restrict__ invK,
                const float* __restrict__ T, float* __restrict__ tri, float* __restrict__ flowo,
                unsigned char* __restrict__ mask, int B, int C, int H, int W, int kdim, int ikdim, float eps) {
-  __shared__ float P[3][4];
-  __shared__ float iK[3][3];
+  __shared__ ts::Projection pr;
   const int b = blockIdx.y;
-  if (threadIdx.x < 12) {
-    const int r = threadIdx.x / 4, c = threadIdx.x % 4;
-    // new_K (4x4, identity-padded when K is 3x3) times T, first three rows (:138-146)
-    float acc = 0.f;
-    for (int k = 0; k < 4; ++k) {
-      float kv;
-      if (k < kdim && r < kdim) kv = K[(static_cast<size_t>(b) * kdim + r) * kdim + k];
-      else kv = (r == k) ? 1.f : 0.f;
-      acc += kv * T[(static_cast<size_t>(b) * 4 + k) * 4 + c];
-    }
-    P[r][c] = acc;
-  } else if (threadIdx.x >= 16 && threadIdx.x < 25) {
-    const int j = threadIdx.x - 16;
-    iK[j / 3][j % 3] = invK[(static_cast<size_t>(b) * ikdim + j / 3) * ikdim + j % 3];
-  }
-  __syncthreads();
+  ts::load_projection(pr, K, invK, T, b, kdim, ikdim);
   const int HW = H * W;
   const int n = C * HW;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -223,19 +208,14 @@ project_kernel(const float* __restrict__ depth, const float* __restrict__ K, con
     const int y = p / W, x = p - y * W;
     const float u = static_cast<float>(x), v = static_cast<float>(y);
     const float z = depth[static_cast<size_t>(b) * n + i];
-    const float X = (iK[0][0] * u + iK[0][1] * v + iK[0][2]) * z;
-    const float Y = (iK[1][0] * u + iK[1][1] * v + iK[1][2]) * z;
-    const float Z = (iK[2][0] * u + iK[2][1] * v + iK[2][2]) * z;
-    const float cx = P[0][0] * X + P[0][1] * Y + P[0][2] * Z + P[0][3];
-    const float cy = P[1][0] * X + P[1][1] * Y + P[1][2] * Z + P[1][3];
-    const float cz = P[2][0] * X + P[2][1] * Y + P[2][2] * Z + P[2][3];
-    const float sx = cx / (cz + eps), sy = cy / (cz + eps);
+    const ts::Projected o = ts::project_pixel(pr, u, v, z, eps);
+    const float cz = o.cz, sx = o.sx, sy = o.sy;
     if (tri) tri[static_cast<size_t>(b) * n + i] = cz;
     if (flowo) {
       flowo[(static_cast<size_t>(b) * C * 2 + 2 * c) * HW + p] = sx - u;
       flowo[(static_cast<size_t>(b) * C * 2 + 2 * c + 1) * HW + p] = sy - v;
     }
-    if (mask) mask[static_cast<size_t>(b) * n + i] = (sx >= 0.f) & (sx <= static_cast<float>(W - 1)) & (sy >= 0.f) & (sy <= static_cast<float>(H - 1));
+    if (mask) mask[static_cast<size_t>(b) * n + i] = ts::projected_inside(sx, sy, H, W);
   }
 }
 

@@ -1985,3 +1985,126 @@ def project_to_3d(depth, K, inv_K=None, T_target_to_source=None, eps=1e-7):
                                                float(eps), _stream()), "ts_project_to_3d_fwd")
     out = {'triangular_depth': tri, 'optical_flow': flow, 'flow_mask': mask.bool()}
     return out
+
+
+# ----------------------------------------------------------------------------------- the 2-D inverse warp
+_WARP_MODES = {'disparity': 0, 'flow': 1, 'depth': 2}
+_WARP_INTERP = {'bilinear': 0, 'nearest': 1, 'bicubic': 2}
+_WARP_PAD = {'zeros': 0, 'border': 1, 'reflection': 2}
+
+
+class _InverseWarp(torch.autograd.Function):
+    """ts_inverse_warp_fwd / ts_inverse_warp_bwd.  Returns (warped, triangular_depth, src_pixel_coord, optical_flow, flow_mask,
+    homo_points_3d); the last five are None unless `side`, and are marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, img, motion, K, inv_K, T, codes, eps, side):
+        mode, interp, pad = codes
+        B, C, Hi, Wi = img.shape
+        H, W = motion.shape[2:]
+        f32 = dict(device=img.device, dtype=torch.float32)
+        out = torch.empty((B, C, H, W), **f32)
+        tri = coord = flow = mask = homo = None
+        if side:
+            tri, coord, flow = torch.empty((B, 1, H, W), **f32), torch.empty((B, 2, H, W), **f32), torch.empty((B, 2, H, W), **f32)
+            mask, homo = torch.empty((B, 1, H, W), device=img.device, dtype=torch.uint8), torch.empty((B, 4, H * W), **f32)
+        kd = K.shape[-1] if K is not None else 0
+        ikd = inv_K.shape[-1] if inv_K is not None else 0
+        p = _lib.ptr
+        rc = _lib.lib().ts_inverse_warp_fwd(p(img), p(motion), p(K), p(inv_K), p(T), p(out), p(tri), p(coord), p(flow), p(mask), p(homo),
+                                            B, C, Hi, Wi, H, W, mode, interp, pad, kd, ikd, float(eps), _stream())
+        _lib.check(rc, "ts_inverse_warp_fwd")
+        ctx.save_for_backward(img, motion, K, inv_K, T)
+        ctx.geom = (codes, kd, ikd, float(eps))
+        if side:
+            mask = mask.bool()
+            ctx.mark_non_differentiable(tri, coord, flow, mask, homo)
+        return out, tri, coord, flow, mask, homo
+
+    @staticmethod
+    def backward(ctx, g, *_side):
+        img, motion, K, inv_K, T = ctx.saved_tensors
+        (mode, interp, pad), kd, ikd, eps = ctx.geom
+        B, C, Hi, Wi = img.shape
+        H, W = motion.shape[2:]
+        need_img, need_motion = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_img or need_motion):
+            return (None,) * 8
+        g = _lib.contiguous(g)
+        gi = torch.zeros_like(img) if need_img else None            # accumulated into with atomics: order not deterministic
+        gm = torch.empty_like(motion) if need_motion else None      # overwritten: deterministic
+        p = _lib.ptr
+        rc = _lib.lib().ts_inverse_warp_bwd(p(img), p(motion), p(K), p(inv_K), p(T), p(g), p(gi), p(gm), B, C, Hi, Wi, H, W,
+                                            mode, interp, pad, kd, ikd, eps, _stream())
+        _lib.check(rc, "ts_inverse_warp_bwd")
+        return (gi, gm) + (None,) * 6
+
+
+def mesh_grid(b, h, w, device, dtype=torch.float):
+    """mesh_grid of the reference (layers/inverse_warp.py:80-90): pixel coordinates [b, 2, h, w], x then y."""
+    x_range = torch.arange(0, w, device=device, dtype=dtype).view(1, 1, 1, w).expand(b, 1, h, w)
+    y_range = torch.arange(0, h, device=device, dtype=dtype).view(1, 1, h, 1).expand(b, 1, h, w)
+    return torch.cat((x_range, y_range), dim=1)
+
+
+def inverse_warp(img, motion, mode='disparity', K=None, inv_K=None, T_target_to_source=None, interpolate_mode='bilinear',
+                 padding_mode='zeros', eps=1e-7, output_all=False):
+    """inverse_warp of the reference (layers/inverse_warp.py:6-77; same arguments, order and defaults): img [B,C,Hi,Wi] sampled at
+    the source position of every pixel of motion -- [B,1,H,W] disparity (X = x + m) or depth (X, Y = src_pixel_coord of
+    project_to_3d with K, inv_K, T_target_to_source), [B,2,H,W] flow -- through the reference's normalise / grid_sample
+    (align_corners=True) round trip, in one launch.  interpolate_mode 'bilinear' | 'nearest' ('bicubic' is refused by the library);
+    padding_mode 'zeros' | 'border' | 'reflection'.  Differentiable in img (atomics: summation order not deterministic) and motion
+    (deterministic); K, inv_K and T_target_to_source are constants and are refused if they require grad.
+
+    output_all=True returns (projected_img, output): in depth mode the reference's five keys (homo_points_3d, triangular_depth,
+    flow_mask (bool), src_pixel_coord, optical_flow) from the same launch, else {}.  The one difference to the reference: these side
+    outputs are not differentiable.  inv_K=None means torch.inverse(K[:, :3, :3]).  Depth mode without T_target_to_source raises a
+    ValueError (the reference fails there with a bare KeyError)."""
+    if img.dim() != 4 or motion.dim() != 4:
+        raise ValueError("inverse_warp: img must be [B,C,Hi,Wi] and motion [B,1|2,H,W], got %s and %s" % (tuple(img.shape), tuple(motion.shape)))
+    B, C, H, W = motion.shape
+    if mode == 'disparity':
+        assert C == 1, "Disparity map must be 1 channel, but {} got!".format(C)
+    elif mode == 'flow':
+        assert C == 2, "Optical flow map must be 2 channel, but {} got!".format(C)
+    elif mode == 'depth':
+        assert C == 1, "Disparity map must be 1 channel, but {} got!".format(C)
+    else:
+        raise TypeError("Inverse warp only support [disparity, flow, depth] mode, but {} got".format(mode))
+    if interpolate_mode not in _WARP_INTERP:
+        raise ValueError("inverse_warp: unknown interpolate_mode %r" % (interpolate_mode,))
+    if padding_mode not in _WARP_PAD:
+        raise ValueError("inverse_warp: unknown padding_mode %r" % (padding_mode,))
+    if img.shape[0] != B:
+        raise ValueError("inverse_warp: img and motion differ in batch size (%d and %d)" % (img.shape[0], B))
+    depth = mode == 'depth'
+    if depth:
+        if K is None:
+            raise ValueError("inverse_warp: mode='depth' needs the intrinsics K")
+        if T_target_to_source is None:
+            raise ValueError("inverse_warp: mode='depth' needs T_target_to_source: without it project_to_3d yields no "
+                             "src_pixel_coord to sample at")
+        for name, t in (("K", K), ("inv_K", inv_K), ("T_target_to_source", T_target_to_source)):
+            if t is not None and t.requires_grad:
+                raise RuntimeError("inverse_warp: %s requires grad, but it is a constant of the HIP kernel (no gradient reaches it)" % name)
+        # the kernel indexes K, inv_K and T by the motion's batch element: a batch of 1 does not broadcast here, it is refused
+        for name, t, dims in (("K", K, (3, 4)), ("inv_K", inv_K, (3, 4)), ("T_target_to_source", T_target_to_source, (4,))):
+            if t is not None and (t.dim() != 3 or t.shape[0] != B or t.shape[1] != t.shape[2] or t.shape[1] not in dims):
+                raise ValueError("inverse_warp: %s must be [%d, k, k] with k in %s (the motion's batch size), got %s"
+                                 % (name, B, dims, tuple(t.shape)))
+        _require_gpu(img, motion, K, inv_K, T_target_to_source)
+        if inv_K is None:
+            inv_K = torch.inverse(K[:, :3, :3])
+        K, inv_K, T = _lib.contiguous(K), _lib.contiguous(inv_K), _lib.contiguous(T_target_to_source)
+    else:
+        _require_gpu(img, motion)
+        K = inv_K = T = None
+    codes = (_WARP_MODES[mode], _WARP_INTERP[interpolate_mode], _WARP_PAD[padding_mode])
+    res = _InverseWarp.apply(_lib.contiguous(img), _lib.contiguous(motion), K, inv_K, T, codes, eps, bool(output_all and depth))
+    if not output_all:
+        return res[0]
+    output = {}
+    if depth:
+        output = {'homo_points_3d': res[5], 'triangular_depth': res[1], 'flow_mask': res[4], 'src_pixel_coord': res[2],
+                  'optical_flow': res[3]}
+    return res[0], output

@@ -1460,6 +1460,102 @@ def augment_cases(M):
     print("\n".join(lines))
 
 
+# ----------------------------------------------------------------------------------------------
+def _warp_geometry(rng, B, H, W, kdim, small):
+    """a camera and a rigid motion per batch element: focal length 0.8 W, principal point at the centre, a rotation of 0.05-0.2 rad
+    about a random axis, a translation of length 0.1-0.4 (`small`: a twentieth of both, for a map of two rows), depth in [1, 9]"""
+    k = 0.05 if small else 1.0
+    K = np.zeros((B, kdim, kdim))
+    T = np.zeros((B, 4, 4))
+    for b in range(B):
+        K[b] = np.eye(kdim)
+        K[b, 0, 0] = K[b, 1, 1] = 0.8 * W
+        K[b, 0, 2], K[b, 1, 2] = (W - 1) / 2.0, (H - 1) / 2.0
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        ang = k * rng.uniform(0.05, 0.2)
+        S = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        T[b] = np.eye(4)
+        T[b, :3, :3] = np.eye(3) + np.sin(ang) * S + (1 - np.cos(ang)) * S @ S
+        t = rng.normal(size=3)
+        T[b, :3, 3] = t / np.linalg.norm(t) * k * rng.uniform(0.1, 0.4)
+    depth = rng.uniform(1.0, 9.0, size=(B, 1, H, W))
+    return K, T, depth
+
+
+def warp_cases(M):
+    """tests/golden/inverse_warp_*.npz: the reference's 2-D inverse_warp (layers/inverse_warp.py:6-77) on the CPU, in fp32 and fp64, on
+    seeded inputs, for every mode and padding (bilinear); dev32_64 = max |fp32 run - fp64 run| per output."""
+    from architecture.modeling.layers.inverse_warp import inverse_warp as ref_warp
+    import warp_ref
+    shapes = [("a", 2, 3, 7, 37, 7, 37, 3), ("b", 1, 5, 2, 66, 2, 66, 4), ("c", 2, 1, 9, 13, 5, 21, 3), ("e", 1, 17, 5, 4, 5, 4, 4)]
+    lines = ["inverse_warp_*.npz: tools/gen_golden.py --only-warp, numpy %s, torch %s CPU -- the reference's own inverse_warp" % (np.__version__, torch.__version__),
+             "(architecture/modeling/layers/inverse_warp.py:6-77, with the project_to_3d and mesh_grid it calls) run on seeded inputs in",
+             "float32 and in float64, bilinear, for mode disparity / flow / depth x padding zeros / border / reflection.",
+             "Inputs: img N(0,1); disparity and flow motions uniform in +-0.75 of the map's width resp. height (a third of the positions",
+             "leave the image, some by more than one period of the reflection); depth mode: focal length 0.8 W, principal point at the",
+             "centre, a rotation of 0.05-0.2 rad, a translation of 0.1-0.4 (a twentieth of both for the two-row map of inverse_warp_b, where",
+             "nothing would stay inside otherwise), depth in [1, 9], inv_K = torch.inverse(K[:, :3, :3]) in fp32.",
+             "The generator draws the depth geometry again (next seed) until no fp64 src_pixel_coord lies within 1e-4 px of a flow_mask",
+             "bound (0, W-1, H-1) and the fp32 and fp64 masks are equal, and asserts both.",
+             "Stored: the inputs, the float32 outputs out_<mode>_<padding> and, in depth mode, the five dictionary entries side_<key>;",
+             "dev_* = max |fp32 run - fp64 run| of that output (dev32_64).  tests/warp_ref.py in fp64 agrees with the reference's fp64 run",
+             "to 1e-12 on every output (asserted here)."]
+    total = 0
+    for tag, B, C, H, W, Hi, Wi, kdim in shapes:
+        rng = np.random.default_rng(synth.SEED0 + 7000 + ord(tag))
+        img = rng.normal(size=(B, C, Hi, Wi))
+        disp = rng.uniform(-0.75, 0.75, size=(B, 1, H, W)) * W
+        flow = rng.uniform(-0.75, 0.75, size=(B, 2, H, W)) * np.array([W, H]).reshape(1, 2, 1, 1)
+        for attempt in range(200):
+            grng = np.random.default_rng(synth.SEED0 + 7100 + 1000 * ord(tag) + attempt)
+            K, Tm, depth = _warp_geometry(grng, B, H, W, kdim, small=H < 4)
+            K32, T32, d32 = T(K).float(), T(Tm).float(), T(depth).float()
+            iK32 = torch.inverse(K32[:, :3, :3])
+            o32 = ref_warp(T(img).float(), d32, 'depth', K32, iK32, T32, output_all=True)[1]
+            o64 = ref_warp(T(img), d32.double(), 'depth', K32.double(), iK32.double(), T32.double(), output_all=True)[1]
+            c = o64['src_pixel_coord']
+            gap = min(c[:, 0].abs().min(), (c[:, 0] - (W - 1)).abs().min(), c[:, 1].abs().min(), (c[:, 1] - (H - 1)).abs().min())
+            if gap > 1e-4 and torch.equal(o32['flow_mask'], o64['flow_mask']):
+                break
+        assert gap > 1e-4 and torch.equal(o32['flow_mask'], o64['flow_mask']), (tag, float(gap))
+        valid = float(o64['flow_mask'].float().mean())
+        arrs = dict(img=T(img).float(), motion_disparity=T(disp).float(), motion_flow=T(flow).float(), motion_depth=d32, K=K32, inv_K=iK32, T=T32)
+        devs = []
+        for mode in ('disparity', 'flow', 'depth'):
+            mot = arrs['motion_' + mode]
+            geo32 = (K32, iK32, T32) if mode == 'depth' else (None, None, None)
+            geo64 = tuple(g.double() for g in geo32) if mode == 'depth' else geo32
+            for pad in ('zeros', 'border', 'reflection'):
+                r32, s32 = ref_warp(arrs['img'], mot, mode, *geo32, 'bilinear', pad, output_all=True)
+                r64, s64 = ref_warp(arrs['img'].double(), mot.double(), mode, *geo64, 'bilinear', pad, output_all=True)
+                w64, ws64 = warp_ref.inverse_warp(arrs['img'].double(), mot.double(), mode, *geo64, 'bilinear', pad)
+                assert (w64 - r64).abs().max() < 1e-12, (tag, mode, pad)
+                arrs['out_%s_%s' % (mode, pad)] = r32
+                arrs['dev_%s_%s' % (mode, pad)] = float((r32.double() - r64).abs().max())
+                devs.append(arrs['dev_%s_%s' % (mode, pad)])
+                if mode == 'depth' and pad == 'zeros':
+                    assert sorted(s32) == ['flow_mask', 'homo_points_3d', 'optical_flow', 'src_pixel_coord', 'triangular_depth']
+                    for k in s32:
+                        arrs['side_' + k] = s32[k]
+                        if k != 'flow_mask':
+                            assert (ws64[k] - s64[k]).abs().max() < 1e-10, (tag, k)
+                            arrs['dev_side_' + k] = float((s32[k].double() - s64[k]).abs().max())
+                        else:
+                            assert torch.equal(ws64[k], s64[k])
+        save("inverse_warp_" + tag, **arrs)
+        size = os.path.getsize(os.path.join(OUT, "inverse_warp_%s.npz" % tag))
+        assert size < 100 * 1024, size
+        total += size
+        lines.append("inverse_warp_%s  B=%d C=%d motion %dx%d image %dx%d K %dx%d  dev32_64 of the warped image %.3g .. %.3g; depth: %.0f %% of the "
+                     "pixels valid, geometry draw %d, nearest bound %.2e px; %.0f KB"
+                     % (tag, B, C, H, W, Hi, Wi, kdim, kdim, min(devs), max(devs), 100 * valid, attempt, float(gap), size / 1024))
+    lines.append("total %.0f KB" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_warp.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -1482,6 +1578,9 @@ def main():
         return
     if "--only-prepare" in sys.argv:
         prepare_cases(M)
+        return
+    if "--only-warp" in sys.argv:
+        warp_cases(M)
         return
     if "--only-augment" in sys.argv:
         augment_cases(M)
