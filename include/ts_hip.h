@@ -450,6 +450,34 @@ int ts_inverse_warp_bwd(const float* img, const float* motion, const float* K, c
                         const float* grad_out, float* grad_img, float* grad_motion, int B, int C, int Hi, int Wi, int H, int W,
                         int mode, int interp, int pad, int k_dim, int inv_k_dim, float eps, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CorrBlock: the RAFT-Stereo correlation pyramid and its windowed lookup (ABI 15).
+ * Replaces CorrBlock  architecture/modeling/aggregation/utils/raft_corr.py:4-67.  fmap1, fmap2 [B,C,H,W], disp [B,1,H,W];
+ * n = (b*H + y)*W + x numbers the pixels, N = B*H*W, W_i = W >> i.
+ *   P_0[n][x'] = sum_c fmap1[b,c,y,x] * fmap2[b,c,y,x'] / sqrt(C);  P_i[n][m] = (P_{i-1}[n][2m] + P_{i-1}[n][2m+1]) / 2, m < W_i
+ *   out[b, i*(2r+1)+k, y, x] = (1 - 2^-(i+1)) * lerp0(P_i[n][:], ((x - disp[n]) / 2^i + (k - r)) * W_i / (W - 1) - 0.5)
+ *   (linear interpolation, zeros outside the row; both the mixed normalisation and the level weights are the reference's).
+ * pyramid: ONE buffer of N * (W_0 + ... + W_{L-1}) floats; level i is [N][W_i] contiguous at float offset N * (W_0 + ... + W_{i-1}).
+ * ts_raft_corr_pyramid_fwd  builds every level in one launch (v_mfma_f32_16x16x4_f32; level 0 is not read back).
+ * ts_raft_corr_lookup_fwd   out [B, L*(2r+1), H, W], one launch.
+ * ts_raft_corr_lookup_bwd   grad_out as out.  grad_disp [B,1,H,W] (needs pyramid) and grad_pyramid are OVERWRITTEN; either may be
+ *                           NULL, not both.  fold != 0: grad_pyramid is G [N][W], the cotangent of level 0 with levels 1..L-1
+ *                           folded in by the pooling's own backward (what ts_raft_corr_pyramid_bwd takes with levels = 1);
+ *                           fold == 0: grad_pyramid has the pyramid's layout, every level written.  No atomics: bit-reproducible.
+ * ts_raft_corr_pyramid_bwd  grad_pyramid with `levels` levels (1: a folded G).  grad_fmap1 = G fmap2^T / sqrt(C) and grad_fmap2 =
+ *                           G^T fmap1^T / sqrt(C) per image row, OVERWRITTEN; either may be NULL, not both.  Deterministic.
+ * Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, W < 2, num_levels < 1, radius < 0, W >> (num_levels - 1) < 1 --
+ * the reference's avg_pool2d raises there), num_levels > 7 or radius > 1024 (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL).
+ * ---------------------------------------------------------------------------------------- */
+int ts_raft_corr_pyramid_fwd(const float* fmap1, const float* fmap2, float* pyramid, int B, int C, int H, int W, int num_levels,
+                             void* stream);
+int ts_raft_corr_lookup_fwd(const float* pyramid, const float* disp, float* out, int B, int H, int W, int num_levels, int radius,
+                            void* stream);
+int ts_raft_corr_lookup_bwd(const float* pyramid, const float* disp, const float* grad_out, float* grad_disp, float* grad_pyramid,
+                            int B, int H, int W, int num_levels, int radius, int fold, void* stream);
+int ts_raft_corr_pyramid_bwd(const float* grad_pyramid, const float* fmap1, const float* fmap2, float* grad_fmap1, float* grad_fmap2,
+                             int B, int C, int H, int W, int levels, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

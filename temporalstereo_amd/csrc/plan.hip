@@ -104,6 +104,8 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_block_cost_sampled_corr_split_fwd), TS_PLAN_OP(ts_conv3d_hw_split_fwd),
     TS_PLAN_OP(ts_conv3d_d_split_fwd),      TS_PLAN_OP(ts_conv3d_hw_x6_split_fwd),
     TS_PLAN_OP(ts_inverse_warp_fwd),        TS_PLAN_OP(ts_inverse_warp_bwd),
+    TS_PLAN_OP(ts_raft_corr_pyramid_fwd),   TS_PLAN_OP(ts_raft_corr_lookup_fwd),
+    TS_PLAN_OP(ts_raft_corr_lookup_bwd),    TS_PLAN_OP(ts_raft_corr_pyramid_bwd),
 };
 
 struct Call {

@@ -2108,3 +2108,220 @@ def inverse_warp(img, motion, mode='disparity', K=None, inv_K=None, T_target_to_
         output = {'homo_points_3d': res[5], 'triangular_depth': res[1], 'flow_mask': res[4], 'src_pixel_coord': res[2],
                   'optical_flow': res[3]}
     return res[0], output
+
+
+# ----------------------------------------------------------------------------------- CorrBlock: the RAFT-Stereo correlation pyramid
+_RAFT_MAX_LEVELS = 7
+
+
+def _raft_level_widths(W, num_levels):
+    return [W >> i for i in range(num_levels)]
+
+
+def _raft_check_levels(W, num_levels):
+    if num_levels < 1:
+        raise ValueError("raft_corr: num_levels must be >= 1, got %d" % num_levels)
+    if num_levels > _RAFT_MAX_LEVELS:
+        raise ValueError("raft_corr: num_levels = %d, the HIP kernel pools at most %d levels" % (num_levels, _RAFT_MAX_LEVELS))
+    if W < 2:
+        raise ValueError("raft_corr: W = %d, need W >= 2 (the lookup divides by W - 1)" % W)
+    if (W >> (num_levels - 1)) < 1:
+        raise ValueError("raft_corr: W = %d is too narrow for num_levels = %d (level %d would be empty; the reference's "
+                         "avg_pool2d raises there)" % (W, num_levels, num_levels - 1))
+
+
+def raft_corr_level_views(pyramid, B, H, W, num_levels):
+    """The levels of a pyramid buffer as the reference's `corr_pyramid` entries: [B*H*W, 1, 1, W >> i] views (no copies)."""
+    N, views, o = B * H * W, [], 0
+    for Wi in _raft_level_widths(W, num_levels):
+        views.append(pyramid[o:o + N * Wi].view(N, 1, 1, Wi))
+        o += N * Wi
+    return views
+
+
+def _raft_levels_of(pyramid, N, W):
+    """num_levels of a pyramid buffer of N pixels and width W (its length decides: the level widths W >> i are positive)."""
+    if pyramid.dim() != 1 or N <= 0 or pyramid.numel() % N:
+        raise ValueError("raft_corr_lookup: pyramid must be the 1-D buffer of raft_corr_pyramid for %d pixels, got %s" % (N, tuple(pyramid.shape)))
+    per, s = pyramid.numel() // N, 0
+    for L in range(1, _RAFT_MAX_LEVELS + 1):
+        s += W >> (L - 1)
+        if s == per and (W >> (L - 1)) >= 1:
+            return L
+    raise ValueError("raft_corr_lookup: a pyramid of %d floats per pixel is no pyramid of width %d" % (per, W))
+
+
+class _RaftCorrPyramid(torch.autograd.Function):
+    """ts_raft_corr_pyramid_fwd / ts_raft_corr_pyramid_bwd (the cotangent keeps its levels: folded while it is staged)."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, num_levels):
+        B, C, H, W = fmap1.shape
+        pyr = torch.empty(B * H * W * sum(_raft_level_widths(W, num_levels)), device=fmap1.device, dtype=torch.float32)
+        p = _lib.ptr
+        _lib.check(_lib.lib().ts_raft_corr_pyramid_fwd(p(fmap1), p(fmap2), p(pyr), B, C, H, W, num_levels, _stream()),
+                   "ts_raft_corr_pyramid_fwd")
+        ctx.save_for_backward(fmap1, fmap2)
+        ctx.num_levels = num_levels
+        return pyr
+
+    @staticmethod
+    def backward(ctx, g):
+        fmap1, fmap2 = ctx.saved_tensors
+        B, C, H, W = fmap1.shape
+        g1 = torch.empty_like(fmap1) if ctx.needs_input_grad[0] else None
+        g2 = torch.empty_like(fmap2) if ctx.needs_input_grad[1] else None
+        if g1 is None and g2 is None:
+            return None, None, None
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        _lib.check(_lib.lib().ts_raft_corr_pyramid_bwd(p(g), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, ctx.num_levels, _stream()),
+                   "ts_raft_corr_pyramid_bwd")
+        return g1, g2, None
+
+
+def _raft_lookup_fwd(pyramid, disp, num_levels, radius):
+    B, _, H, W = disp.shape
+    out = torch.empty((B, num_levels * (2 * radius + 1), H, W), device=disp.device, dtype=torch.float32)
+    p = _lib.ptr
+    _lib.check(_lib.lib().ts_raft_corr_lookup_fwd(p(pyramid), p(disp), p(out), B, H, W, num_levels, radius, _stream()),
+               "ts_raft_corr_lookup_fwd")
+    return out
+
+
+class _RaftCorrLookup(torch.autograd.Function):
+    """ts_raft_corr_lookup_fwd / ts_raft_corr_lookup_bwd with fold = 0: the gradient with respect to a free pyramid, level by level."""
+
+    @staticmethod
+    def forward(ctx, pyramid, disp, num_levels, radius):
+        ctx.save_for_backward(pyramid, disp)
+        ctx.geom = (num_levels, radius)
+        return _raft_lookup_fwd(pyramid, disp, num_levels, radius)
+
+    @staticmethod
+    def backward(ctx, g):
+        pyramid, disp = ctx.saved_tensors
+        L, r = ctx.geom
+        B, _, H, W = disp.shape
+        gp = torch.empty_like(pyramid) if ctx.needs_input_grad[0] else None
+        gd = torch.empty_like(disp) if ctx.needs_input_grad[1] else None
+        if gp is None and gd is None:
+            return None, None, None, None
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        _lib.check(_lib.lib().ts_raft_corr_lookup_bwd(p(pyramid), p(disp), p(g), p(gd), p(gp), B, H, W, L, r, 0, _stream()),
+                   "ts_raft_corr_lookup_bwd")
+        return gp, gd, None, None
+
+
+class _RaftCorrBlockLookup(torch.autograd.Function):
+    """The lookup of a CorrBlock, differentiable in the FEATURES the pyramid was built from: backward is ts_raft_corr_lookup_bwd
+    with fold = 1 (one [B*H*W, W] cotangent of level 0, written once) and ts_raft_corr_pyramid_bwd on it -- the per-level
+    cotangent of the pyramid is never materialised."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, pyramid, disp, num_levels, radius):
+        ctx.save_for_backward(fmap1, fmap2, pyramid, disp)
+        ctx.geom = (num_levels, radius)
+        return _raft_lookup_fwd(pyramid, disp, num_levels, radius)
+
+    @staticmethod
+    def backward(ctx, g):
+        fmap1, fmap2, pyramid, disp = ctx.saved_tensors
+        L, r = ctx.geom
+        B, C, H, W = fmap1.shape
+        need1, need2, _, needd = ctx.needs_input_grad[:4]
+        if not (need1 or need2 or needd):
+            return (None,) * 6
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        feats = need1 or need2
+        G = torch.empty(B * H * W * W, device=g.device, dtype=torch.float32) if feats else None
+        gd = torch.empty_like(disp) if needd else None
+        _lib.check(_lib.lib().ts_raft_corr_lookup_bwd(p(pyramid), p(disp), p(g), p(gd), p(G), B, H, W, L, r, 1, _stream()),
+                   "ts_raft_corr_lookup_bwd")
+        g1 = torch.empty_like(fmap1) if need1 else None
+        g2 = torch.empty_like(fmap2) if need2 else None
+        if feats:
+            _lib.check(_lib.lib().ts_raft_corr_pyramid_bwd(p(G), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, 1, _stream()),
+                       "ts_raft_corr_pyramid_bwd")
+        return g1, g2, None, gd, None, None
+
+
+def _raft_check_features(fmap1, fmap2, num_levels):
+    if fmap1.dim() != 4 or fmap2.dim() != 4:
+        raise ValueError("raft_corr: fmap1 and fmap2 must be [B,C,H,W], got %s and %s" % (tuple(fmap1.shape), tuple(fmap2.shape)))
+    if fmap1.shape != fmap2.shape:
+        raise ValueError("raft_corr: fmap1 and fmap2 differ in shape (%s and %s)" % (tuple(fmap1.shape), tuple(fmap2.shape)))
+    _raft_check_levels(fmap1.shape[3], int(num_levels))
+    _require_gpu(fmap1, fmap2)
+
+
+def _raft_check_disp(disp, radius):
+    if disp.dim() != 4:
+        raise ValueError("raft_corr: disp must be [B,1,H,W], got %s" % (tuple(disp.shape),))
+    if disp.shape[1] != 1:
+        raise ValueError("raft_corr: disp must have 1 channel, got %d" % disp.shape[1])
+    if radius < 0:
+        raise ValueError("raft_corr: radius must be >= 0, got %d" % radius)
+
+
+def raft_corr_pyramid(fmap1, fmap2, num_levels):
+    """The correlation pyramid of the reference's CorrBlock (aggregation/utils/raft_corr.py:15-22, :55-67) in one launch:
+    level 0 is the all-pairs row correlation sum_c fmap1[b,c,y,x] fmap2[b,c,y,x'] / sqrt(C), level i the average of adjacent
+    pairs of level i-1 along x' (an odd tail is dropped).  Returns ONE 1-D fp32 buffer: level i is [B*H*W, W >> i] contiguous
+    at offset B*H*W * (W + (W >> 1) + ... + (W >> (i-1))) -- `raft_corr_level_views` slices it.  Differentiable in both maps."""
+    _raft_check_features(fmap1, fmap2, num_levels)
+    return _RaftCorrPyramid.apply(_lib.contiguous(fmap1), _lib.contiguous(fmap2), int(num_levels))
+
+
+def raft_corr_lookup(pyramid, disp, radius):
+    """The windowed lookup of the reference's CorrBlock.__call__ (raft_corr.py:24-53) in one launch: out [B, L*(2r+1), H, W],
+    channel i*(2r+1)+k = (1 - 2^-(i+1)) * the linear interpolation (zeros outside) of level i's row of the pixel at
+    ((x - disp) / 2^i + (k - r)) * (W >> i) / (W - 1) - 0.5.  `pyramid` is the buffer of raft_corr_pyramid for the same B, H, W
+    (the number of levels follows from its length).  Differentiable in the pyramid (every level) and in disp."""
+    _raft_check_disp(disp, int(radius))
+    _require_gpu(pyramid, disp)
+    B, _, H, W = disp.shape
+    if W < 2:
+        raise ValueError("raft_corr: W = %d, need W >= 2 (the lookup divides by W - 1)" % W)
+    L = _raft_levels_of(pyramid, B * H * W, W)
+    return _RaftCorrLookup.apply(_lib.contiguous(pyramid), _lib.contiguous(disp), L, int(radius))
+
+
+class CorrBlock:
+    """CorrBlock of the reference (aggregation/utils/raft_corr.py:4-67; same arguments and attributes), for disparity: the
+    all-pairs row correlation of fmap1 and fmap2 [B,C,H,W] as a pyramid of `num_levels` levels (one launch, one buffer), and
+    `__call__(disp)` with disp [B,1,H,W]: the (2*radius+1)-tap bilinear window around x - disp on every level,
+    [B, num_levels*(2*radius+1), H, W].  `corr_pyramid[i]` is the [B*H*W, 1, 1, W >> i] view of level i.
+
+    Gradients reach disp and the two feature maps through `__call__` (the pyramid's per-level cotangent is never materialised:
+    ts_raft_corr_lookup_bwd folds it into one level-0 cotangent, ts_raft_corr_pyramid_bwd contracts that); the `corr_pyramid`
+    views themselves carry no gradient.  No host reads: build and lookup can be captured."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        num_levels, radius = int(num_levels), int(radius)
+        _raft_check_features(fmap1, fmap2, num_levels)
+        if radius < 0:
+            raise ValueError("raft_corr: radius must be >= 0, got %d" % radius)
+        self.num_levels = num_levels
+        self.radius = radius
+        f1, f2 = _lib.contiguous(fmap1), _lib.contiguous(fmap2)
+        with torch.no_grad():
+            self._pyramid = _RaftCorrPyramid.apply(f1, f2, num_levels)
+        self._shape = tuple(fmap1.shape)
+        # the feature maps are kept only where a backward can ask for them (the reference keeps the pyramid alone)
+        self._fmaps = (f1, f2) if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad) else None
+        B, _, H, W = self._shape
+        self.corr_pyramid = raft_corr_level_views(self._pyramid, B, H, W, num_levels)
+
+    def __call__(self, disp):
+        _raft_check_disp(disp, self.radius)
+        _require_gpu(disp)
+        B, _, H, W = self._shape
+        if (disp.shape[0], disp.shape[2], disp.shape[3]) != (B, H, W):
+            raise ValueError("raft_corr: disp %s does not match the feature maps %s" % (tuple(disp.shape), self._shape))
+        disp = _lib.contiguous(disp)
+        if self._fmaps is None:
+            return _RaftCorrLookup.apply(self._pyramid, disp, self.num_levels, self.radius)
+        return _RaftCorrBlockLookup.apply(self._fmaps[0], self._fmaps[1], self._pyramid, disp, self.num_levels, self.radius)

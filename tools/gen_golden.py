@@ -1556,6 +1556,94 @@ def warp_cases(M):
     print("\n".join(lines))
 
 
+def raft_cases(M):
+    """tests/golden/raft_corr_*.npz: the reference's own CorrBlock (aggregation/utils/raft_corr.py:4-67) on the CPU, in fp32 and fp64,
+    forward and backward, on seeded inputs; dev_* = how far its fp32 run lies from its fp64 run."""
+    from architecture.modeling.aggregation.utils.raft_corr import CorrBlock as RefCorrBlock
+    import raft_ref
+    shapes = [("a", 2, 6, 3, 37, 4, 4), ("b", 1, 5, 2, 66, 4, 4), ("c", 1, 40, 1, 8, 4, 1), ("e", 1, 32, 4, 64, 3, 2)]
+    lines = ["raft_corr_*.npz: tools/gen_golden.py --only-raft, numpy %s, torch %s CPU -- the reference's own CorrBlock" % (np.__version__, torch.__version__),
+             "(architecture/modeling/aggregation/utils/raft_corr.py:4-67) built and called on seeded inputs in float32 and in float64,",
+             "with the backward of a seeded cotangent in both.",
+             "Inputs: fmap1, fmap2 N(0,1), kept as their seed (tests/synth.py; raft_ref.load_fixture draws them again); disp uniform in [-0.2 W, 0.7 W]; the cotangent is k / 8 with k an integer in [-8, 8].",
+             "The generator draws the disparity of single pixels again until, in the fp64 evaluation, no position xp of any level or",
+             "tap lies within 1e-3 of an integer and floor(xp) agrees between the fp32 and the fp64 evaluation (the gradient with",
+             "respect to disp has a kink at integer xp), and asserts both; it asserts that 50-95 % of the outputs are non-zero.",
+             "Stored: seed and shape of the feature maps, disp, the float32 output `out`, the float32 pyramid levels `pyr_<i>` [B*H*W, W >> i], the cotangent",
+             "`cot`, the gradients of the float32 run `grad_fmap1`, `grad_fmap2`, `grad_disp`; dev_out and dev_pyr_<i> = max |fp32 run -",
+             "fp64 run| (the output compared in double: tests/raft_ref.py in fp64 stands for the fp64 run's output, which the",
+             "reference casts to float32 at the end; the two agree to that cast, asserted here; the fp64 pyramid levels are the",
+             "reference's own), rel_grad_* = relative L2 of the fp32 run's gradient against the fp64 run's."]
+    total = 0
+    for tag, B, C, H, W, L, r in shapes:
+        rng = np.random.default_rng(synth.SEED0 + 8000 + ord(tag))
+        seed = synth.SEED0 + 8000 + ord(tag)
+        f1, f2 = (T(a) for a in raft_ref.fixture_features(seed, (B, C, H, W)))
+        disp = T(rng.uniform(-0.2, 0.7, size=(B, 1, H, W)) * W).float()
+        cot = T(rng.integers(-8, 9, size=(B, L * (2 * r + 1), H, W)) / 8.0).float()
+
+        def bad_pixels(d):
+            bad = torch.zeros(d.shape, dtype=torch.bool)
+            gap = 1.0
+            for i in range(L):
+                x64 = raft_ref.positions(d.double(), i, r, W >> i)
+                x32 = raft_ref.positions(d, i, r, W >> i)
+                near = (x64 - torch.round(x64)).abs()
+                gap = min(gap, float(near.min()))
+                b = (near < 1e-3) | (torch.floor(x64) != torch.floor(x32.double()))
+                bad |= b.any(dim=-1).unsqueeze(1)
+            return bad, gap
+        redrawn = 0
+        for attempt in range(200):
+            bad, gap = bad_pixels(disp)
+            n = int(bad.sum())
+            if n == 0:
+                break
+            redrawn += n
+            disp[bad] = T(rng.uniform(-0.2, 0.7, size=n) * W).float()
+        bad, gap = bad_pixels(disp)
+        assert int(bad.sum()) == 0 and gap >= 1e-3, (tag, int(bad.sum()), gap)
+
+        def run(dt):
+            a, b_, d = (t.detach().clone().to(dt).requires_grad_(True) for t in (f1, f2, disp))
+            blk = RefCorrBlock(a, b_, num_levels=L, radius=r)
+            o = blk(d)
+            o.backward(cot.to(o.dtype))
+            return o.detach(), [lv.detach() for lv in blk.corr_pyramid], (a.grad, b_.grad, d.grad)
+        o32, p32, g32 = run(torch.float32)
+        o64f, p64, g64 = run(torch.float64)
+        own64 = raft_ref.corr_block(f1.double(), f2.double(), disp.double(), L, r)
+        assert o32.dtype == torch.float32 and o64f.dtype == torch.float32 and tuple(o32.shape) == (B, L * (2 * r + 1), H, W)
+        scale = float(own64.abs().max())
+        assert float((own64 - o64f.double()).abs().max()) <= 2.0 ** -24 * scale, (tag, float((own64 - o64f.double()).abs().max()))
+        nz = float((o32 != 0).float().mean())
+        assert 0.50 <= nz <= 0.95, (tag, nz)
+        own_levels = raft_ref.corr_pyramid(f1.double(), f2.double(), L)
+        arrs = dict(seed=seed, shape=np.array([B, C, H, W]), disp=disp, out=o32, cot=cot, grad_fmap1=g32[0], grad_fmap2=g32[1], grad_disp=g32[2],
+                    num_levels=L, radius=r, dev_out=float((o32.double() - own64).abs().max()))
+        for i in range(L):
+            assert tuple(p32[i].shape) == (B * H * W, 1, 1, W >> i)
+            assert float((own_levels[i].reshape(p64[i].shape) - p64[i]).abs().max()) < 1e-12, (tag, i)
+            arrs["pyr_%d" % i] = p32[i].reshape(B * H * W, W >> i)
+            arrs["dev_pyr_%d" % i] = float((p32[i].double() - p64[i]).abs().max())
+        rels = []
+        for name, a, b_ in zip(("fmap1", "fmap2", "disp"), g32, g64):
+            arrs["rel_grad_" + name] = float((a.double() - b_).norm() / b_.norm())
+            rels.append(arrs["rel_grad_" + name])
+        save("raft_corr_" + tag, **arrs)
+        size = os.path.getsize(os.path.join(OUT, "raft_corr_%s.npz" % tag))
+        total += size
+        lines.append("raft_corr_%s  B=%d C=%d H=%d W=%d L=%d r=%d  %.0f %% of the outputs non-zero, %d disparities drawn again, nearest "
+                     "integer %.2e; dev_out %.3g, dev_pyr %.3g .. %.3g, rel_grad fmap1 %.3g fmap2 %.3g disp %.3g; %.0f KB"
+                     % (tag, B, C, H, W, L, r, 100 * nz, redrawn, gap, arrs["dev_out"], min(arrs["dev_pyr_%d" % i] for i in range(L)),
+                        max(arrs["dev_pyr_%d" % i] for i in range(L)), rels[0], rels[1], rels[2], size / 1024))
+    assert total < 400 * 1024, total
+    lines.append("total %.0f KB" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_raft.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -1581,6 +1669,9 @@ def main():
         return
     if "--only-warp" in sys.argv:
         warp_cases(M)
+        return
+    if "--only-raft" in sys.argv:
+        raft_cases(M)
         return
     if "--only-augment" in sys.argv:
         augment_cases(M)

@@ -104,6 +104,13 @@ def main():
         tsec = time_op(lambda: fn(L32, R32, d48), max(a.iters // 4, 20))
         nb = 4 * H * W * (2 * 32 + 48 + ch * 48)
         print("ref-bench %-7s C=32 96x312 D=48     %8.1f us  %7.1f MB  %7.1f GB/s   (reference: %.1f us on a GTX3090)" % (name, tsec * 1e6, nb / 1e6, nb / tsec / 1e9, ref_us))
+    # CorrBlock as the reference times it (raft_corr.py:196-227: build + lookup, num_levels 4, radius 4, disp = randn * 192, no grad)
+    Lr, Rr = torch.randn(1, 32, H, W, device=dev), torch.randn(1, 32, H, W, device=dev)
+    dr = torch.randn(1, 1, H, W, device=dev) * 192
+    with torch.no_grad():
+        tsec = time_op(lambda: ts.CorrBlock(Lr, Rr, num_levels=4, radius=4)(dr), a.iters)
+    nb = 4 * H * W * (W * (2 - 2 ** -3) + 2 * 32 + 1 + 4 * 9)
+    print("ref-bench CorrBlock C=32 96x312 L=4 r=4  %8.1f us  %7.1f MB  %7.1f GB/s   (reference: 1730.1 us on its own GPU)" % (tsec * 1e6, nb / 1e6, nb / tsec / 1e9))
     # the large-tensor stress shape of SURVEY.md section 8(f)-3
     Lb, Rb = torch.rand(4, 32, 136, 240, device=dev), torch.rand(4, 32, 136, 240, device=dev)
     db = torch.linspace(0, 47, 48, device=dev).view(1, 48, 1, 1).expand(4, 48, 136, 240).contiguous()
