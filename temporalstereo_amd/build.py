@@ -34,6 +34,14 @@ def hipcc():
     raise RuntimeError("hipcc not found")
 
 
+def compile_cmd(src, obj, extra=()):
+    """The hipcc line that compiles one csrc/*.hip into an object: the project's flags, then `extra`, then TS_HIPCC_FLAGS
+    (e.g. TS_HIPCC_FLAGS=-DTS_EXACT_SILU python -m temporalstereo_amd.build --force)."""
+    return [hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,
+            "-Wall", "-Wno-unused-function", "-ffp-contract=on", "-munsafe-fp-atomics", "-fno-slp-vectorize"] + \
+        list(extra) + os.environ.get("TS_HIPCC_FLAGS", "").split()
+
+
 def build(force=False, verbose=True):
     """Compile every csrc/*.hip into one shared library.  Returns its path."""
     if not force and not _stale():
@@ -44,9 +52,7 @@ def build(force=False, verbose=True):
     for src in sources():
         obj = os.path.join(HERE, "build", os.path.basename(src) + ".o")
         objs.append(obj)
-        cmd = [hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", obj,
-               "-Wall", "-Wno-unused-function", "-ffp-contract=on", "-munsafe-fp-atomics", "-fno-slp-vectorize"]
-        cmd += os.environ.get("TS_HIPCC_FLAGS", "").split()     # e.g. TS_HIPCC_FLAGS=-DTS_EXACT_SILU python -m temporalstereo_amd.build --force
+        cmd = compile_cmd(src, obj)
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -501,7 +501,7 @@ bool bn_vec(const void* a, const void* b, const void* c, long long N, long long 
 }
 
 bool bn_small(int B, long long N) {
-  if (g_bn_small_elems < 0) { const char* e = getenv("TS_BN_SMALL_ELEMS"); g_bn_small_elems = e ? atoll(e) : kSmallElems; }
+  if (g_bn_small_elems < 0) g_bn_small_elems = ts::env_ll("TS_BN_SMALL_ELEMS", kSmallElems);
   return static_cast<long long>(B) * N <= g_bn_small_elems;
 }
 

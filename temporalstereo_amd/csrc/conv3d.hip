@@ -1330,9 +1330,9 @@ wgrad_finish_many(const WgradFinishDesc* __restrict__ table, int n) {
 // a tail of 16 (120 us; 23 x 22 = 506: 94 us), and the Cout <= 16 first layers of the sampled levels (40 KB: three fit) two per CU
 // (304 -> 8 on 5 x 136 x 240: 262 -> 214 us with three).  Layers whose workgroups fit once per CU keep two rounds.
 // TS_WGRAD_GROUPS_PER_CU > 0 forces the old rule with that many per CU.
+const long long g_wgrad_per_cu = ts::env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
 int wgrad_groups(int ciblocks, size_t lds_bytes) {
-  static const long long per_cu_env = ts::env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
-  if (per_cu_env > 0) return (static_cast<int>(per_cu_env) * ts::kNumCU + ciblocks - 1) / ciblocks;
+  if (g_wgrad_per_cu > 0) return (static_cast<int>(g_wgrad_per_cu) * ts::kNumCU + ciblocks - 1) / ciblocks;
   int fit = static_cast<int>((160 * 1024) / (lds_bytes ? lds_bytes : 1));
   fit = fit < 1 ? 1 : (fit > 4 ? 4 : fit);
   const int target = (fit >= 2 ? fit : 2) * ts::kNumCU;
@@ -1340,8 +1340,7 @@ int wgrad_groups(int ciblocks, size_t lds_bytes) {
   return g < 1 ? 1 : g;
 }
 int wgrad_groups_max(int ciblocks) {      // what the workspace is sized for
-  static const long long per_cu_env = ts::env_ll("TS_WGRAD_GROUPS_PER_CU", 0);
-  const int per_cu = per_cu_env > 4 ? static_cast<int>(per_cu_env) : 4;
+  const int per_cu = g_wgrad_per_cu > 4 ? static_cast<int>(g_wgrad_per_cu) : 4;
   return (per_cu * ts::kNumCU + ciblocks - 1) / ciblocks;
 }
 

@@ -41,6 +41,27 @@ constexpr int XP_WBUF = XP_WROWS * 32;    // 16-byte units per weight buffer
 constexpr int XP_GSLOTS = 10;             // tap slots of the GLOBAL weight layout (slot 9: zeros, not fetched)
 constexpr int XP_MAXC = 512;              // widest layer (ts_conv3d_hw_x6_supported)
 
+#ifdef TS_X6P_LAB      // the laboratory the kernel was developed with (tools/exp/x6p_trace.py, x6p_wgtimes.py, x6p_abl.py): in a -DTS_X6P_LAB build only
+struct XPLab {
+  unsigned long long *trc, *wgt;        // TS_X6P_TRACE=<workgroup id>: cycle stamps of the first wave of each half of that workgroup, its first tiles | =-2: start / end of EVERY one
+  int dbg, ntr = 0;                     // TS_X6P_DBG, phase ablation: 1 no input fetch, 2 no matrix loop, 4 no commit, 8 no output stores, 16 no weight DMA
+  __device__ XPLab(const ts::X6P& p, int g, int half, int tid) : trc((p.trace && g == p.trace_wg && tid == 0) ? p.trace + half * 256 : nullptr),
+        wgt((p.trace && p.trace_wg == -2 && half == 0 && tid == 0 && g < 8000) ? p.trace + 512 + 4 * g : nullptr), dbg(p.dbg) {}
+  __device__ bool skip(int bit) const { return dbg & bit; }
+  __device__ void stamp() { if (trc && ntr < 250) trc[ntr] = __builtin_amdgcn_s_memtime(); ++ntr; }
+  __device__ void begin() { if (wgt) { wgt[0] = __builtin_amdgcn_s_memtime(); wgt[3] = __builtin_amdgcn_s_memrealtime(); } }
+  __device__ void end() { if (wgt) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); wgt[1] = __builtin_amdgcn_s_memtime(); wgt[2] = __builtin_amdgcn_s_memrealtime(); } }
+  template <int N> __device__ void pin(const f32x16 (&acc)[N]) { if (trc) asm volatile("s_nop 0" :: "v"(acc[0][0]), "v"(acc[N - 1][15])); }      // live up to the stamp
+};
+#else                  // the product build: a stand-in of constexpr no-ops -- nothing of the lab reaches its kernel, and ts::X6P has no field for it
+struct XPLab {
+  __device__ constexpr XPLab(const ts::X6P&, int, int, int) {}
+  __device__ static constexpr bool skip(int) { return false; }
+  __device__ static constexpr void stamp() {}   __device__ static constexpr void begin() {}   __device__ static constexpr void end() {}
+  template <int N> __device__ static constexpr void pin(const f32x16 (&)[N]) {}
+};
+#endif
+
 __device__ __forceinline__ void phase_barrier() {
   // LDS writes / reads of this wave are done (lgkmcnt), then the workgroup barrier.  NOT __syncthreads(): with an LDS-DMA or the next
   // chunk's fetch in flight its fence would drain vmcnt too.
@@ -137,17 +158,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
   const __amdgpu_buffer_rsrc_t wr = ig_rsrc(w6, p.w_bytes);
   const unsigned wchunk_b = static_cast<unsigned>(3 * XP_GSLOTS * 2 * p.coutp) * 16u;
 
-  // experiment: cycle stamps of the first wave of each half of ONE workgroup (TS_X6P_TRACE=<workgroup id>), its first tiles
-  unsigned long long* trc = (p.trace && g == p.trace_wg && (tid == 0)) ? p.trace + half * 256 : nullptr;
-  int ntr = 0;
-  auto stamp = [&]() {
-    if (trc && ntr < 250) trc[ntr] = __builtin_amdgcn_s_memtime();
-    ++ntr;
-  };
-  stamp();
-  // experiment (TS_X6P_TRACE=-2): start / end stamp of EVERY workgroup
-  unsigned long long* wgt = (p.trace && p.trace_wg == -2 && threadIdx.x == 0 && g < 8000) ? p.trace + 512 + 4 * g : nullptr;
-  if (wgt) { wgt[0] = __builtin_amdgcn_s_memtime(); wgt[3] = __builtin_amdgcn_s_memrealtime(); }
+  XPLab lab(p, g, half, tid); lab.stamp(); lab.begin();
 
   // the tile whose chunks are being FETCHED (one step ahead of the tile being multiplied)
   // (split input: the second base behind a descriptor of its own, sized to its own allocation; a halo offset is kOOB for both)
@@ -167,7 +178,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
     for (int e = 0; e < NCH; ++e) {
       // channels past Cin re-read the last real one; their weights are zero
       const unsigned co = static_cast<unsigned>(min(c * XP_NC + sg * 8 + shalf * 4 + e, p.Cin - 1) - cbs.c_first) * cbs.cstride_b;
-      rin[e] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(cbs.rsrc, (goff == kOOB || (p.dbg & 1)) ? kOOB : goff + co, 0, 0));
+      rin[e] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(cbs.rsrc, (goff == kOOB || lab.skip(1)) ? kOOB : goff + co, 0, 0));
     }
   };
   // weight DMA: instruction i (0..26) = (part, tap) = (i / 9, i % 9), its 64 lanes = (group, co); wave w of half 1 issues i = w, w + 4, ...
@@ -175,7 +186,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
   auto dma_weights = [&](int c, int co0, int buf, int share) {
     u32x4* dst = wls + buf * XP_WBUF;
     const unsigned cbase = static_cast<unsigned>(c) * wchunk_b;
-    const bool lane_ok = co0 + px < p.coutp && !(p.dbg & 16);
+    const bool lane_ok = co0 + px < p.coutp && !lab.skip(16);
 #pragma unroll
     for (int q = 0; q < 7; ++q) {
       const int i = share < 0 ? wave + 4 * q : 2 * (wave + 4 * q) + share;
@@ -188,7 +199,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
     }
   };
   auto commit = [&]() {
-    if (stager && !(p.dbg & 4)) {
+    if (stager && !lab.skip(4)) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         unsigned part[3][NCH / 2];
@@ -225,7 +236,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
   // other half multiplies.  scale / shift were copied to LDS when the workgroup started.
   constexpr int EPITCH = NPB * 32 + 4;
   float* scr = reinterpret_cast<float*>(ldsp + G::TILE0 + 2 * G::HALF_U) + (threadIdx.x >> 6) * (8 * EPITCH);
-  const float* ss = reinterpret_cast<const float*>(ldsp + G::TILE0 + 2 * G::HALF_U) + 8 * 8 * EPITCH;
+  float* ss = reinterpret_cast<float*>(ldsp + G::TILE0 + 2 * G::HALF_U) + 8 * 8 * EPITCH;
   auto epilogue = [&](const XPTile& t) {
     // split-K (p.ksplit > 1): the slice's RAW sums go to the workspace, [slice][batch][channel][plane]; conv_splitk_finish (conv3d.hip)
     // adds the slices in a fixed order and applies addend / scale / shift / activation
@@ -280,7 +291,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
         const v4f val = *reinterpret_cast<const v4f*>(scr + c8 * EPITCH + q * 4);
         const int oy = t.ty0 + wave * NPB + (q >> 3), ox = t.tx0 + (q & 7) * 4;
         const int co = t.co0 + 8 * k + c8;
-        const unsigned off = (oy < p.H && ox < p.W && co < p.Cout && !(p.dbg & 8))
+        const unsigned off = (oy < p.H && ox < p.W && co < p.Cout && !lab.skip(8))
             ? (obase + static_cast<unsigned>(oy) * p.W + ox) * 4u + static_cast<unsigned>(co) * ocs : kOOB;
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), yr, off, 0, 0);
       }
@@ -295,13 +306,10 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
   //   fetches issued after it), read from phase 2s + 3 on (half 0's compute(s + 1)).  Step 0 goes out in half 1's idle phase.
   // (a step = one chunk of one tile; steps run through the workgroup's tiles without a seam)
   if (first >= band1) return;
-  {
-    float* ssw = reinterpret_cast<float*>(ldsp + G::TILE0 + 2 * G::HALF_U) + 8 * 8 * EPITCH;
-    for (int i = threadIdx.x; i < p.coutp; i += 512) {
-      ssw[i] = scale ? scale[i] : 1.f;
-      ssw[XP_MAXC + i] = shift ? shift[i] : 0.f;
-    }
-  }                           // (the whole workgroup: an XCD's band can be shorter than its workgroup count)
+  for (int i = threadIdx.x; i < p.coutp; i += 512) {      // (the whole workgroup: an XCD's band can be shorter than its workgroup count)
+    ss[i] = scale ? scale[i] : 1.f;
+    ss[XP_MAXC + i] = shift ? shift[i] : 0.f;
+  }
   XPTile cur = tile_at(first);
   aim(cur);
   fetch(cur.c0);
@@ -312,7 +320,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     phase_barrier();                                    // half 1 runs one phase behind
   }
-  stamp();
+  lab.stamp();
   int wcur = 0, wnext = 1;                              // weight buffers of this step and the next (rotating through NWB)
   for (int L = first; L < band1; L += step) {
     const bool more = L + step < band1;
@@ -324,15 +332,12 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
     for (int c = cur.c0; c < cur.c1; ++c, wcur = wnext, wnext = (wnext + 1 == NWB ? 0 : wnext + 1)) {
       const bool last = c + 1 == cur.c1;
       // ---- stage: the fetched registers have landed; split and commit
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      stamp();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); lab.stamp();
       if ((NWB == 3 || half == 1) && (!last || more))
         dma_weights(last ? nxt.c0 : c + 1, last ? nxt.co0 : cur.co0, wnext, NWB == 3 ? half : -1);
       commit();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stamp();
-      phase_barrier();
-      stamp();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); lab.stamp();
+      phase_barrier(); lab.stamp();
       // ---- compute
       if (!last) fetch(c + 1);
       else if (more) { aim(nxt); fetch(nxt.c0); }
@@ -353,7 +358,7 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
           for (int pb = 0; pb < NPB; ++pb) bf[buf][OB[k]][pb] = __builtin_bit_cast(bf16x8, in6[OB[k] * 2 * NPIX + rbase[(pb + tap / 3) & 1][tap % 3] + ((pb + tap / 3) >> 1) * 80]);
         }
       };
-      if (!(p.dbg & 2)) {
+      if (!lab.skip(2)) {
         load_frag(0, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 3 + 3 * NPB, 0);
 #pragma unroll
@@ -393,18 +398,15 @@ ig_conv_x6p_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
           for (int k = 1; k < CH; ++k) v += part[pb * CH + k][r];
           acc[pb][r] += v;
         }
-      if (trc) asm volatile("s_nop 0" :: "v"(acc[0][0]), "v"(acc[NPB - 1][15]));
-      stamp();
+      lab.pin(acc); lab.stamp();
       // the next step's weights (this half's share of them) are in LDS: everything but the fetches issued after them has landed
       if (NWB == 3 || half == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NCH) : "memory");
-      phase_barrier();
-      stamp();
+      phase_barrier(); lab.stamp();
     }
-    epilogue(cur);
-    stamp();
+    epilogue(cur); lab.stamp();
     cur = nxt;
   }
-  if (wgt) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); wgt[1] = __builtin_amdgcn_s_memtime(); wgt[2] = __builtin_amdgcn_s_memrealtime(); }
+  lab.end();
   if (half == 0) phase_barrier();                       // both halves pass the same number of barriers
 }
 
@@ -422,9 +424,6 @@ int launch_x6p(const float* x, const void* w6, const float* scale, const float* 
 }  // namespace
 
 namespace ts {
-
-static unsigned long long* trace_buf = nullptr;
-constexpr size_t kTraceBytes = 4096 + 8000 * 32;
 
 static long long tiles_of(const X6P& p, int hr) {
   return static_cast<long long>((p.H + 2 * hr - 1) / (2 * hr)) * ((p.W + 31) / 32) * p.D * p.B * ((p.Cout + 31) / 32) * (p.ksplit > 1 ? p.ksplit : 1);
@@ -444,13 +443,21 @@ int x6p_rows(const X6P& p) {
 // 8 x 32 work items of the layer, slices included (the caller's threshold between this kernel and ig_conv_x6_kernel)
 long long x6p_grid(const X6P& p) { return tiles_of(p, 4); }
 
+#ifdef TS_X6P_LAB      // the stamps (2 halves x 256, then 4 per workgroup) to the host.  Not in the ABI header, and it synchronises: the product library has neither
+static unsigned long long* x6p_trace_buf = nullptr; constexpr size_t kX6PTraceBytes = 4096 + 8000 * 32;
+extern "C" int ts_x6p_trace_read(unsigned long long* host) {
+  if (!x6p_trace_buf) return -1;
+  (void)hipDeviceSynchronize();
+  return static_cast<int>(hipMemcpy(host, x6p_trace_buf, kX6PTraceBytes, hipMemcpyDeviceToHost));
+}
+#endif
 int x6p_launch(const float* x, const void* w6, const float* scale, const float* shift, float* y, X6P p, void* stream) {
   const int hr = x6p_rows(p);
-  static const long long dbg = ts::env_ll("TS_X6P_DBG", 0);
-  p.dbg = static_cast<int>(dbg);
-  static const long long trace_wg = ts::env_ll("TS_X6P_TRACE", -1);
-  if (trace_wg != -1 && !trace_buf) { (void)hipMalloc(reinterpret_cast<void**>(&trace_buf), kTraceBytes); (void)hipMemset(trace_buf, 0, kTraceBytes); }
-  p.trace = trace_buf; p.trace_wg = static_cast<int>(trace_wg);
+#ifdef TS_X6P_LAB
+  static const long long dbg = ts::env_ll("TS_X6P_DBG", 0), trace_wg = ts::env_ll("TS_X6P_TRACE", -1);
+  if (trace_wg != -1 && !x6p_trace_buf) { (void)hipMalloc(reinterpret_cast<void**>(&x6p_trace_buf), kX6PTraceBytes); (void)hipMemset(x6p_trace_buf, 0, kX6PTraceBytes); }
+  p.dbg = static_cast<int>(dbg); p.trace = x6p_trace_buf; p.trace_wg = static_cast<int>(trace_wg);
+#endif
   p.tiles_x = (p.W + 31) / 32;
   p.co_groups = (p.Cout + 31) / 32;
   p.tiles_pp = ((p.H + 2 * hr - 1) / (2 * hr)) * p.tiles_x;
@@ -482,10 +489,3 @@ int x6p_launch(const float* x, const void* w6, const float* scale, const float* 
 }
 
 }  // namespace ts
-
-// experiment (tools/exp/x6p_trace.py): the cycle stamps of the traced workgroup, 2 halves x 256, to the host; not part of the ABI header
-extern "C" int ts_x6p_trace_read(unsigned long long* host) {
-  if (!ts::trace_buf) return -1;
-  (void)hipDeviceSynchronize();
-  return static_cast<int>(hipMemcpy(host, ts::trace_buf, ts::kTraceBytes, hipMemcpyDeviceToHost));
-}

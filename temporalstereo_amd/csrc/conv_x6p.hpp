@@ -21,9 +21,9 @@ struct X6P {
   int csplit;
   long long in2_bstride, in2_cstride;
   unsigned in2_bytes;
-  int dbg;                      // experiment switches (TS_X6P_DBG; 0 in production)
-  unsigned long long* trace;    // experiment: cycle stamps of workgroup trace_wg (TS_X6P_TRACE), else null
-  int trace_wg;
+#ifdef TS_X6P_LAB               // lab build only (XPLab, conv_x6p.hip): TS_X6P_DBG bits; cycle stamps of workgroup trace_wg (TS_X6P_TRACE), else null
+  int dbg; unsigned long long* trace; int trace_wg;
+#endif
 };
 
 // workgroups the launch would have (the caller's choice between this kernel and ig_conv_x6_kernel)

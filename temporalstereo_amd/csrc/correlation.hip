@@ -276,7 +276,7 @@ extern "C" int ts_correlation_fwd(const float* left, const float* right, float* 
     // fewer, fatter workgroups lose more to the tail than the prefetch wins)
     const long long strips_all = static_cast<long long>((W + CX - 1) / CX) * H * B;
     int rpw = strips_all >= 8ll * 3 * ts::kNumCU ? 2 : 1;
-    static const int rpw_env = getenv("TS_CORR_ROWS") ? atoi(getenv("TS_CORR_ROWS")) : 0;
+    static const int rpw_env = static_cast<int>(ts::env_ll("TS_CORR_ROWS", 0));
     if (rpw_env > 0) rpw = rpw_env;
     const dim3 grid((W + CX - 1) / CX, (H + rpw - 1) / rpw, B);
     hipStream_t st = ts::as_stream(stream);

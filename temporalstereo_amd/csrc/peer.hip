@@ -98,8 +98,8 @@ peer_exchange_kernel(const PeerCtx ctx, const float* src, float* dst, int n, con
 unsigned long long g_timeout_ticks = 0;
 unsigned long long timeout_ticks() {
   if (g_timeout_ticks == 0) {
-    long long ms = 120000;
-    if (const char* e = getenv("TS_PEER_TIMEOUT_MS")) { const long long v = atoll(e); if (v > 0) ms = v; }
+    long long ms = ts::env_ll("TS_PEER_TIMEOUT_MS", 0);
+    if (ms <= 0) ms = 120000;
     g_timeout_ticks = static_cast<unsigned long long>(ms) * 100000ull;
   }
   return g_timeout_ticks;

@@ -1,8 +1,9 @@
-"""CPU: libts_hip.so builds, loads, and exports every symbol include/ts_hip.h declares
+"""CPU: libts_hip.so builds, loads, and exports every symbol include/ts_hip.h declares and no other ts_ symbol
 (no compute calls -- there is no GPU here)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -27,6 +28,34 @@ def test_header_symbols_exported(built_lib):
     assert len(syms) >= 8
     for name in syms:
         assert hasattr(handle, name), "libts_hip.so does not export %s" % name
+
+
+def defined_ts_symbols(path):
+    """The ts_-prefixed dynamic symbols an object or shared library defines (binutils nm)."""
+    out = subprocess.run(["nm", "-D" if path.endswith(".so") else "-g", "--defined-only", path],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, check=True).stdout
+    return set(l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("ts_"))
+
+
+def test_exported_symbols_are_the_header(built_lib):
+    """The converse of the test above: the library exports nothing under ts_ that include/ts_hip.h does not declare."""
+    exported, declared = defined_ts_symbols(built_lib), set(declared_symbols())
+    assert exported == declared, (
+        "libts_hip.so and include/ts_hip.h disagree: exported but not declared %s, declared but not exported %s.  A library built with "
+        "-DTS_X6P_LAB (the lab build of csrc/conv_x6p.hip, which adds ts_x6p_trace_read) is expected to fail here: rebuild it with "
+        "`python -m temporalstereo_amd.build --force`" % (sorted(exported - declared), sorted(declared - exported)))
+
+
+def test_lab_build_of_conv_x6p_compiles(tmp_path):
+    """-DTS_X6P_LAB (trace stamps and phase ablation in ig_conv_x6p_kernel, for tools/exp/x6p_trace.py, x6p_wgtimes.py and x6p_abl.py) is
+    not what ships, so nothing else compiles it: this keeps it compiling.  One file with the build's own command, into a temporary
+    directory -- libts_hip.so and temporalstereo_amd/build/ are not touched."""
+    from temporalstereo_amd import build
+    obj = str(tmp_path / "conv_x6p.lab.o")
+    cmd = build.compile_cmd(os.path.join(build.CSRC, "conv_x6p.hip"), obj, extra=["-DTS_X6P_LAB"])
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, "hipcc failed for the lab build:\n%s" % p.stdout[-4000:]
+    assert "ts_x6p_trace_read" in defined_ts_symbols(obj)
 
 
 def test_python_signature_table_matches_header(built_lib):

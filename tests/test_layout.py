@@ -54,3 +54,18 @@ def test_bench_lines_fit_120_columns():
         with open(path) as f:
             long = [(n, len(line.rstrip("\n"))) for n, line in enumerate(f, 1) if len(line.rstrip("\n")) > 120]
         assert not long, "%s: lines over 120 columns: %s" % (os.path.relpath(path, root), long[:5])
+
+
+def test_environment_switch_table_lists_every_variable_the_product_reads():
+    """INTEGRATION.md, "Environment switches": one row per TS_* environment variable read by temporalstereo_amd/**/*.py or csrc/* --
+    no read without a row, no row without a read, and the lab build's two variables marked as such (names only are compared)."""
+    read = set()
+    site = re.compile(r'(?:env_ll|env_not_zero|getenv|environ\.get)\(\s*"(TS_[A-Z0-9_]+)"')
+    for path in _sources(PKG, (".py", ".hip", ".hpp")):
+        read.update(site.findall(open(path).read()))
+    assert len(read) >= 40, sorted(read)
+    section = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("Environment switches\n", 1)[1]
+    section = re.split(r"^## ", section, flags=re.M)[0]
+    rows = dict(re.findall(r"^\| `(TS_[A-Z0-9_]+)` \|(.*)$", section, re.M))
+    assert set(rows) == read, "read but not in the table: %s; in the table but not read: %s" % (sorted(read - set(rows)), sorted(set(rows) - read))
+    assert sorted(n for n, rest in rows.items() if "lab build only" in rest) == ["TS_X6P_DBG", "TS_X6P_TRACE"]

@@ -1,6 +1,9 @@
 """Experiment: phase ablation of ig_conv_x6p_kernel through TS_X6P_DBG (1 no input fetch, 2 no matrix loop, 4 no commit, 8 no output stores, 16 no weight DMA)."""
-import os, subprocess, sys
+import ctypes, os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from temporalstereo_amd import _lib
+if not hasattr(ctypes.CDLL(_lib.LIB_PATH), "ts_x6p_trace_read"):       # the lab build's marker: without it every row would time the complete kernel
+    sys.exit(os.path.basename(__file__) + " needs the lab build: TS_HIPCC_FLAGS=-DTS_X6P_LAB python -m temporalstereo_amd.build --force")
 SHAPES = [("128->32 272x480", 128, 32, 1, 272, 480), ("32->32 272x480", 32, 32, 1, 272, 480), ("64->64 136x240", 64, 64, 1, 136, 240)]
 if "--child" in sys.argv:
     import torch

@@ -5,6 +5,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import numpy as np
 import torch
 from temporalstereo_amd import _lib
+if not hasattr(ctypes.CDLL(_lib.LIB_PATH), "ts_x6p_trace_read"):       # the lab build's marker: without it nothing stamps
+    sys.exit(os.path.basename(__file__) + " needs the lab build: TS_HIPCC_FLAGS=-DTS_X6P_LAB python -m temporalstereo_amd.build --force")
 from temporalstereo_amd.aggregation import native as N
 
 N._X6_MIN_GRID = 1
