@@ -478,6 +478,37 @@ int ts_raft_corr_lookup_bwd(const float* pyramid, const float* disp, const float
 int ts_raft_corr_pyramid_bwd(const float* grad_pyramid, const float* fmap1, const float* fmap2, float* grad_fmap1, float* grad_fmap2,
                              int B, int C, int H, int W, int levels, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FlowCorrBlock: the RAFT all-pairs correlation pyramid for optical flow and its windowed lookup (ABI 16).
+ * Replaces FlowCorrBlock + bilinear_sampler  architecture/modeling/aggregation/utils/raft_corr.py:71-160.  fmap1, fmap2 [B,C,H,W],
+ * coords [B,2,H,W] (channel 0 = x, 1 = y, level-0 scale); N = H*W, n / m number the pixels of frame 1 / frame 2 row-major,
+ * H_i = H >> i, W_i = W >> i, K = 2r + 1.
+ *   P_0[b,n,m] = (f1_n.f1_m - 2 f1_n.f2_m + f2_n.f2_m) / sqrt(C)   (the reference's full Gram matrices; = (f1_n.D_m - D_n.f2_m) / sqrt(C),
+ *   D = f1 - f2, which is how it is evaluated);  P_i[b,n] = avg_pool2d(P_{i-1}[b,n] as an H_{i-1} x W_{i-1} image, 2, 2)
+ *   out[b, i*K*K + a*K + bb, y, x] = bilinear(P_i[b,n], x_t / 2^i + (a - r), y_t / 2^i + (bb - r)), zeros outside: the FIRST window
+ *   index moves x (the reference's meshgrid(dy, dx)); the position takes bilinear_sampler's and grid_sample's fp32 steps in order.
+ * pyramid: ONE buffer; level i is [B*N][H_i*W_i] contiguous at float offset B*N * sum_{l<i} H_l*W_l.
+ * ts_flow_corr_pyramid_fwd  builds every level in one launch (v_mfma_f32_16x16x4_f32; level 0 is not read back).
+ * ts_flow_corr_lookup_fwd   out [B, L*K*K, H, W], one launch.
+ * ts_flow_corr_lookup_bwd   grad_out as out.  grad_coords [B,2,H,W] (needs pyramid) and grad_pyramid are OVERWRITTEN; either may be
+ *                           NULL, not both.  fold != 0: grad_pyramid is G [B*N][N], the cotangent of level 0 with levels 1..L-1
+ *                           folded in by the pooling's own backward (what ts_flow_corr_pyramid_bwd takes with levels = 1);
+ *                           fold == 0: grad_pyramid has the pyramid's layout, every level written.  No atomics: bit-reproducible.
+ * ts_flow_corr_pyramid_bwd  grad_pyramid with `levels` levels (1: a folded G).  Per batch grad_fmap1 = ((G + G^T) f1 - 2 G f2) / sqrt(C),
+ *                           grad_fmap2 = ((G + G^T) f2 - 2 G^T f1) / sqrt(C), OVERWRITTEN; either may be NULL, not both.  Deterministic.
+ * Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, num_levels < 1, radius < 0, a level smaller than 2 x 2 -- the
+ * reference divides by H_i - 1 and W_i - 1), num_levels > 4 or radius > 1024 or a window too large for LDS (TS_ERR_UNSUPPORTED),
+ * then pointers (TS_ERR_NULL).
+ * ---------------------------------------------------------------------------------------- */
+int ts_flow_corr_pyramid_fwd(const float* fmap1, const float* fmap2, float* pyramid, int B, int C, int H, int W, int num_levels,
+                             void* stream);
+int ts_flow_corr_lookup_fwd(const float* pyramid, const float* coords, float* out, int B, int H, int W, int num_levels, int radius,
+                            void* stream);
+int ts_flow_corr_lookup_bwd(const float* pyramid, const float* coords, const float* grad_out, float* grad_coords, float* grad_pyramid,
+                            int B, int H, int W, int num_levels, int radius, int fold, void* stream);
+int ts_flow_corr_pyramid_bwd(const float* grad_pyramid, const float* fmap1, const float* fmap2, float* grad_fmap1, float* grad_fmap2,
+                             int B, int C, int H, int W, int levels, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

@@ -163,6 +163,10 @@ SIGNATURES = {
     "ts_raft_corr_lookup_fwd": (c_int, [c_f32p] * 3 + [c_int] * 5 + [c_ptr]),
     "ts_raft_corr_lookup_bwd": (c_int, [c_f32p] * 5 + [c_int] * 6 + [c_ptr]),
     "ts_raft_corr_pyramid_bwd": (c_int, [c_f32p] * 5 + [c_int] * 5 + [c_ptr]),
+    "ts_flow_corr_pyramid_fwd": (c_int, [c_f32p] * 3 + [c_int] * 5 + [c_ptr]),
+    "ts_flow_corr_lookup_fwd": (c_int, [c_f32p] * 3 + [c_int] * 5 + [c_ptr]),
+    "ts_flow_corr_lookup_bwd": (c_int, [c_f32p] * 5 + [c_int] * 6 + [c_ptr]),
+    "ts_flow_corr_pyramid_bwd": (c_int, [c_f32p] * 5 + [c_int] * 5 + [c_ptr]),
     "ts_reproject_memory_workspace_bytes": (c_size, [c_int] * 5),
     "ts_reproject_memory_fwd": (c_int, [c_f32p, ctypes.c_longlong, c_int, c_int, c_f32p, c_f32p, c_int, c_f32p, c_int, c_int,
                                         c_f32p, c_int, c_f32p, c_f32p, c_f32p, c_float, c_float, c_f32p, c_f32p, c_f32p,

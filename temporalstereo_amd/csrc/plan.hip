@@ -106,6 +106,8 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_inverse_warp_fwd),        TS_PLAN_OP(ts_inverse_warp_bwd),
     TS_PLAN_OP(ts_raft_corr_pyramid_fwd),   TS_PLAN_OP(ts_raft_corr_lookup_fwd),
     TS_PLAN_OP(ts_raft_corr_lookup_bwd),    TS_PLAN_OP(ts_raft_corr_pyramid_bwd),
+    TS_PLAN_OP(ts_flow_corr_pyramid_fwd),   TS_PLAN_OP(ts_flow_corr_lookup_fwd),
+    TS_PLAN_OP(ts_flow_corr_lookup_bwd),    TS_PLAN_OP(ts_flow_corr_pyramid_bwd),
 };
 
 struct Call {

@@ -32,36 +32,24 @@
 //   is staged.
 #include <cmath>
 
-#include "ts_common.hpp"
+#include "corr_common.hpp"
 
 namespace {
 
+using namespace corr;          // v4f, RKC, RPM, kMaxLevels, Levels, pow2_neg, mfma_chunk, store_tile, grid_blocks
+
 constexpr int RT = 64;           // tile edge: pixels x and x' per workgroup
-constexpr int RKC = 32;          // contraction elements per staged chunk
-// LDS pitches.  A 4-byte LDS read or write is served per 32-lane half over banks (address / 4) mod 32; a fragment read has lane
-// (j = lane & 15, kq = lane >> 4), so a half holds j = 0..15 and two values of kq.  Not measured: the bank arithmetic only.
+// LDS pitches by the bank arithmetic of corr_common.hpp (RPM, the pitch of a [64][k] operand image, is there).  Not measured.
 constexpr int RPK = 80;          // pitch of a [k][64] operand image: bank 16 kq + j (80 == 16 mod 32), disjoint within a half
-constexpr int RPM = 34;          // pitch of a [64][k] operand image: bank 2 j + kq (34 == 2 mod 32), disjoint within a half
 constexpr int RPO = 68;          // pitch of the output tile: a store of the accumulators hits bank 16 kq + j (4 * 68 == 16 mod 32)
-constexpr int kMaxLevels = 7;    // 64 >> 6 == 1: the deepest level a 64-wide tile still pools by itself
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-struct Raft {
+struct Raft : Levels {           // off[i]: float offset of level i in the pyramid buffer
   int B, C, H, W, L, r;
-  size_t off[kMaxLevels];        // float offset of level i in the pyramid buffer
 };
 
 void level_offsets(Raft& p) {
-  const size_t N = static_cast<size_t>(p.B) * p.H * p.W;
-  size_t o = 0;
-  for (int i = 0; i < kMaxLevels; ++i) {
-    p.off[i] = o;
-    o += N * static_cast<size_t>(p.W >> i);
-  }
+  corr::level_offsets(p, static_cast<size_t>(p.B) * p.H * p.W, [&](int i) { return p.W >> i; });
 }
-
-__device__ __forceinline__ float pow2_neg(int i) { return __int_as_float((127 - i) << 23); }      // 2^-i, exact
 
 // Position of tap k of level i in the level's row, the reference's fp32 sequence: x - d, / 2^i, + (k - r), * 2 / (W - 1) - 1, then
 // grid_sample's ((g + 1) * W_i - 1) / 2.  The clamp keeps the conversion to int defined: every position it moves has both taps
@@ -116,22 +104,11 @@ raft_pyramid_fwd_kernel(const float* __restrict__ f1, const float* __restrict__ 
     }
     __syncthreads();
     const int ksteps = min(RKC / 4, (p.C - c0 + 3) / 4);
-#pragma unroll
-    for (int q = 0; q < RKC / 4; ++q) {
-      if (q < ksteps) {
-        const float a = sA[(4 * q + kq) * RPK + 16 * wave + j];
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, sB[(4 * q + kq) * RPK + 16 * t + j], acc[t], 0, 0, 0);
-      }
-    }
+    mfma_chunk<RPK, RPK, 4>(acc, sA, 16 * wave, sB, 0, ksteps, j, kq);
   }
   // ---- the tile, divided by sqrt(C), into LDS: a lane of an accumulator holds x' = j of four pixels
   __syncthreads();
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sO[(16 * wave + 4 * kq + r) * RPO + 16 * t + j] = __fdiv_rn(acc[t][r], sqrtC);
+  store_tile<RPO, 4>(sO, acc, 16 * wave, 0, sqrtC, j, kq);
   __syncthreads();
   // ---- level 0: a wave store is one pixel's 64 consecutive x'
   const size_t n0 = row * p.W + x0;
@@ -373,14 +350,11 @@ int check(const Raft& p, bool with_c, bool with_r) {
   return TS_OK;
 }
 
-// blocks of a 1-D grid, or 0 when they do not fit one
-unsigned grid_blocks(unsigned long long n) { return n < 0x7fffffffull ? static_cast<unsigned>(n) : 0u; }
-
 }  // namespace
 
 extern "C" int ts_raft_corr_pyramid_fwd(const float* fmap1, const float* fmap2, float* pyramid, int B, int C, int H, int W,
                                         int num_levels, void* stream) {
-  Raft p{B, C, H, W, num_levels, 0, {}};
+  Raft p{{}, B, C, H, W, num_levels, 0};
   if (int rc = check(p, true, false)) return rc;
   TS_REQUIRE_PTR(fmap1); TS_REQUIRE_PTR(fmap2); TS_REQUIRE_PTR(pyramid);
   level_offsets(p);
@@ -394,7 +368,7 @@ extern "C" int ts_raft_corr_pyramid_fwd(const float* fmap1, const float* fmap2, 
 
 extern "C" int ts_raft_corr_lookup_fwd(const float* pyramid, const float* disp, float* out, int B, int H, int W, int num_levels,
                                        int radius, void* stream) {
-  Raft p{B, 0, H, W, num_levels, radius, {}};
+  Raft p{{}, B, 0, H, W, num_levels, radius};
   if (int rc = check(p, false, true)) return rc;
   TS_REQUIRE_PTR(pyramid); TS_REQUIRE_PTR(disp); TS_REQUIRE_PTR(out);
   level_offsets(p);
@@ -407,7 +381,7 @@ extern "C" int ts_raft_corr_lookup_fwd(const float* pyramid, const float* disp, 
 
 extern "C" int ts_raft_corr_lookup_bwd(const float* pyramid, const float* disp, const float* grad_out, float* grad_disp,
                                        float* grad_pyramid, int B, int H, int W, int num_levels, int radius, int fold, void* stream) {
-  Raft p{B, 0, H, W, num_levels, radius, {}};
+  Raft p{{}, B, 0, H, W, num_levels, radius};
   if (int rc = check(p, false, true)) return rc;
   TS_REQUIRE_PTR(disp); TS_REQUIRE_PTR(grad_out);
   TS_REQUIRE(grad_disp != nullptr || grad_pyramid != nullptr, TS_ERR_NULL, "raft_corr_lookup_bwd: grad_disp and grad_pyramid are both NULL");
@@ -428,7 +402,7 @@ extern "C" int ts_raft_corr_lookup_bwd(const float* pyramid, const float* disp, 
 
 extern "C" int ts_raft_corr_pyramid_bwd(const float* grad_pyramid, const float* fmap1, const float* fmap2, float* grad_fmap1,
                                         float* grad_fmap2, int B, int C, int H, int W, int levels, void* stream) {
-  Raft p{B, C, H, W, levels, 0, {}};
+  Raft p{{}, B, C, H, W, levels, 0};
   if (int rc = check(p, true, false)) return rc;
   TS_REQUIRE_PTR(grad_pyramid);
   TS_REQUIRE(grad_fmap1 != nullptr || grad_fmap2 != nullptr, TS_ERR_NULL, "raft_corr_pyramid_bwd: grad_fmap1 and grad_fmap2 are both NULL");

@@ -2325,3 +2325,233 @@ class CorrBlock:
         if self._fmaps is None:
             return _RaftCorrLookup.apply(self._pyramid, disp, self.num_levels, self.radius)
         return _RaftCorrBlockLookup.apply(self._fmaps[0], self._fmaps[1], self._pyramid, disp, self.num_levels, self.radius)
+
+
+# ------------------------------------------------------------------- FlowCorrBlock: the 2-D all-pairs correlation pyramid of RAFT
+_FLOW_MAX_LEVELS = 4            # csrc/flow_corr.hip pools levels 1..3 from an 8-row patch of the level-0 tile
+
+
+def _flow_level_sizes(H, W, num_levels):
+    return [(H >> i, W >> i) for i in range(num_levels)]
+
+
+def _flow_check_levels(H, W, num_levels):
+    if num_levels < 1:
+        raise ValueError("flow_corr: num_levels must be >= 1, got %d" % num_levels)
+    if num_levels > _FLOW_MAX_LEVELS:
+        raise ValueError("flow_corr: num_levels = %d, the HIP kernel pools at most %d levels" % (num_levels, _FLOW_MAX_LEVELS))
+    for i, (Hi, Wi) in enumerate(_flow_level_sizes(H, W, num_levels)):
+        if Hi < 2 or Wi < 2:
+            raise ValueError("flow_corr: level %d of a %d x %d map is %d x %d, need >= 2 x 2 (the lookup divides by H_i - 1 and "
+                             "W_i - 1)" % (i, H, W, Hi, Wi))
+
+
+def flow_corr_level_views(pyramid, B, H, W, num_levels):
+    """The levels of a pyramid buffer as the reference's `corr_pyramid` entries: [B*H*W, 1, H >> i, W >> i] views (no copies)."""
+    N, views, o = B * H * W, [], 0
+    for Hi, Wi in _flow_level_sizes(H, W, num_levels):
+        views.append(pyramid[o:o + N * Hi * Wi].view(N, 1, Hi, Wi))
+        o += N * Hi * Wi
+    return views
+
+
+def _flow_levels_of(pyramid, N, H, W):
+    """num_levels of a pyramid buffer of N source pixels over an H x W map (its length decides)."""
+    if pyramid.dim() != 1 or N <= 0 or pyramid.numel() % N:
+        raise ValueError("flow_corr_lookup: pyramid must be the 1-D buffer of flow_corr_pyramid for %d pixels, got %s" % (N, tuple(pyramid.shape)))
+    per, s = pyramid.numel() // N, 0
+    for L in range(1, _FLOW_MAX_LEVELS + 1):
+        Hi, Wi = H >> (L - 1), W >> (L - 1)
+        s += Hi * Wi
+        if s == per and Hi >= 2 and Wi >= 2:
+            return L
+    raise ValueError("flow_corr_lookup: a pyramid of %d floats per pixel is no pyramid of a %d x %d map" % (per, H, W))
+
+
+class _FlowCorrPyramid(torch.autograd.Function):
+    """ts_flow_corr_pyramid_fwd / ts_flow_corr_pyramid_bwd (the cotangent keeps its levels: folded while it is staged)."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, num_levels):
+        B, C, H, W = fmap1.shape
+        pyr = torch.empty(B * H * W * sum(h * w for h, w in _flow_level_sizes(H, W, num_levels)), device=fmap1.device, dtype=torch.float32)
+        p = _lib.ptr
+        _lib.check(_lib.lib().ts_flow_corr_pyramid_fwd(p(fmap1), p(fmap2), p(pyr), B, C, H, W, num_levels, _stream()),
+                   "ts_flow_corr_pyramid_fwd")
+        ctx.save_for_backward(fmap1, fmap2)
+        ctx.num_levels = num_levels
+        return pyr
+
+    @staticmethod
+    def backward(ctx, g):
+        fmap1, fmap2 = ctx.saved_tensors
+        B, C, H, W = fmap1.shape
+        g1 = torch.empty_like(fmap1) if ctx.needs_input_grad[0] else None
+        g2 = torch.empty_like(fmap2) if ctx.needs_input_grad[1] else None
+        if g1 is None and g2 is None:
+            return None, None, None
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        _lib.check(_lib.lib().ts_flow_corr_pyramid_bwd(p(g), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, ctx.num_levels, _stream()),
+                   "ts_flow_corr_pyramid_bwd")
+        return g1, g2, None
+
+
+def _flow_lookup_fwd(pyramid, coords, num_levels, radius):
+    B, _, H, W = coords.shape
+    out = torch.empty((B, num_levels * (2 * radius + 1) ** 2, H, W), device=coords.device, dtype=torch.float32)
+    p = _lib.ptr
+    _lib.check(_lib.lib().ts_flow_corr_lookup_fwd(p(pyramid), p(coords), p(out), B, H, W, num_levels, radius, _stream()),
+               "ts_flow_corr_lookup_fwd")
+    return out
+
+
+class _FlowCorrLookup(torch.autograd.Function):
+    """ts_flow_corr_lookup_fwd / ts_flow_corr_lookup_bwd with fold = 0: the gradient with respect to a free pyramid, level by level."""
+
+    @staticmethod
+    def forward(ctx, pyramid, coords, num_levels, radius):
+        ctx.save_for_backward(pyramid, coords)
+        ctx.geom = (num_levels, radius)
+        return _flow_lookup_fwd(pyramid, coords, num_levels, radius)
+
+    @staticmethod
+    def backward(ctx, g):
+        pyramid, coords = ctx.saved_tensors
+        L, r = ctx.geom
+        B, _, H, W = coords.shape
+        gp = torch.empty_like(pyramid) if ctx.needs_input_grad[0] else None
+        gc = torch.empty_like(coords) if ctx.needs_input_grad[1] else None
+        if gp is None and gc is None:
+            return None, None, None, None
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        _lib.check(_lib.lib().ts_flow_corr_lookup_bwd(p(pyramid), p(coords), p(g), p(gc), p(gp), B, H, W, L, r, 0, _stream()),
+                   "ts_flow_corr_lookup_bwd")
+        return gp, gc, None, None
+
+
+class _FlowCorrBlockLookup(torch.autograd.Function):
+    """The lookup of a FlowCorrBlock, differentiable in the FEATURES the pyramid was built from: backward is ts_flow_corr_lookup_bwd
+    with fold = 1 (one [B*H*W, H*W] cotangent of level 0, written once) and ts_flow_corr_pyramid_bwd on it -- the per-level
+    cotangent of the pyramid is never materialised."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, pyramid, coords, num_levels, radius):
+        ctx.save_for_backward(fmap1, fmap2, pyramid, coords)
+        ctx.geom = (num_levels, radius)
+        return _flow_lookup_fwd(pyramid, coords, num_levels, radius)
+
+    @staticmethod
+    def backward(ctx, g):
+        fmap1, fmap2, pyramid, coords = ctx.saved_tensors
+        L, r = ctx.geom
+        B, C, H, W = fmap1.shape
+        need1, need2, _, needc = ctx.needs_input_grad[:4]
+        if not (need1 or need2 or needc):
+            return (None,) * 6
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        feats = need1 or need2
+        G = torch.empty(B * (H * W) ** 2, device=g.device, dtype=torch.float32) if feats else None
+        gc = torch.empty_like(coords) if needc else None
+        _lib.check(_lib.lib().ts_flow_corr_lookup_bwd(p(pyramid), p(coords), p(g), p(gc), p(G), B, H, W, L, r, 1, _stream()),
+                   "ts_flow_corr_lookup_bwd")
+        g1 = torch.empty_like(fmap1) if need1 else None
+        g2 = torch.empty_like(fmap2) if need2 else None
+        if feats:
+            _lib.check(_lib.lib().ts_flow_corr_pyramid_bwd(p(G), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, 1, _stream()),
+                       "ts_flow_corr_pyramid_bwd")
+        return g1, g2, None, gc, None, None
+
+
+def _flow_check_features(fmap1, fmap2, num_levels):
+    if fmap1.dim() != 4 or fmap2.dim() != 4:
+        raise ValueError("flow_corr: fmap1 and fmap2 must be [B,C,H,W], got %s and %s" % (tuple(fmap1.shape), tuple(fmap2.shape)))
+    if fmap1.shape != fmap2.shape:
+        raise ValueError("flow_corr: fmap1 and fmap2 differ in shape (%s and %s)" % (tuple(fmap1.shape), tuple(fmap2.shape)))
+    _flow_check_levels(fmap1.shape[2], fmap1.shape[3], int(num_levels))
+    _require_gpu(fmap1, fmap2)
+
+
+def _flow_check_coords(coords, radius, size=None):
+    if coords.dim() != 4 or coords.shape[1] != 2:
+        raise ValueError("flow_corr: coords must be [B,2,H,W], got %s" % (tuple(coords.shape),))
+    if size is not None and (coords.shape[0], coords.shape[2], coords.shape[3]) != tuple(size):
+        raise ValueError("flow_corr: coords %s does not match the feature maps' (B, H, W) = %s" % (tuple(coords.shape), tuple(size)))
+    if radius < 0:
+        raise ValueError("flow_corr: radius must be >= 0, got %d" % radius)
+
+
+def flow_corr_pyramid(fmap1, fmap2, num_levels):
+    """The correlation pyramid of the reference's FlowCorrBlock (aggregation/utils/raft_corr.py:73-87, :112-123) in one launch:
+    level 0 is the all-pairs cost (f1_n.f1_m - 2 f1_n.f2_m + f2_n.f2_m) / sqrt(C) between pixel n of fmap1 and pixel m of fmap2
+    (the reference's full Gram matrices), level i the 2x2 average of level i-1 over m (an odd last row or column is dropped).
+    Returns ONE 1-D fp32 buffer: level i is [B*H*W, (H >> i)*(W >> i)] contiguous, stored after the levels before it --
+    `flow_corr_level_views` slices it.  Differentiable in both maps."""
+    _flow_check_features(fmap1, fmap2, num_levels)
+    return _FlowCorrPyramid.apply(_lib.contiguous(fmap1), _lib.contiguous(fmap2), int(num_levels))
+
+
+def flow_corr_lookup(pyramid, coords, radius, size=None):
+    """The windowed lookup of the reference's FlowCorrBlock.__call__ (raft_corr.py:89-110, bilinear_sampler :146-160) in one launch:
+    out [B, L*(2r+1)^2, H, W], channel i*(2r+1)^2 + a*(2r+1) + b = the bilinear sample (zeros outside) of pixel (y, x)'s level-i
+    row at (coords_x / 2^i + a - r, coords_y / 2^i + b - r): the first window index moves x, as the reference's does.  `pyramid`
+    is the buffer of flow_corr_pyramid for the same B, H, W (`size` = (H, W), by default coords' own; the number of levels
+    follows from the buffer's length).  Differentiable in the pyramid (every level) and in coords."""
+    _flow_check_coords(coords, int(radius))
+    B, _, H, W = coords.shape
+    if size is not None and tuple(size) != (H, W):
+        raise ValueError("flow_corr: coords %s does not match size = %s" % (tuple(coords.shape), tuple(size)))
+    L = _flow_levels_of(pyramid, B * H * W, H, W)
+    _require_gpu(pyramid, coords)
+    return _FlowCorrLookup.apply(_lib.contiguous(pyramid), _lib.contiguous(coords), L, int(radius))
+
+
+class FlowCorrBlock:
+    """FlowCorrBlock of the reference (aggregation/utils/raft_corr.py:71-144; same arguments and attributes), for optical flow:
+    the all-pairs cost between every pixel of fmap1 and every pixel of fmap2 [B,C,H,W] as a pyramid of `num_levels` levels (one
+    launch, one buffer), and `__call__(coords)` with coords [B,2,H,W] (x, y): the (2*radius+1)^2 bilinear window around the
+    target coordinate on every level, [B, num_levels*(2*radius+1)^2, H, W].  `corr_pyramid[i]` is the [B*H*W, 1, H >> i, W >> i]
+    view of level i.
+
+    Gradients reach coords and the two feature maps through `__call__` (the pyramid's per-level cotangent is never materialised:
+    ts_flow_corr_lookup_bwd folds it into one level-0 cotangent, ts_flow_corr_pyramid_bwd contracts that); the `corr_pyramid`
+    views themselves carry no gradient.  No host reads: build and lookup can be captured."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        num_levels, radius = int(num_levels), int(radius)
+        if radius < 0:
+            raise ValueError("flow_corr: radius must be >= 0, got %d" % radius)
+        _flow_check_features(fmap1, fmap2, num_levels)
+        self.num_levels = num_levels
+        self.radius = radius
+        f1, f2 = _lib.contiguous(fmap1), _lib.contiguous(fmap2)
+        with torch.no_grad():
+            self._pyramid = _FlowCorrPyramid.apply(f1, f2, num_levels)
+        self._shape = tuple(fmap1.shape)
+        # the feature maps are kept only where a backward can ask for them (the reference keeps the pyramid alone)
+        self._fmaps = (f1, f2) if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad) else None
+        B, _, H, W = self._shape
+        self.corr_pyramid = flow_corr_level_views(self._pyramid, B, H, W, num_levels)
+
+    def __call__(self, coords):
+        B, _, H, W = self._shape
+        _flow_check_coords(coords, self.radius, (B, H, W))
+        _require_gpu(coords)
+        coords = _lib.contiguous(coords)
+        if self._fmaps is None:
+            return _FlowCorrLookup.apply(self._pyramid, coords, self.num_levels, self.radius)
+        return _FlowCorrBlockLookup.apply(self._fmaps[0], self._fmaps[1], self._pyramid, coords, self.num_levels, self.radius)
+
+    @staticmethod
+    def init_flow(size, device, flow_init=None):
+        """(ref_coord, tgt_coord) of raft_corr.py:125-144: the pixel grid [B,2,H,W] (channel 0 = x, 1 = y) of a [B,C,H,W] `size`,
+        the target moved by `flow_init` when given.  Plain torch."""
+        if len(size) != 4:
+            raise ValueError("flow_corr: init_flow expects a size [B, C, H, W], got %s" % (tuple(size),))
+        b, _, h, w = size
+        xs = torch.arange(0, w, device=device, dtype=torch.float).view(1, 1, 1, w).expand(b, 1, h, w)
+        ys = torch.arange(0, h, device=device, dtype=torch.float).view(1, 1, h, 1).expand(b, 1, h, w)
+        grid = torch.cat((xs, ys), dim=1).detach()
+        return grid, (grid if flow_init is None else grid + flow_init)

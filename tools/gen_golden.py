@@ -1644,6 +1644,102 @@ def raft_cases(M):
     print("\n".join(lines))
 
 
+def flow_cases(M):
+    """tests/golden/flow_corr_*.npz: the reference's own FlowCorrBlock (aggregation/utils/raft_corr.py:71-160) on the CPU, in fp32 and
+    fp64, forward and backward, on seeded inputs; dev_* = how far its fp32 run lies from its fp64 run."""
+    from architecture.modeling.aggregation.utils.raft_corr import FlowCorrBlock as RefFlowCorrBlock
+    import flow_corr_ref
+    shapes = [("a", 2, 6, 8, 11, 3, 2), ("c", 1, 40, 4, 4, 2, 1), ("e", 1, 32, 8, 16, 3, 3)]
+    lines = ["flow_corr_*.npz: tools/gen_golden.py --only-flow, numpy %s, torch %s CPU -- the reference's own FlowCorrBlock" % (np.__version__, torch.__version__),
+             "(architecture/modeling/aggregation/utils/raft_corr.py:71-160) built and called on seeded inputs in float32 and in float64,",
+             "with the backward of a seeded cotangent in both.",
+             "Inputs: fmap1, fmap2 N(0,1), kept as their seed (tests/synth.py; flow_corr_ref.load_fixture draws them again); coords = the pixel grid (x, y) plus a flow uniform in +-0.25 (W, H); the cotangent is k / 8 with k an integer in [-8, 8].",
+             "The generator draws the flow of single pixels again until, in the fp64 evaluation, no sample position of any level or",
+             "tap lies within 1e-3 of an integer in x or in y and the floors agree between the fp32 and the fp64 evaluation (the",
+             "gradient with respect to coords has a kink at integer positions), and asserts both; it asserts that 40-95 % of the outputs are non-zero.",
+             "Stored: seed and shape of the feature maps, coords, the float32 output `out`, the float32 pyramid levels `pyr_<i>` [B*H*W, (H >> i)*(W >> i)], the cotangent",
+             "`cot`, the gradients of the float32 run `grad_fmap1`, `grad_fmap2`, `grad_coords`; dev_out and dev_pyr_<i> = max |fp32 run -",
+             "fp64 run| (the output compared in double: tests/flow_corr_ref.py in fp64 stands for the fp64 run's output, which the",
+             "reference casts to float32 at the end; the two agree to that cast, asserted here; the fp64 pyramid levels are the",
+             "reference's own), rel_grad_* = relative L2 of the fp32 run's gradient against the fp64 run's."]
+    total = 0
+    for tag, B, C, H, W, L, r in shapes:
+        seed = synth.SEED0 + 9000 + ord(tag)
+        rng = np.random.default_rng(seed)
+        f1, f2 = (T(a) for a in flow_corr_ref.fixture_features(seed, (B, C, H, W)))
+        grid = RefFlowCorrBlock.init_flow((B, C, H, W), "cpu")[1].clone()
+        span = torch.tensor([W, H], dtype=torch.float64).view(1, 2, 1, 1)
+
+        def draw(n):
+            return T(rng.uniform(-0.25, 0.25, size=(n, 2))) * span.view(1, 2)
+        coords = (grid.double() + draw(B * H * W).view(B, H, W, 2).permute(0, 3, 1, 2)).float()
+        cot = T(rng.integers(-8, 9, size=(B, L * (2 * r + 1) ** 2, H, W)) / 8.0).float()
+
+        def bad_pixels(c):
+            bad = torch.zeros((B, H, W), dtype=torch.bool)
+            gap = 1.0
+            for i in range(L):
+                p64 = flow_corr_ref.positions(c.double(), i, r, H >> i, W >> i)
+                p32 = flow_corr_ref.positions(c, i, r, H >> i, W >> i)
+                for a64, a32 in zip(p64, p32):
+                    near = (a64 - torch.round(a64)).abs()
+                    gap = min(gap, float(near.min()))
+                    bad |= ((near < 1e-3) | (torch.floor(a64) != torch.floor(a32.double()))).any(dim=-1)
+            return bad, gap
+        redrawn = 0
+        for attempt in range(200):
+            bad, gap = bad_pixels(coords)
+            n = int(bad.sum())
+            if n == 0:
+                break
+            redrawn += n
+            fresh = (grid.double().permute(0, 2, 3, 1)[bad] + draw(n)).float()
+            cp = coords.permute(0, 2, 3, 1).contiguous()
+            cp[bad] = fresh
+            coords = cp.permute(0, 3, 1, 2).contiguous()
+        bad, gap = bad_pixels(coords)
+        assert int(bad.sum()) == 0 and gap >= 1e-3, (tag, int(bad.sum()), gap)
+
+        def run(dt):
+            a, b_, c = (t.detach().clone().to(dt).requires_grad_(True) for t in (f1, f2, coords))
+            blk = RefFlowCorrBlock(a, b_, num_levels=L, radius=r)
+            o = blk(c)
+            o.backward(cot.to(o.dtype))
+            return o.detach(), [lv.detach() for lv in blk.corr_pyramid], (a.grad, b_.grad, c.grad)
+        o32, p32, g32 = run(torch.float32)
+        o64f, p64, g64 = run(torch.float64)
+        own64 = flow_corr_ref.flow_corr_block(f1.double(), f2.double(), coords.double(), L, r)
+        assert o32.dtype == torch.float32 and o64f.dtype == torch.float32 and tuple(o32.shape) == (B, L * (2 * r + 1) ** 2, H, W)
+        scale = float(own64.abs().max())
+        assert float((own64 - o64f.double()).abs().max()) <= 2.0 ** -24 * scale, (tag, float((own64 - o64f.double()).abs().max()))
+        nz = float((o32 != 0).float().mean())
+        assert 0.40 <= nz <= 0.95, (tag, nz)
+        own_levels = flow_corr_ref.corr_pyramid(f1.double(), f2.double(), L)
+        arrs = dict(seed=seed, shape=np.array([B, C, H, W]), coords=coords, out=o32, cot=cot, grad_fmap1=g32[0], grad_fmap2=g32[1], grad_coords=g32[2],
+                    num_levels=L, radius=r, dev_out=float((o32.double() - own64).abs().max()))
+        for i in range(L):
+            assert tuple(p32[i].shape) == (B * H * W, 1, H >> i, W >> i)
+            assert float((own_levels[i].reshape(p64[i].shape) - p64[i]).abs().max()) < 1e-12, (tag, i)
+            arrs["pyr_%d" % i] = p32[i].reshape(B * H * W, (H >> i) * (W >> i))
+            arrs["dev_pyr_%d" % i] = float((p32[i].double() - p64[i]).abs().max())
+        rels = []
+        for name, a, b_ in zip(("fmap1", "fmap2", "coords"), g32, g64):
+            arrs["rel_grad_" + name] = float((a.double() - b_).norm() / b_.norm())
+            rels.append(arrs["rel_grad_" + name])
+        save("flow_corr_" + tag, **arrs)
+        size = os.path.getsize(os.path.join(OUT, "flow_corr_%s.npz" % tag))
+        assert size <= 200 * 1024, (tag, size)
+        total += size
+        lines.append("flow_corr_%s  B=%d C=%d H=%d W=%d L=%d r=%d  %.0f %% of the outputs non-zero, %d flows drawn again, nearest "
+                     "integer %.2e; dev_out %.3g, dev_pyr %.3g .. %.3g, rel_grad fmap1 %.3g fmap2 %.3g coords %.3g; %.0f KB"
+                     % (tag, B, C, H, W, L, r, 100 * nz, redrawn, gap, arrs["dev_out"], min(arrs["dev_pyr_%d" % i] for i in range(L)),
+                        max(arrs["dev_pyr_%d" % i] for i in range(L)), rels[0], rels[1], rels[2], size / 1024))
+    lines.append("total %.0f KB" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_flow.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -1672,6 +1768,9 @@ def main():
         return
     if "--only-raft" in sys.argv:
         raft_cases(M)
+        return
+    if "--only-flow" in sys.argv:
+        flow_cases(M)
         return
     if "--only-augment" in sys.argv:
         augment_cases(M)
