@@ -283,6 +283,65 @@ int ts_disp_render_fwd(const float* est, const float* gt, const float* max_disp,
                        float* stats, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Optical flow: metrics, colour maps and the KITTI 16-bit decode (architecture/data/evaluation/flow_pixel_error.py:9-96
+ * `flow_calc_error`, architecture/utils/visualization/flow_colormap.py:8-220, architecture/data/utils/load_flow.py:54-78 `load_png`).
+ * A flow map is fp32 [B,2,h,w], or [B,h,w,2] with the call's *_HWC flag: either is read in place (quads where the rows are
+ * 16-byte aligned and the width is a multiple of 4, single pixels otherwise).  Every quantity that feeds a decision is fp32 in the
+ * reference's operation order, every operation rounded on its own.
+ * ts_flow_metrics_fwd: flow_calc_error of up to four estimates against one ground truth in one call.
+ *   est<l> [B,2,h<l>,w<l>] (n_est = 1..4; unused pointers may be NULL); a level whose size differs from the ground truth's is read
+ *   through F.interpolate(est, (Hg,Wg), bilinear, align_corners) evaluated in registers, then u * Wg / w and v * Hg / h.
+ *   gt [B,2,Hg,Wg].  Valid pixels: no NaN in gt, lb < sqrt(gt_u^2 + gt_v^2) < ub (strict), and with TS_FLOW_SPARSE not
+ *   (|gt_u| < 1e-12 and |gt_v| < 1e-12).
+ *   out [n_est][5] fp32: {1px, 2px, 3px, 5px, epe} of err = sqrt((gt_u - est_u)^2 + (gt_v - est_v)^2) (percent; 0 when no pixel is
+ *   valid; a NaN estimate inside the mask leaves the counts alone and makes epe NaN).
+ *   Counts are exact integers, sums fp64 in a fixed order: bit-identical from run to run.  Two launches, no synchronisation.
+ * ts_flow_render_fwd: est [B,2,h,w] is read at the size of the target (Hg,Wg) as above; gt [B,2,Hg,Wg] (NULL when no selected
+ *   output needs it); flags selects the outputs and their form:
+ *     TS_FLOW_RENDER_EST_COLOR / TS_FLOW_RENDER_GT_COLOR  flow_to_color (:143-167) of est / gt into flow_color: [B,Hg,Wg,3], or with
+ *                            both set [B,2Hg,Wg,3], est above gt.  Unknown pixels (|u| or |v| > 1e7, or NaN) count as 0 in the
+ *                            maximum radius and are black.  The maximum is each map's own (per image), the one of both maps with
+ *                            TS_FLOW_RENDER_MAX_SHARED, or max_rad[b] with TS_FLOW_RENDER_MAX_GIVEN.  wheel: the 55 x 3 fp32 table
+ *                            of make_color_wheel (:8-56), values 0..255 (device pointer).
+ *     TS_FLOW_RENDER_ERR_CLASS  flow_err_to_color (:170-220) into err_class [B,Hg,Wg,3]; gt_val (may be NULL) fp32 [B,Hg,Wg]
+ *                            multiplies the error, and 0 gives black
+ *     TS_FLOW_RENDER_STATS   stats is written although no selected output needs it
+ *     TS_FLOW_RENDER_UINT8   colour outputs are uint8, floor(255 v + 0.5) after a clamp to [0,1], NaN -> 0; else fp32
+ *     TS_FLOW_RENDER_CHW     colour outputs are [B,3,rows,Wg] instead of [B,rows,Wg,3]
+ *   stats [B][TS_FLOW_STATS_FLOATS] (written with TS_FLOW_RENDER_STATS or when a maximum is taken from the data; needs workspace):
+ *     [0] max radius of est  [1] of gt (0 without gt)  [2] of both  [4..13] the members' counts of the ten error classes, int32
+ *     bit patterns (0 without gt)  [3], [14], [15] zero.
+ *   Two launches (statistics + finish) are skipped when stats is not needed; then the colour launch.  No atomics, no
+ *   synchronisation; bit-identical from run to run.
+ * ts_flow_u16_decode_fwd: raw uint16 [B,H,W,3], or [B,3,H,W] with TS_FLOW_U16_CHW -> flow fp32 [B,2,H,W] = (raw - 2^15) / 64 (exact),
+ *   both components 0 where the third channel is 0; valid (may be NULL) uint8 [B,1,H,W] = third channel != 0.  One launch.
+ * ---------------------------------------------------------------------------------------- */
+#define TS_FLOW_SPARSE 1
+#define TS_FLOW_EST_HWC 2
+#define TS_FLOW_GT_HWC 4
+#define TS_FLOW_RENDER_EST_COLOR 1
+#define TS_FLOW_RENDER_GT_COLOR 2
+#define TS_FLOW_RENDER_ERR_CLASS 4
+#define TS_FLOW_RENDER_STATS 8
+#define TS_FLOW_RENDER_UINT8 16
+#define TS_FLOW_RENDER_CHW 32
+#define TS_FLOW_RENDER_MAX_SHARED 64
+#define TS_FLOW_RENDER_MAX_GIVEN 128
+#define TS_FLOW_RENDER_EST_HWC 256
+#define TS_FLOW_RENDER_GT_HWC 512
+#define TS_FLOW_STATS_FLOATS 16
+#define TS_FLOW_U16_CHW 1
+size_t ts_flow_metrics_workspace_bytes(int B, int Hg, int Wg);
+int ts_flow_metrics_fwd(const float* est0, const float* est1, const float* est2, const float* est3, int n_est, int h0, int w0,
+                        int h1, int w1, int h2, int w2, int h3, int w3, const float* gt, int B, int Hg, int Wg, float lb, float ub,
+                        int flags, float* out, void* workspace, void* stream);
+size_t ts_flow_render_workspace_bytes(int B, int Hg, int Wg);
+int ts_flow_render_fwd(const float* est, const float* gt, const float* gt_val, const float* max_rad, const float* wheel, int B,
+                       int h, int w, int Hg, int Wg, int flags, void* flow_color, void* err_class, float* stats, void* workspace,
+                       void* stream);
+int ts_flow_u16_decode_fwd(const void* raw, int B, int H, int W, int flags, float* flow, void* valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Preparation of the input frames (projects/TemporalStereo/video_inference.py:100-110 `read_image`, :135-140 `read_disparity`, :246-251;
  * architecture/data/datasets/base.py:99-187 `do_transform`, :231-248 the intrinsics pyramid): uint8 frames in, the batch's tensors out.
  * ts_frames_prepare_fwd: one launch for the whole batch and both eyes.

@@ -16,11 +16,12 @@ from .aggregation import (TEMPORALSTEREO, CoarseAggregation, FineAggregation, Pr
 from .prediction import SOFTARGMIN, ARGMIN  # noqa: F401
 from . import temporal  # noqa: F401
 from . import evaluation  # noqa: F401
-from .evaluation import validation_metrics  # noqa: F401
+from .evaluation import validation_metrics, flow_calc_error, do_flow_evaluation, flow_validation_metrics  # noqa: F401
 from . import visualization  # noqa: F401
-from .visualization import render_frame  # noqa: F401
+from .visualization import (render_frame, make_color_wheel, flow_max_rad, flow_color, flow_to_color, flow_err_to_color,  # noqa: F401
+                            render_flow_frame)
 from . import preprocess  # noqa: F401
-from .preprocess import prepare_frames, prepare_batch, intrinsics_pyramid, disp_from_uint16  # noqa: F401
+from .preprocess import prepare_frames, prepare_batch, intrinsics_pyramid, disp_from_uint16, decode_kitti_flow  # noqa: F401
 from . import augment  # noqa: F401
 from .augment import (Augmentation, draw_augmentation, gamma_table, augment_frames, prepare_train_batch,  # noqa: F401
                       disp_window_from_uint16)

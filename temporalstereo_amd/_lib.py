@@ -86,6 +86,11 @@ SIGNATURES = {
     "ts_disp_metrics_fwd": (c_int, [c_f32p] * 4 + [c_int] * 9 + [c_f32p] * 2 + [c_int] * 3 + [c_float, c_float, c_int, c_f32p, c_ptr, c_ptr]),
     "ts_disp_render_workspace_bytes": (c_size, [c_int] * 3),
     "ts_disp_render_fwd": (c_int, [c_f32p] * 4 + [c_int] * 6 + [c_float] + [c_ptr] * 4 + [c_f32p, c_ptr, c_ptr]),
+    "ts_flow_metrics_workspace_bytes": (c_size, [c_int] * 3),
+    "ts_flow_metrics_fwd": (c_int, [c_f32p] * 4 + [c_int] * 9 + [c_f32p] + [c_int] * 3 + [c_float, c_float, c_int, c_f32p, c_ptr, c_ptr]),
+    "ts_flow_render_workspace_bytes": (c_size, [c_int] * 3),
+    "ts_flow_render_fwd": (c_int, [c_f32p] * 5 + [c_int] * 6 + [c_ptr] * 2 + [c_f32p, c_ptr, c_ptr]),
+    "ts_flow_u16_decode_fwd": (c_int, [c_ptr] + [c_int] * 4 + [c_f32p, c_ptr, c_ptr]),
     "ts_frames_prepare_fwd": (c_int, [c_ptr] * 2 + [c_int] * 4 + [c_float] * 6 + [c_int] * 2 + [c_ptr] + [c_f32p] * 2 +
                               [ctypes.c_longlong] + [c_f32p] * 2 + [ctypes.c_longlong, c_ptr]),
     "ts_intrinsics_pyramid_fwd": (c_int, [c_ptr] + [c_int] * 5 + [c_f32p] * 2 + [c_ptr]),

@@ -1,6 +1,7 @@
 // torch's align_corners=True bilinear rescale of a disparity map, evaluated at one output pixel in registers: the arithmetic of
 // ts_resize_bilinear_fwd (pyramid_ops.hip), shared by the kernels that read a low-resolution disparity at full resolution without
-// writing the rescaled map (losses.hip: smooth-L1 on the wrapper's rescale; evaluation.hip: the validation metrics).
+// writing the rescaled map (losses.hip: smooth-L1 on the wrapper's rescale; evaluation.hip: the validation metrics; render.hip;
+// flow_frame.hip: each flow component through its strides).
 // Same expressions as resize_bilinear_kernel, so the same contraction into fused multiply-adds and the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,15 +16,23 @@ __device__ __forceinline__ void lin_src(float scale, int dst, int in_size, int& 
   l1 = s - static_cast<float>(i0);
 }
 
-// F.interpolate(e * vs, bilinear, align_corners=True) at (oy, ox) of the full-size map; e is one [h, w] plane
-__device__ __forceinline__ float rescaled(const float* __restrict__ e, int h, int w, float sh, float sw, float vs, int oy, int ox) {
+// F.interpolate(e, bilinear, align_corners=True) at (oy, ox) of the full-size map, times vs; e is one [h, w] plane whose pixel
+// (y, x) is e[y sy + x sx] (element strides: a dense plane has sy = w, sx = 1)
+template <class Idx>
+__device__ __forceinline__ float rescaled_at(const float* __restrict__ e, Idx sy, Idx sx, int h, int w, float sh, float sw, float vs,
+                                             int oy, int ox) {
   int y0, y1, x0, x1;
   float ly, lx;
   lin_src(sh, oy, h, y0, y1, ly);
   lin_src(sw, ox, w, x0, x1, lx);
-  const float top = (1.f - lx) * e[y0 * w + x0] + lx * e[y0 * w + x1];
-  const float bot = (1.f - lx) * e[y1 * w + x0] + lx * e[y1 * w + x1];
+  const float top = (1.f - lx) * e[y0 * sy + x0 * sx] + lx * e[y0 * sy + x1 * sx];
+  const float bot = (1.f - lx) * e[y1 * sy + x0 * sx] + lx * e[y1 * sy + x1 * sx];
   return ((1.f - ly) * top + ly * bot) * vs;
+}
+
+// the same of a dense plane
+__device__ __forceinline__ float rescaled(const float* __restrict__ e, int h, int w, float sh, float sw, float vs, int oy, int ox) {
+  return rescaled_at<int>(e, w, 1, h, w, sh, sw, vs, oy, ox);
 }
 
 // source step of an align_corners resize from in_size to out_size samples

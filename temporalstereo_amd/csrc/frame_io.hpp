@@ -1,9 +1,12 @@
-// Byte, quad and row helpers shared by the frame-side kernels (preprocess.hip, augment.hip, render.hip, evaluation.hip), gfx950.
+// Byte, quad and row helpers shared by the frame-side kernels (preprocess.hip, augment.hip, render.hip, evaluation.hip,
+// flow_frame.hip), gfx950.
 // These kernels are bit-exact against reference-made fixtures, so whatever decides a bit is written once, here:
 //   ByteTables         byte / 255 and ((byte / 255) - mean[c]) / std[c], correctly rounded divisions, 1,024 floats in LDS
 //   load_quad, store4  four horizontally adjacent pixels: 12 source bytes in, one 16-byte store per channel out
 //   u16 quads          four 16-bit disparities in, raw / scale where raw > 0 and the mask raw > 0 out
 //   load_row           V floats of a row
+//   FlowMap, load_uv   a two-channel flow map read in place through element strides, [B,2,H,W] or [B,H,W,2]
+//   q8, store_rgb      the uint8 code of a colour and V pixels of a colour output, fp32 or uint8, HWC or CHW
 //   grid_blocks        the one ceil / cap / at-least-one rule of the grid sizes
 //   frames_check_*     the argument checks ts_frames_prepare_fwd and ts_frames_augment_fwd have in common
 // The device helpers hold no multiply-add pair, only explicitly rounded intrinsics and integer work, so a
@@ -119,11 +122,111 @@ __device__ __forceinline__ void load_row(const float* __restrict__ p, float (&ou
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------- two-channel flow maps
+// A flow map read in place: channel c of pixel (y, x) of image b is p[b sb + c sc + y sy + x sx] (element strides), so
+// [B,2,H,W] (sx = 1) and [B,H,W,2] (sx = 2, sc = 1) need no copy.
+struct FlowMap {
+  const float* p;
+  long long sb, sc, sy, sx;
+  int h, w;
+};
+
+inline FlowMap flow_map(const float* p, int h, int w, bool hwc) {
+  const long long hw = static_cast<long long>(h) * w;
+  return hwc ? FlowMap{p, 2 * hw, 1, 2LL * w, 2, h, w} : FlowMap{p, 2 * hw, hw, w, 1, h, w};
+}
+
+// whether load_uv<4> may be used on every row quad of the map: whole rows of quads, every quad's first float 16-byte aligned
+inline bool flow_quads_ok(const FlowMap& m) {
+  if (m.p == nullptr) return true;
+  const bool dense = (m.sx == 1) || (m.sx == 2 && m.sc == 1);
+  return dense && m.w % 4 == 0 && aligned16(m.p) && m.sb % 4 == 0 && m.sy % 4 == 0 && (m.sx == 2 || m.sc % 4 == 0);
+}
+
+// (u, v) of V horizontally adjacent pixels of row y from column x0 of image b.  V = 4 (the caller has checked flow_quads_ok):
+// two 16-byte loads, one per plane (sx = 1) or the eight interleaved floats (sx = 2); V = 1: two floats through the strides.
+template <int V>
+__device__ __forceinline__ void load_uv(const FlowMap& m, int b, int y, int x0, float (&u)[V], float (&v)[V]) {
+  const float* p = m.p + b * m.sb + y * m.sy + x0 * m.sx;
+  if constexpr (V == 4) {
+    if (m.sx == 1) {
+      load_row<4>(p, u);
+      load_row<4>(p + m.sc, v);
+    } else {
+      float lo[4], hi[4];
+      load_row<4>(p, lo);
+      load_row<4>(p + 4, hi);
+      u[0] = lo[0]; v[0] = lo[1]; u[1] = lo[2]; v[1] = lo[3];
+      u[2] = hi[0]; v[2] = hi[1]; u[3] = hi[2]; v[3] = hi[3];
+    }
+  } else {
+    u[0] = p[0];
+    v[0] = p[m.sc];
+  }
+}
+
 // workgroups for `items` work items at `threads` items each: at most `cap`, at least one (a grid-stride loop takes the rest)
 inline int grid_blocks(long long items, int threads, long long cap) {
   long long nb = (items + threads - 1) / threads;
   if (nb > cap) nb = cap;
   return static_cast<int>(nb < 1 ? 1 : nb);
+}
+
+// floor(255 v + 0.5) after a clamp to [0,1], NaN -> 0; the product and the sum are rounded separately (an elementwise restatement
+// in a tensor library does the same)
+__device__ __forceinline__ unsigned q8(float v) {
+  if (v != v) return 0u;
+  v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+  return static_cast<unsigned>(floorf(__fadd_rn(__fmul_rn(255.f, v), 0.5f)));
+}
+
+// V pixels of row `row`, from column x0, of image b of a colour output with `rows` rows: HWC [B,rows,W,3] or CHW [B,3,rows,W]
+template <int V, bool U8>
+__device__ __forceinline__ void store_rgb(void* base, bool chw, int rows, int W, int b, int row, int x0, const float (&c)[V][3]) {
+  if (!chw) {
+    const size_t o = ((static_cast<size_t>(b) * rows + row) * W + x0) * 3;
+    if constexpr (U8) {
+      unsigned char* p = static_cast<unsigned char*>(base) + o;
+      if constexpr (V == 4) {
+        unsigned q[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) q[i] = q8(c[i / 3][i % 3]);
+        unsigned* d = reinterpret_cast<unsigned*>(p);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = q[4 * i] | (q[4 * i + 1] << 8) | (q[4 * i + 2] << 16) | (q[4 * i + 3] << 24);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = static_cast<unsigned char>(q8(c[0][k]));
+      }
+    } else {
+      float* p = static_cast<float*>(base) + o;
+      if constexpr (V == 4) {
+        float4* d = reinterpret_cast<float4*>(p);
+        d[0] = make_float4(c[0][0], c[0][1], c[0][2], c[1][0]);
+        d[1] = make_float4(c[1][1], c[1][2], c[2][0], c[2][1]);
+        d[2] = make_float4(c[2][2], c[3][0], c[3][1], c[3][2]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = c[0][k];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const size_t o = ((static_cast<size_t>(b) * 3 + k) * rows + row) * W + x0;
+      if constexpr (U8) {
+        unsigned char* p = static_cast<unsigned char*>(base) + o;
+        if constexpr (V == 4)
+          *reinterpret_cast<unsigned*>(p) = q8(c[0][k]) | (q8(c[1][k]) << 8) | (q8(c[2][k]) << 16) | (q8(c[3][k]) << 24);
+        else
+          p[0] = static_cast<unsigned char>(q8(c[0][k]));
+      } else {
+        float* p = static_cast<float*>(base) + o;
+        if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(c[0][k], c[1][k], c[2][k], c[3][k]);
+        else p[0] = c[0][k];
+      }
+    }
+  }
 }
 
 // ------------------------------------------------------------------ the checks of ts_frames_prepare_fwd / ts_frames_augment_fwd

@@ -108,6 +108,7 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_raft_corr_lookup_bwd),    TS_PLAN_OP(ts_raft_corr_pyramid_bwd),
     TS_PLAN_OP(ts_flow_corr_pyramid_fwd),   TS_PLAN_OP(ts_flow_corr_lookup_fwd),
     TS_PLAN_OP(ts_flow_corr_lookup_bwd),    TS_PLAN_OP(ts_flow_corr_pyramid_bwd),
+    TS_PLAN_OP(ts_flow_metrics_fwd),        TS_PLAN_OP(ts_flow_render_fwd),         TS_PLAN_OP(ts_flow_u16_decode_fwd),
 };
 
 struct Call {

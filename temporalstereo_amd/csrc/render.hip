@@ -76,6 +76,7 @@ struct RenderArgs {
 };
 
 using ts::nan_max;
+using ts::store_rgb;
 
 // V estimates of row y starting at column x0 of image b: read at full size, or rescaled in registers
 template <int V>
@@ -312,63 +313,6 @@ __device__ __forceinline__ int bar_index(int x, int W) {
   }
   const double xi = __dmul_rn(v, 256.0);
   return xi >= 256.0 ? 255 : static_cast<int>(xi);
-}
-
-// floor(255 v + 0.5) after a clamp to [0,1], NaN -> 0; the product and the sum are rounded separately (an elementwise restatement
-// in a tensor library does the same)
-__device__ __forceinline__ unsigned q8(float v) {
-  if (v != v) return 0u;
-  v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
-  return static_cast<unsigned>(floorf(__fadd_rn(__fmul_rn(255.f, v), 0.5f)));
-}
-
-// V pixels of row `row`, from column x0, of image b of a colour output with `rows` rows: HWC [B,rows,W,3] or CHW [B,3,rows,W]
-template <int V, bool U8>
-__device__ __forceinline__ void store_rgb(void* base, bool chw, int rows, int W, int b, int row, int x0, const float (&c)[V][3]) {
-  if (!chw) {
-    const size_t o = ((static_cast<size_t>(b) * rows + row) * W + x0) * 3;
-    if constexpr (U8) {
-      unsigned char* p = static_cast<unsigned char*>(base) + o;
-      if constexpr (V == 4) {
-        unsigned q[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) q[i] = q8(c[i / 3][i % 3]);
-        unsigned* d = reinterpret_cast<unsigned*>(p);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) d[i] = q[4 * i] | (q[4 * i + 1] << 8) | (q[4 * i + 2] << 16) | (q[4 * i + 3] << 24);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = static_cast<unsigned char>(q8(c[0][k]));
-      }
-    } else {
-      float* p = static_cast<float*>(base) + o;
-      if constexpr (V == 4) {
-        float4* d = reinterpret_cast<float4*>(p);
-        d[0] = make_float4(c[0][0], c[0][1], c[0][2], c[1][0]);
-        d[1] = make_float4(c[1][1], c[1][2], c[2][0], c[2][1]);
-        d[2] = make_float4(c[2][2], c[3][0], c[3][1], c[3][2]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = c[0][k];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const size_t o = ((static_cast<size_t>(b) * 3 + k) * rows + row) * W + x0;
-      if constexpr (U8) {
-        unsigned char* p = static_cast<unsigned char*>(base) + o;
-        if constexpr (V == 4)
-          *reinterpret_cast<unsigned*>(p) = q8(c[0][k]) | (q8(c[1][k]) << 8) | (q8(c[2][k]) << 16) | (q8(c[3][k]) << 24);
-        else
-          p[0] = static_cast<unsigned char>(q8(c[0][k]));
-      } else {
-        float* p = static_cast<float*>(base) + o;
-        if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(c[0][k], c[1][k], c[2][k], c[3][k]);
-        else p[0] = c[0][k];
-      }
-    }
-  }
 }
 
 template <int V, bool U8>

@@ -23,6 +23,24 @@ Differences, deliberate:
     which the reference does in the other order (scale, then interpolate): within an ulp of the reference's map, and bit-identical to
     `do_evaluation(rescale_to_full(d, (Hg, Wg)), gt)`.
 fp32 GPU tensors only: a CPU tensor raises, there is no CPU fallback.
+
+Optical flow, on the kernels of csrc/flow_frame.hip -- drop-ins with the reference's signatures, keys and return shapes:
+  flow_calc_error            architecture/data/evaluation/flow_pixel_error.py:9-96
+  do_flow_evaluation         architecture/data/evaluation/flow_eval.py:6-37
+and `flow_validation_metrics`, the fused multi-level form: up to four estimates [B,2,h,w] at their native resolutions against one
+ground truth per launch pair.
+Semantics kept from the reference:
+  - valid pixels: no NaN in either ground-truth component, lb < sqrt(gt_u^2 + gt_v^2) < ub (both strict) and, with sparse=True,
+    not (|gt_u| < 1e-12 and |gt_v| < 1e-12); err = sqrt((gt_u - est_u)^2 + (gt_v - est_v)^2), both radii in fp32 with every
+    operation rounded on its own, so the counts are the reference's;
+  - {1,2,3,5}px = count(err > t) / N * 100 in fp32, epe = mean err; all five are 0 when no pixel is valid; a NaN estimate inside the
+    mask leaves the counts alone and makes epe NaN;
+  - the early returns: CPU zeros when an argument is not a tensor, a warning and {} for a None in do_flow_evaluation;
+  - the quirk of do_flow_evaluation: it does NOT pass lb / ub on (flow_eval.py:35), so its bounds are always 0.0 and 400.
+Differences, deliberate:
+  - values are [1]-shaped fp32 views of one device buffer, counts exact integers, epe summed in fp64 in a fixed order, as above;
+  - flow_validation_metrics rescales a smaller or larger estimate with the arithmetic of `losses.rescale_to_full` (align-corners
+    bilinear, then u * Wg / w and v * Hg / h).  The reference has no rescale for flow: this one is defined by that torch composition.
 """
 import warnings
 
@@ -33,7 +51,8 @@ from .functional import _require_gpu, _stream
 
 KEYS = ('1px', '2px', '3px', '5px', 'epe')
 SPLITS = ('all', 'occ', 'noc')
-MAX_LEVELS = 4          # levels per ts_disp_metrics_fwd call
+MAX_LEVELS = 4          # levels per ts_disp_metrics_fwd / ts_flow_metrics_fwd call
+FLOW_SPARSE, FLOW_EST_HWC, FLOW_GT_HWC = 1, 2, 4          # flag word of ts_flow_metrics_fwd (include/ts_hip.h)
 
 
 def _zero_dict(prefix=''):
@@ -159,3 +178,80 @@ def metric_keys(n_levels, eval_ids=None, occlusion=True):
     """The keys validation_metrics returns for n_levels disparities, in its order (that of log_metric)."""
     splits = SPLITS if occlusion else SPLITS[:1]
     return ['metric_disparity_{}/{}_{}'.format(i, s, k) for i in _eval_ids(n_levels, eval_ids) for s in splits for k in KEYS]
+
+
+def _flow_metrics(ests, gt, lb, ub, sparse):
+    """One ts_flow_metrics_fwd call over 1..4 estimates [B,2,h,w] / [2,h,w] against gt [B,2,Hg,Wg] / [2,Hg,Wg]; out [n, 5]."""
+    _require_gpu(*ests, gt)
+    if not 1 <= len(ests) <= MAX_LEVELS:
+        raise ValueError("between 1 and %d flow maps per call (got %d)" % (MAX_LEVELS, len(ests)))
+    if gt.dim() not in (3, 4):
+        raise ValueError("the ground truth must be [2,H,W] or [B,2,H,W] (got %s)" % (tuple(gt.shape),))
+    if gt.shape[-3] != 2:
+        raise ValueError("flow should have horizontal and vertical dimension, but got {}".format(gt.shape[-3]))
+    B = gt.shape[0] if gt.dim() == 4 else 1
+    Hg, Wg = gt.shape[-2:]
+    dims = []
+    for e in ests:
+        if e.dim() != gt.dim() or e.shape[:-2] != gt.shape[:-2]:
+            raise ValueError("flow of shape %s against a ground truth of shape %s" % (tuple(e.shape), tuple(gt.shape)))
+        dims.append(tuple(e.shape[-2:]))
+    out_shape = (len(ests), len(KEYS))
+    if B * Hg * Wg == 0 or any(h * w == 0 for h, w in dims):
+        return torch.zeros(out_shape, device=gt.device, dtype=torch.float32)       # nothing valid: the reference's zeros
+    ests = [_lib.contiguous(e) for e in ests]
+    gt = _lib.contiguous(gt)
+    L = _lib.lib()
+    out = torch.empty(out_shape, device=gt.device, dtype=torch.float32)
+    ws = torch.empty(int(L.ts_flow_metrics_workspace_bytes(B, Hg, Wg)), device=gt.device, dtype=torch.uint8)
+    p = [_lib.ptr(e) for e in ests] + [None] * (MAX_LEVELS - len(ests))
+    hw = [v for d in dims + [(0, 0)] * (MAX_LEVELS - len(dims)) for v in d]
+    _lib.check(L.ts_flow_metrics_fwd(*p, len(ests), *hw, _lib.ptr(gt), B, Hg, Wg, float(lb), float(ub), FLOW_SPARSE if sparse else 0,
+                                     _lib.ptr(out), _lib.ptr(ws), _stream()), "ts_flow_metrics_fwd")
+    return out
+
+
+def flow_calc_error(est_flow=None, gt_flow=None, lb=0.0, ub=400, sparse=False):
+    """flow_pixel_error.py:9-96: {'1px', '2px', '3px', '5px': percent, 'epe'} of est_flow against gt_flow ([2,H,W] or [B,2,H,W], one
+    shape) over the pixels with lb < |gt| < ub, no NaN in gt and, with sparse, a ground truth that is not (0, 0)."""
+    if not torch.is_tensor(est_flow) or not torch.is_tensor(gt_flow):
+        return _zero_dict()
+    if est_flow.shape != gt_flow.shape:
+        raise ValueError("est_flow has shape %s, gt_flow %s" % (tuple(est_flow.shape), tuple(gt_flow.shape)))
+    out = _flow_metrics([est_flow], gt_flow, lb, ub, sparse)
+    return {k: out[0, i:i + 1] for i, k in enumerate(KEYS)}
+
+
+def do_flow_evaluation(est_flow, gt_flow, lb=0.0, ub=400, sparse=False):
+    """flow_eval.py:6-37: flow_calc_error after the reference's None checks (a warning and {}).  As in the reference, lb and ub are
+    accepted and NOT passed on (:35): the bounds are flow_calc_error's defaults, 0.0 and 400, whatever is given here."""
+    if est_flow is None:
+        warnings.warn('Estimated flow map is None')
+        return {}
+    if gt_flow is None:
+        warnings.warn('Reference ground truth flow map is None')
+        return {}
+    return flow_calc_error(est_flow, gt_flow, sparse=sparse)
+
+
+def flow_validation_metrics(flows, gt_flow, lb=0.0, ub=400, sparse=False, eval_ids=None):
+    """flow_calc_error of several estimates, fused.  flows: flow maps [B,2,h,w] at their NATIVE resolutions (each is read through the
+    align-corners rescale to gt_flow's size, u scaled by Wg / w and v by Hg / h); gt_flow [B,2,Hg,Wg]; eval_ids: the levels to
+    score (default every level), filtered to the levels present.
+    Returns {'metric_flow_{id}/all_1px': ..., ..., 'metric_flow_{id}/all_epe': ...}: [1]-shaped fp32 device tensors.
+    One launch pair per group of up to four levels."""
+    if gt_flow is None:
+        return {}
+    ids = _eval_ids(len(flows), eval_ids)
+    result = {}
+    for g in range(0, len(ids), MAX_LEVELS):
+        group = ids[g:g + MAX_LEVELS]
+        out = _flow_metrics([flows[i] for i in group], gt_flow, lb, ub, sparse)
+        for j, i in enumerate(group):
+            result.update({'metric_flow_{}/all_{}'.format(i, k): out[j, n:n + 1] for n, k in enumerate(KEYS)})
+    return result
+
+
+def flow_metric_keys(n_levels, eval_ids=None):
+    """The keys flow_validation_metrics returns for n_levels flow maps, in its order."""
+    return ['metric_flow_{}/all_{}'.format(i, k) for i in _eval_ids(n_levels, eval_ids) for k in KEYS]

@@ -27,7 +27,10 @@ Differences, deliberate:
   - `disp_from_uint16` takes torch.uint16 where this torch has it, or int16 storage REINTERPRETED as unsigned (the bits a 16-bit
     PNG reader hands over viewed as int16); an int32 tensor is accepted with its low 16 bits taken (a cast on the device);
     the valid mask comes from the kernel (torch's comparisons do not cover uint16).
-Out of scope, on purpose: decoding files (PIL / cv2), PFM / flow loaders.  ColorJitter / gamma, the random occlusion patches of
+  - `decode_kitti_flow` is the arithmetic of load_png (architecture/data/utils/load_flow.py:54-78) on the raw 16-bit channels of a
+    KITTI flow PNG: flow = (raw - 2^15) / 64, exact in fp32, both components 0 where the third channel is 0; the file itself is
+    decoded elsewhere.
+Out of scope, on purpose: decoding files (PIL / cv2), PFM / .flo loaders.  ColorJitter / gamma, the random occlusion patches of
 base.py:157-173 and the ground truth cut to a window whose origin lives on the device are in augment.py (`prepare_train_batch`).
 Cropping an fp32 ground-truth map is a tensor slice.
 uint8 GPU tensors only: a CPU tensor raises, there is no CPU fallback.
@@ -143,6 +146,34 @@ def disp_from_uint16(raw, scale=256.0, with_valid=False):
         disp = disp[0, 0]
         valid = valid[0, 0] if with_valid else None
     return (disp, valid.view(torch.bool)) if with_valid else disp
+
+
+def decode_kitti_flow(raw, layout='HWC'):
+    """load_flow.py:54-78 (`load_png`, the arithmetic): the three 16-bit channels of a KITTI flow map, [H,W,3] / [B,H,W,3] (layout
+    'HWC', what a PNG reader hands over) or [3,H,W] / [B,3,H,W] ('CHW') -> (flow, valid): flow fp32 [2,H,W] / [B,2,H,W] =
+    (raw - 2^15) / 64 with both components 0 where the third channel is 0, valid bool [1,H,W] / [B,1,H,W] = third channel != 0.
+    raw: torch.uint16, or torch.int16 whose bits are REINTERPRETED as unsigned.  One launch."""
+    what = "decode_kitti_flow"
+    if layout not in ('HWC', 'CHW'):
+        raise ValueError("layout must be 'HWC' or 'CHW' (got %r)" % (layout,))
+    if not torch.is_tensor(raw):
+        raise TypeError("%s: expected a tensor, got %s" % (what, type(raw).__name__))
+    _on_gpu(what, raw)
+    if raw.dtype != torch.int16 and raw.dtype != getattr(torch, "uint16", None):
+        raise TypeError("%s: raw must be uint16 or int16 (reinterpreted), got %s" % (what, raw.dtype))
+    if raw.dim() not in (3, 4) or raw.shape[-1 if layout == 'HWC' else -3] != 3 or raw.numel() == 0:
+        raise ValueError("%s: raw must be a non-empty [H,W,3] / [B,H,W,3] (HWC) or [3,H,W] / [B,3,H,W] (CHW) map, got %s"
+                         % (what, tuple(raw.shape)))
+    batched = raw.dim() == 4
+    B = raw.shape[0] if batched else 1
+    H, W = (raw.shape[-3], raw.shape[-2]) if layout == 'HWC' else (raw.shape[-2], raw.shape[-1])
+    r = _lib.contiguous(raw)
+    flow = torch.empty((B, 2, H, W), device=r.device, dtype=torch.float32)
+    valid = torch.empty((B, 1, H, W), device=r.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().ts_flow_u16_decode_fwd(_lib.ptr(r), B, H, W, CHW if layout == 'CHW' else 0, _lib.ptr(flow), _lib.ptr(valid),
+                                                 _stream()), "ts_flow_u16_decode_fwd")
+    valid = valid.view(torch.bool)
+    return (flow, valid) if batched else (flow[0], valid[0])
 
 
 def prepare_batch(left, right, K_norm, baseline, size, timestamp=0, disp_gt_raw=None, crop=None, k_size=None, num_scales=None,

@@ -1740,6 +1740,352 @@ def flow_cases(M):
     print("\n".join(lines))
 
 
+def save_fixed(name, **arrs):
+    """`save` with the archive's time stamps pinned, so that a fixture regenerates byte for byte."""
+    import zipfile
+    path = os.path.join(OUT, name + ".npz")
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrs.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w", force_zip64=True) as fh:
+                np.lib.format.write_array(fh, np.asanyarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v), allow_pickle=False)
+    print("wrote %-38s %8.1f KB" % (name + ".npz", os.path.getsize(path) / 1024))
+    return os.path.getsize(path)
+
+
+def _reference_flow_frame():
+    """The reference's flow_calc_error, do_flow_evaluation, flow_colormap.py and load_png.  The packages' __init__s import more than
+    this image has, so the files are loaded by path; do_flow_evaluation is taken from flow_eval.py's syntax tree and compiled as it
+    is (its relative import replaced by the loaded flow_calc_error); load_flow.py's `png` (pypng, absent here) is bound to a reader
+    that hands load_png the rows of an array in pypng's asDirect() form -- decoding the file is not what is restated."""
+    import ast
+    import importlib.util
+    import types
+    import warnings
+    os.environ.setdefault("MPLBACKEND", "Agg")
+
+    def by_path(name, *parts):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(ref_import.REFERENCE_ROOT, *parts))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+    pe = by_path("_ref_flow_pixel_error", "architecture", "data", "evaluation", "flow_pixel_error.py")
+    path = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "data", "evaluation", "flow_eval.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    fns = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "do_flow_evaluation"]
+    ns = {"torch": torch, "warnings": warnings, "flow_calc_error": pe.flow_calc_error}
+    exec(compile(ast.Module(body=fns, type_ignores=[]), path, "exec"), ns)
+    cm = by_path("_ref_flow_colormap", "architecture", "utils", "visualization", "flow_colormap.py")
+    held = {}
+
+    class Reader:
+        def __init__(self, filename):
+            self.a = held[filename]
+
+        def asDirect(self):
+            h, w, _ = self.a.shape
+            return w, h, (row.reshape(-1).tolist() for row in self.a), {'size': (w, h)}
+    before = sys.modules.get("png")
+    sys.modules["png"] = types.SimpleNamespace(Reader=Reader)
+    try:
+        lf = by_path("_ref_load_flow", "architecture", "data", "utils", "load_flow.py")
+    finally:
+        if before is None:
+            del sys.modules["png"]
+        else:
+            sys.modules["png"] = before
+
+    def load_png(raw_hw3):
+        held["mem"] = raw_hw3
+        return lf.load_png("mem")
+    return pe.flow_calc_error, ns["do_flow_evaluation"], cm, load_png
+
+
+FLOW_FRAME_TIE_CAP = 0.005
+
+
+def flow_frame_cases(M):
+    """tests/golden/flow_frame_*.npz: the reference's own flow_calc_error / do_flow_evaluation, flow_max_rad / flow_to_color /
+    flow_err_to_color / make_color_wheel and load_png on seeded flow maps on the CPU.
+
+    Inputs are stored as int16 in 1/64 px (KITTI's grid) plus the planted non-finite / huge / negative-zero values at their flat
+    indices.  Discrete outputs (percentages, class maps) are the reference's own; tests/flow_frame_ref.py must reproduce them
+    exactly, asserted here.  Continuous outputs (colours) are the reference's float32 images; dev_own / dev_given = the largest
+    distance of tests/flow_frame_ref.py from them over the cases with a maximum taken from the data / a given or shared maximum.
+    tie_* = pixels whose normalised radius lies within 4 x (the largest float32-vs-float64 deviation of that radius) of 1, the one
+    discontinuity rounding can move under a given or shared maximum; at most 0.5 % of a case's pixels, asserted here.  With the
+    map's own maximum the reference, which normalises in float64 by the float32 maximum, can find the pixel that set the maximum
+    a rounding outside the disc and darken it; bright_* marks those pixels (at most two per image, and maximal: asserted), where
+    the device is compared with tests/flow_frame_ref.py instead.
+    The rescaled case scores the torch composition F.interpolate(est, size, bilinear, align_corners=True) * (Wg / w, Hg / h) on the
+    CPU; tau = 16 units in the last place of the largest rescaled component (three lerps of at most three roundings each, the scale,
+    the difference, the radius: under ten half-units per component) and near_thr / tie_class = the pixels within tau of a
+    threshold / a class bound."""
+    import warnings
+    import torch.nn.functional as F
+    import flow_frame_ref as R
+    warnings.filterwarnings("ignore")
+    calc, do_eval, cm, load_png = _reference_flow_frame()
+    ALL = ("color_est", "color_gt", "color_est_given", "color_shared", "class", "class_val")
+    cases = {"dense": dict(hw=(48, 80), B=1, outs=("color_est", "color_gt", "class", "class_val"), planted=True),
+             "sparse": dict(hw=(40, 64), B=2, zero_block=True, outs=("class",)),
+             "none_valid": dict(hw=(16, 24), B=1, all_zero=True, outs=("color_gt", "class")),
+             "nonfinite": dict(hw=(40, 60), B=2, nonfinite=True, outs=("color_est", "color_gt", "class")),
+             "ragged": dict(hw=(50, 78), B=2, outs=("color_est", "class")),
+             "tiny1": dict(hw=(1, 1), B=1, outs=ALL, given=0.6),
+             "tiny35": dict(hw=(3, 5), B=2, outs=ALL, given=0.6),
+             "batch3": dict(hw=(30, 50), B=3, unknown_image=1, outs=("color_est", "color_est_given"), given=0.2),
+             "given_max": dict(hw=(49, 83), B=1, outs=("color_est_given",), given=25.0, absolute=True),
+             "shared": dict(hw=(44, 72), B=1, outs=("color_shared",)),
+             "rescaled": dict(hw=(56, 88), low=(14, 22), B=1, outs=("class",))}
+    assert tuple(cases) == R.CASES
+    VARIANTS = ((0.0, 400, False), (-1.0, 400, True), (2.0, 30.0, False), (-1.0, 400, False))          # (lb, ub, sparse) of metrics[0..3]
+    runs = {}
+    for ci, (name, c) in enumerate(cases.items()):
+        seed = synth.SEED0 + 9500 + ci
+        B = c["B"]
+        H, W = c["hw"]
+        h, w = c.get("low", c["hw"])
+        yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+        amp = synth.uniform(seed, "amp", (B, 1, 1), 12.0, 40.0).astype(np.float64)
+        gu = amp * (0.2 + 0.7 * np.sin(2 * np.pi * xx / max(W, 2) + amp) + 0.3 * np.cos(2 * np.pi * yy / max(H, 2)))
+        gv = 0.6 * amp * (0.1 + 0.8 * np.cos(2 * np.pi * xx / max(W, 2) - 0.5 * amp) - 0.4 * np.sin(2 * np.pi * yy / max(H, 2) + amp))
+        gt = np.stack([gu, gv], axis=1) + synth.uniform(seed, "gtn", (B, 2, H, W), -0.5, 0.5)
+        # errors spread over every class: many small ones, a few beyond 48 px
+        uu = synth.uniform(seed, "eu", (B, 1, H, W))
+        mag = np.where(uu < 0.3, 0.15, np.where(uu < 0.55, 0.6, np.where(uu < 0.75, 2.5, np.where(uu < 0.9, 9.0, np.where(uu < 0.97, 30.0, 70.0)))))
+        full = gt + synth.normal(seed, "en", (B, 2, H, W), 1.0).astype(np.float64) * mag
+        if c.get("all_zero"):
+            gt = np.zeros_like(gt)
+        if c.get("zero_block"):
+            gt[:, :, H // 4:H // 2, W // 8:W // 2] = 0.0
+        gq = np.round(gt * 64).astype(np.int16)
+        if (h, w) != (H, W):
+            iy, ix = (np.arange(h) * H) // h, (np.arange(w) * W) // w
+            eq = np.round(full[:, :, iy][..., ix] * np.array([w / W, h / H]).reshape(1, 2, 1, 1) * 64).astype(np.int16)
+        else:
+            eq = np.round(full * 64).astype(np.int16)
+        es, gs = [], []                                     # planted (flat index, value)
+        at = lambda b, ch, y, x, hh=H, ww=W: ((b * 2 + ch) * hh + y) * ww + x
+        if c.get("planted"):
+            # E exactly on the class end points 0.1875, 3.0 and 48.0; err exactly 1, 2, 3 and 5; the pair (3, +0.0), (3, -0.0)
+            for k, (du, dv) in enumerate(((12, 0), (192, 0), (0, 3072), (64, 0), (0, 128), (192, 256))):
+                eq[0, 0, 5, 10 + k] = gq[0, 0, 5, 10 + k] - du
+                eq[0, 1, 5, 10 + k] = gq[0, 1, 5, 10 + k] - dv
+            eq[0, :, 7, 20] = (192, 0)
+            eq[0, :, 7, 21] = (192, 0)
+            es.append((at(0, 1, 7, 21), np.float32(-0.0)))
+        if c.get("nonfinite"):
+            es += [(at(0, 0, 10, 20), np.float32(np.nan)), (at(0, 1, 11, 21), np.float32(np.inf)), (at(1, 0, 12, 22), np.float32(-np.inf)),
+                   (at(1, 1, 13, 23), np.float32(2e7)), (at(1, 0, 14, 24), np.float32(-3e7))]
+            gs += [(at(0, 0, 20, 30), np.float32(np.nan)), (at(0, 1, 21, 31), np.float32(np.nan)), (at(1, 1, 22, 32), np.float32(np.inf)),
+                   (at(1, 0, 23, 33), np.float32(2e7))]
+        if "unknown_image" in c:
+            b = c["unknown_image"]
+            es += [(at(b, 0, y, x), np.float32(3e7)) for y in range(H) for x in range(W)]
+        unpack = lambda lst: (np.array([i for i, _ in lst], dtype=np.int64), np.array([v for _, v in lst], dtype=np.float32))
+        ei, ev_ = unpack(es)
+        gi, gv_ = unpack(gs)
+        est, gtf = R.dequant(eq, ei, ev_), R.dequant(gq, gi, gv_)
+        gt_val = None
+        if "class_val" in c["outs"]:
+            r = synth.uniform(seed, "val", (B, H, W))
+            gt_val = np.where(r < 0.3, 0, np.where(r < 0.4, 1, 2)).astype(np.uint8)           # in halves: 0, 0.5, 1
+        runs[name] = dict(c=c, eq=eq, gq=gq, ei=ei, ev=ev_, gi=gi, gv=gv_, est=est, gt=gtf, gt_val=gt_val)
+
+    # ---- the reference's outputs
+    dev = {"own": 0.0, "given": 0.0}
+    dev_rad = 0.0
+    for name, r in runs.items():
+        c, est, gt = r["c"], r["est"], r["gt"]
+        B = c["B"]
+        H, W = c["hw"]
+        o = r["out"] = {}
+        if est.shape[-2:] != (H, W):
+            scale = torch.tensor([W / est.shape[-1], H / est.shape[-2]], dtype=torch.float32).view(1, 2, 1, 1)
+            full = (F.interpolate(T(est), size=(H, W), mode='bilinear', align_corners=True) * scale).numpy()
+            o["est_full"] = full
+            o["tau"] = np.float64(16 * np.spacing(np.float32(np.abs(full).max())))
+        else:
+            full = est
+        # metrics
+        met, nv = [], []
+        for lb, ub, sparse in VARIANTS:
+            d = calc(T(full.copy()), T(gt.copy()), lb=lb, ub=ub, sparse=sparse)
+            met.append([float(d[k]) for k in R.KEYS])
+            mine, n = R.calc_error(full, gt, lb, ub, sparse)
+            nv.append(n)
+            got = np.array(met[-1], dtype=np.float32)
+            assert np.array_equal(got[:4], mine[:4]), (name, lb, ub, sparse, got, mine)
+            assert np.array_equal(np.isnan(got), np.isnan(mine)), (name, got, mine)
+            if np.isfinite(got[4]):
+                assert abs(float(got[4]) - float(mine[4])) <= 2e-6 * abs(float(got[4])), (name, got, mine)
+        o["metrics"] = np.array(met, dtype=np.float32)
+        o["n_valid"] = np.array(nv, dtype=np.int64)
+        d = do_eval(T(full.copy()), T(gt.copy()), lb=2.0, ub=30.0, sparse=False)       # its lb / ub are not passed on
+        o["do_flow_evaluation"] = np.array([float(d[k]) for k in R.KEYS], dtype=np.float32)
+        assert np.array_equal(o["do_flow_evaluation"], o["metrics"][0], equal_nan=True), name
+        if "tau" in o:
+            near = []
+            for lb, ub, sparse in VARIANTS:
+                e = R.flow_error(full, gt)[R.valid_mask(gt, lb, ub, sparse)].astype(np.float64)
+                near.append([int((np.abs(e - t) <= o["tau"]).sum()) for t in (1, 2, 3, 5)])
+            o["near_thr"] = np.array(near, dtype=np.int64)
+        # colours
+        fh, gh = R.hwc(full), R.hwc(gt)
+        own_e = np.array([cm.flow_max_rad(fh[b].copy()) for b in range(B)], dtype=np.float32)
+        own_g = np.array([cm.flow_max_rad(gh[b].copy()) for b in range(B)], dtype=np.float32)
+        o["max_rad_est"], o["max_rad_gt"] = own_e, own_g
+        assert np.array_equal(own_e, np.array([R.max_rad(fh[b]) for b in range(B)])), name
+        assert np.array_equal(own_g, np.array([R.max_rad(gh[b]) for b in range(B)])), name
+
+        def color(key, maps, maxima, group):
+            """the reference's image of each map with its maximum (None: its own); the restatement's distance from it"""
+            nonlocal dev_rad
+            img = np.stack([cm.flow_to_color(maps[b].copy(), max_rad=None if maxima is None else float(maxima[b])) for b in range(B)])
+            assert img.dtype == np.float32 and img.shape == (B, H, W, 3)
+            mine = np.stack([R.flow_to_color(maps[b], None if maxima is None else maxima[b], data_max=maxima is None or group == "shared")
+                             for b in range(B)])
+            m = own_e if maps is fh else own_g
+            m = m if maxima is None else np.asarray(maxima, dtype=np.float32)
+            rad32 = np.stack([R.norm_radius(maps[b], m[b]) for b in range(B)])
+            kn = np.stack([R.known(maps[b]) for b in range(B)]).astype(np.float64)
+            den = (m.astype(np.float32) + np.float32(2.0 ** -52)).astype(np.float64).reshape(B, 1, 1)
+            rad64 = np.sqrt((kn[..., 0] / den) ** 2 + (kn[..., 1] / den) ** 2)
+            ok = np.isfinite(rad64)
+            if ok.any():
+                dev_rad = max(dev_rad, float(np.abs(rad32.astype(np.float64) - rad64)[ok].max()))
+            if maxima is None:
+                # The reference normalises in float64 by the float32 maximum, so the pixel(s) that set the maximum can come out
+                # at a radius a rounding above 1 and are then darkened (x 0.75).  The device never does that: those pixels are
+                # marked, left out of the distance, and must be the maximal ones.
+                bright = rad64 > 1
+                r0 = np.stack([R.radius(R.known(maps[b])[..., 0], R.known(maps[b])[..., 1]) for b in range(B)])
+                assert (r0[bright] == np.broadcast_to(m.reshape(B, 1, 1), r0.shape)[bright]).all() and bright.sum() <= 2 * B, (name, key)
+                o["bright_" + key[6:]] = bright
+                r["skip_" + key] = bright
+            o[key] = img
+            r["rad64_" + key] = rad64
+            r["mine_" + key] = mine
+            r["group_" + key] = "own" if maxima is None else "given"
+            return img
+
+        if "color_est" in c["outs"]:
+            color("color_est", fh, None, "own")
+        if "color_gt" in c["outs"]:
+            color("color_gt", gh, None, "own")
+        if "color_est_given" in c["outs"]:
+            given = np.full(B, c["given"], dtype=np.float32) if c.get("absolute") else (own_e * np.float32(c["given"])).astype(np.float32)
+            o["given_max"] = given
+            color("color_est_given", fh, given, "given")
+            if B * H * W >= 400:
+                outside = float((np.stack([R.norm_radius(fh[b], given[b]) for b in range(B)]) > 1).mean())
+                assert 0.03 <= outside <= 0.8, (name, outside)
+                o["outside_share"] = np.float64(outside)
+        if "color_shared" in c["outs"]:
+            shared = np.maximum(own_e, own_g)
+            o["shared_max"] = shared
+            color("color_shared_est", fh, shared, "shared")
+            color("color_shared_gt", gh, shared, "shared")
+        # classes
+        idx_of = lambda img: np.where(img.reshape(-1, 3).sum(axis=1) == 0, -1,
+                                      np.abs(img.reshape(-1, 1, 3) - (R.CLASS_RGB / np.float32(255))[None]).sum(axis=2).argmin(axis=1)).astype(np.int8)
+        if "class" in c["outs"]:
+            img = np.stack([cm.flow_err_to_color(fh[b].copy(), gh[b].copy()) for b in range(B)])
+            assert img.dtype == np.float32
+            cls = idx_of(img).reshape(B, H, W)
+            assert np.array_equal(R.class_colors(cls), img), name
+            assert np.array_equal(cls, R.err_class(full, gt)), name
+            o["class_idx"] = cls
+            if "tau" in o:
+                E = R.flow_error(full, gt).astype(np.float64)
+                tie = np.zeros(E.shape, dtype=bool)
+                for lo in R.CLASS_LO[1:]:
+                    tie |= np.abs(E - float(lo)) <= o["tau"]
+                assert tie.mean() <= FLOW_FRAME_TIE_CAP, (name, tie.mean())
+                o["tie_class"] = tie
+        if "class_val" in c["outs"]:
+            val = r["gt_val"].astype(np.float32) / np.float32(2)
+            img = np.stack([cm.flow_err_to_color(fh[b].copy(), gh[b].copy(), val[b].copy()) for b in range(B)])
+            cls = idx_of(img).reshape(B, H, W)
+            assert np.array_equal(R.class_colors(cls), img), name
+            assert np.array_equal(cls, R.err_class(full, gt, val)), name
+            o["class_val_idx"] = cls
+        for key in [k for k in r if k.startswith("mine_")]:
+            k = key[5:]
+            d = np.abs(r[key].astype(np.float64) - o[k].astype(np.float64))
+            if r["group_" + k] == "given":                  # the branch may differ on a near-tie pixel: measured away from them below
+                r["diff_" + k] = d
+            else:
+                away = d[~r["skip_" + k]]
+                if away.size:
+                    dev["own"] = max(dev["own"], float(away.max()))
+    tau_rad = 4 * dev_rad
+    for name, r in runs.items():
+        o = r["out"]
+        for key in [k for k in r if k.startswith("diff_")]:
+            k = key[5:]
+            tie = np.abs(r["rad64_" + k] - 1.0) <= tau_rad
+            assert tie.mean() <= FLOW_FRAME_TIE_CAP or tie.size < 400, (name, k, tie.mean())
+            o["tie_" + k[6:]] = tie
+            away = r[key][~tie]
+            if away.size:
+                dev["given"] = max(dev["given"], float(away.max()))
+    wheel = cm.make_color_wheel()
+    assert wheel.shape == (55, 3) and np.array_equal(wheel, R.make_color_wheel())
+    lines = ["flow_frame_*.npz: tools/gen_golden.py --only-flow-frame, numpy %s, torch %s CPU -- the reference's own flow_calc_error /" % (np.__version__, torch.__version__),
+             "do_flow_evaluation (architecture/data/evaluation), make_color_wheel / flow_max_rad / flow_to_color / flow_err_to_color",
+             "(architecture/utils/visualization/flow_colormap.py) and the arithmetic of load_png (architecture/data/utils/load_flow.py) on seeded maps.",
+             "Inputs: int16 in 1/64 px plus planted NaN / inf / > 1e7 / -0.0 values.  metrics[0..3] = (lb, ub, sparse) of %s;" % (VARIANTS,),
+             "do_flow_evaluation was called with lb=2, ub=30 and equals metrics[0]: it does not pass its bounds on.",
+             "Percentages, maximum radii, class maps and the decode are the reference's and tests/flow_frame_ref.py reproduces them exactly (asserted).",
+             "Colours: dev_own = %.3g (maximum from the data), dev_given = %.3g (given or shared maximum, away from the near-tie pixels) = the" % (dev["own"], dev["given"]),
+             "largest |tests/flow_frame_ref.py - reference| over those cases; a device result may lie 4 x that from the reference.",
+             "Near ties: the float32 normalised radius deviates from its float64 value by at most %.3g; tie_* = |rad - 1| <= 4 x that = %.3g," % (dev_rad, tau_rad),
+             "at most %.1f %% of a case's pixels (asserted).  bright_* = the pixels that set a map's own maximum and that the reference, normalising in" % (100 * FLOW_FRAME_TIE_CAP),
+             "float64 by the float32 maximum, finds a rounding outside the disc and darkens; the device keeps them inside (left out of dev_own)."]
+    total = 0
+    for name, r in runs.items():
+        c, o = r["c"], r["out"]
+        arrs = dict(est_q64=r["eq"], gt_q64=r["gq"], est_special_idx=r["ei"], est_special_val=r["ev"], gt_special_idx=r["gi"],
+                    gt_special_val=r["gv"], dev_own=np.float64(dev["own"]), dev_given=np.float64(dev["given"]), tau_rad=np.float64(tau_rad))
+        if r["gt_val"] is not None:
+            arrs["gt_val_half"] = r["gt_val"]
+        if name == "dense":
+            arrs["wheel"] = wheel
+        arrs.update(o)
+        size = save_fixed("flow_frame_" + name, **arrs)
+        assert size <= 260 * 1024, (name, size)
+        total += size
+        ties = {k: int(v.sum()) for k, v in o.items() if k.startswith("tie_") or k.startswith("bright_")}
+        lines.append("flow_frame_%-10s B=%d %dx%d%s  N = %s  outputs %s%s%s; %.0f KB"
+                     % (name, c["B"], c["hw"][0], c["hw"][1], (" est %dx%d" % c["low"]) if "low" in c else "", o["n_valid"].tolist(),
+                        ", ".join(c["outs"]), ("  near ties %s" % ties) if ties else "",
+                        ("  tau %.3g near thresholds %s" % (o["tau"], o["near_thr"].tolist())) if "tau" in o else "", size / 1024))
+    # KITTI 16-bit flow
+    seed = synth.SEED0 + 9590
+    B, H, W = 2, 20, 31
+    raw = np.empty((B, H, W, 3), dtype=np.uint16)
+    raw[..., :2] = np.clip(32768 + np.round(synth.normal(seed, "uv", (B, H, W, 2), 40.0) * 64), 0, 65535).astype(np.uint16)
+    raw[..., 2] = (synth.uniform(seed, "ok", (B, H, W)) >= 0.3).astype(np.uint16)
+    raw[0, 0, 0] = (0, 65535, 1)
+    raw[0, 0, 1] = (65535, 0, 7)
+    raw[1, 3, 4] = (12345, 54321, 0)
+    ref = np.stack([load_png(raw[b]) for b in range(B)])
+    assert ref.dtype == np.float32 and ref.shape == (B, H, W, 3)
+    flow, valid = R.decode_kitti(raw)
+    assert np.array_equal(flow, np.moveaxis(ref[..., :2], -1, 1)) and np.array_equal(valid[:, 0], ref[..., 2] != 0)
+    size = save_fixed("flow_frame_kitti", raw=raw, flow=np.ascontiguousarray(np.moveaxis(ref[..., :2], -1, 1)), valid=(ref[..., 2] != 0)[:, None])
+    total += size
+    lines.append("flow_frame_kitti      B=%d %dx%d uint16 [B,H,W,3], %.0f %% invalid: load_png's flow and third channel; %.0f KB"
+                 % (B, H, W, 100 * float((raw[..., 2] == 0).mean()), size / 1024))
+    lines.append("total %.0f KB" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_flow_frame.txt"), "w") as fh_:
+        fh_.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -1771,6 +2117,9 @@ def main():
         return
     if "--only-flow" in sys.argv:
         flow_cases(M)
+        return
+    if "--only-flow-frame" in sys.argv:
+        flow_frame_cases(M)
         return
     if "--only-augment" in sys.argv:
         augment_cases(M)
