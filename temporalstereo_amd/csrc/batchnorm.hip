@@ -71,6 +71,34 @@ __device__ __forceinline__ void block_sum2(float& a, float& b) {      // 256 thr
   }
 }
 
+// The pivot scheme is only as good as the pivot is typical of its channel: E[x'^2] is var + d^2 for a pivot d away from the mean, and
+// the fp32 partial sums carry ~1e-7 of THAT into the variance (a first element 30 std out: 2.6e-5 of the variance in the two- and
+// three-launch forms, tests/test_batchnorm_gpu.py [2,3,2135]).  The mean survives (it is linear in the sums), so where the sums
+// themselves say that the pivot was more than 8 std out, the variance is taken again about the mean.  Anywhere else nothing changes.
+__device__ __forceinline__ bool bn_pivot_far(double m1, double v) { return m1 * m1 > 64.0 * v; }
+
+// sum (x - m)^2 / (B * N) of channel c in double, by wave 0 of the calling workgroup in a fixed order (the same in every kernel, so the
+// launch forms agree to the bit); every thread gets the result.  All threads of the workgroup must call it.
+__device__ __forceinline__ double channel_var_about(const float* __restrict__ x, int c, float m, int B, long long N, long long bstride,
+                                                    long long cstride) {
+  __shared__ double bv;
+  if (threadIdx.x < 64) {
+    double q = 0.0;
+    for (int b = 0; b < B; ++b) {
+      const float* xp = x + static_cast<size_t>(b) * bstride + static_cast<size_t>(c) * cstride;
+      for (long long i = threadIdx.x; i < N; i += 64) {
+        const double d = static_cast<double>(xp[i]) - static_cast<double>(m);
+        q += d * d;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    if (threadIdx.x == 0) bv = q / (static_cast<double>(B) * static_cast<double>(N));
+  }
+  __syncthreads();
+  return bv;
+}
+
 struct BN {
   int B, C;
   long long N;                  // elements per (batch, channel) plane block (D*H*W), contiguous
@@ -124,11 +152,12 @@ bn_stats_finish(const float* __restrict__ x, const float2* __restrict__ partial,
     s += __shfl_xor(s, o, 64);
     q += __shfl_xor(q, o, 64);
   }
+  const double cnt = static_cast<double>(p.B) * static_cast<double>(p.N);
+  const double m1 = s / cnt;
+  double v = fmax(q / cnt - m1 * m1, 0.0);
+  const float m = static_cast<float>(m1 + static_cast<double>(x[static_cast<size_t>(c) * p.cstride]));
+  if (bn_pivot_far(m1, v)) v = channel_var_about(x, c, m, p.B, p.N, p.bstride, p.cstride);
   if (threadIdx.x == 0) {
-    const double cnt = static_cast<double>(p.B) * static_cast<double>(p.N);
-    const double m1 = s / cnt;
-    const double v = fmax(q / cnt - m1 * m1, 0.0);
-    const float m = static_cast<float>(m1 + static_cast<double>(x[static_cast<size_t>(c) * p.cstride]));
     mean[c] = m;
     var[c] = static_cast<float>(v);
     if (running_mean) {
@@ -308,8 +337,9 @@ bn_finish_apply_act_kernel(const float* __restrict__ x, const float2* __restrict
   channel_partial_sum(partial, c, npart, s, q);
   const double cnt = static_cast<double>(p.B) * static_cast<double>(p.N);
   const double m1 = s / cnt;
-  const double v = fmax(q / cnt - m1 * m1, 0.0);
+  double v = fmax(q / cnt - m1 * m1, 0.0);
   const float m = static_cast<float>(m1 + static_cast<double>(pivot));
+  if (bn_pivot_far(m1, v)) v = channel_var_about(x, c, m, p.B, p.N, p.xb, p.xc);
   const float vf = static_cast<float>(v);
   if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
     mean[c] = m;
@@ -411,8 +441,9 @@ bn_train_fwd_small_kernel(const float* __restrict__ x, float* __restrict__ mean,
   block_sum2_double(ds, dq);
   const double cnt = static_cast<double>(p.B) * static_cast<double>(p.N);
   const double m1 = ds / cnt;
-  const double v = fmax(dq / cnt - m1 * m1, 0.0);
+  double v = fmax(dq / cnt - m1 * m1, 0.0);
   const float m = static_cast<float>(m1 + static_cast<double>(pivot));
+  if (bn_pivot_far(m1, v)) v = channel_var_about(x, c, m, p.B, p.N, p.xb, p.xc);
   const float vf = static_cast<float>(v);
   if (threadIdx.x == 0) {
     mean[c] = m;
