@@ -568,6 +568,52 @@ int ts_flow_corr_lookup_bwd(const float* pyramid, const float* coords, const flo
 int ts_flow_corr_pyramid_bwd(const float* grad_pyramid, const float* fmap1, const float* fmap2, float* grad_fmap1, float* grad_fmap2,
                              int B, int C, int H, int W, int levels, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SPP3D: the memory-bound pieces of the 3-D pyramid pooling module (ABI 18).
+ * Replaces the avg_pool3d / interpolate / cat of SPP3D.forward  architecture/modeling/aggregation/utils/SPP3D.py:38-49; its
+ * convolutions run on the (k,1,1) and (1,3,3) families above.  x [B,C,D,H,W] (batch / channel strides in elements, D*H*W dense).
+ * Level i of stride s_i (num_levels <= 4, unused strides ignored): box k_i = (min(D,s_i), min(H,s_i), min(W,s_i)), n_i = floor(dim / k_i)
+ * cells per axis, a trailing remainder is dropped.
+ *   pooled: ONE buffer; level i is [B][C][n_i] contiguous at float offset B*C * sum_{l<i} |n_l|.
+ * ts_spp3d_pool_fwd    every level in one launch; a level whose box is a whole multiple of the previous level's is summed from that
+ *                      level's partial sums (LDS), the others from x.
+ * ts_spp3d_pool_bwd    grad_x[v] = addend[v] + sum_i g_i[cell_i(v)] / |k_i| over the levels whose covered region holds v, OVERWRITTEN;
+ *                      g_i [B,C,n_i] dense, one pointer per level (the cotangents arrive as separate tensors); addend (strided like x, may be NULL) is the part of the concat gradient that belongs to x.
+ * ts_spp3d_expand_fwd  cat [B, C + Cl*L, D, H, W] = [x | resize(lv0) | ...]: lv_i [B,Cl,n_i] dense, resized trilinearly with
+ *                      align_corners (the framework's fp32 order: scale (n_in-1)/(n_out-1), pos = scale*o, floor, upper index clamped).
+ * ts_spp3d_expand_bwd  g_i [B,Cl,n_i] OVERWRITTEN from channels [C, C + Cl*L) of grad_cat (strided); one wave per coarse cell gathers
+ *                      over that cell's support.  (The gradient of x through the concat is a view of grad_cat: no kernel.)
+ * ts_depth_sum3_fwd    y[d] = act(scale[c] * (z0[d-1] + z1[d] + z2[d+1]) + shift[c]), planes outside [0,D) zero; scale / shift may be
+ *                      NULL (1 / 0); act 0 none, 1 SiLU, 2 ReLU; y may be z1.  With z0 and z2 exchanged it sums the three data
+ *                      gradients of a 3x3x3 convolution run as three (1,3,3) convolutions.
+ * No atomics: every entry is bit-reproducible.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, num_levels < 1, a stride
+ * < 1, overlapping strides), num_levels > 4, an axis >= 2^20, B * channels > 65535 (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL).
+ * ---------------------------------------------------------------------------------------- */
+int ts_spp3d_pool_fwd(const float* x, float* pooled, int B, int C, int D, int H, int W, int num_levels, int s0, int s1, int s2, int s3,
+                      long long x_bstride, long long x_cstride, void* stream);
+int ts_spp3d_pool_bwd(const float* g0, const float* g1, const float* g2, const float* g3, const float* addend, float* grad_x, int B,
+                      int C, int D, int H, int W, int num_levels, int s0, int s1, int s2, int s3, long long addend_bstride,
+                      long long addend_cstride, long long gx_bstride, long long gx_cstride, void* stream);
+int ts_spp3d_expand_fwd(const float* x, const float* lv0, const float* lv1, const float* lv2, const float* lv3, float* cat, int B, int C,
+                        int Cl, int D, int H, int W, int num_levels, int s0, int s1, int s2, int s3, long long x_bstride,
+                        long long x_cstride, void* stream);
+int ts_spp3d_expand_bwd(const float* grad_cat, float* g0, float* g1, float* g2, float* g3, int B, int C, int Cl, int D, int H, int W,
+                        int num_levels, int s0, int s1, int s2, int s3, long long g_bstride, long long g_cstride, void* stream);
+int ts_depth_sum3_fwd(const float* z0, const float* z1, const float* z2, const float* scale, const float* shift, float* y, int B, int C,
+                      int D, int H, int W, int act, long long z0_bstride, long long z0_cstride, long long z1_bstride,
+                      long long z1_cstride, long long z2_bstride, long long z2_cstride, long long y_bstride, long long y_cstride,
+                      void* stream);
+
+/* Train-mode BatchNorm -> activation backward for FEW values per channel (B * N <= 4096; a coarse SPP3D level has down to two), carried
+ * in fp64 up to the final rounding: y [B,C,N] the raw convolution output, g the incoming cotangent, dy OVERWRITTEN (all three strided),
+ * sum_g [C] = sum of the cotangent behind the activation (the gradient of beta), sum_gx [C] = its sum against xhat (the gradient of
+ * gamma).  The batch statistics are formed again from y.  With two values per channel the result is what a cancellation leaves,
+ * O(eps / var) of its terms: an fp32 rounding of xhat costs 2^-24 var / eps of it.  gamma / beta may be NULL (1 / 0); act 0 | 1 | 2.
+ * Checks: sizes, one value per channel, overlapping strides (TS_ERR_SHAPE), B * N > 4096 (TS_ERR_UNSUPPORTED), pointers (TS_ERR_NULL). */
+int ts_bn_small_train_bwd(const float* y, const float* g, const float* gamma, const float* beta, float* sum_g, float* sum_gx, float* dy,
+                          int B, int C, int N, long long y_bstride, long long y_cstride, long long g_bstride, long long g_cstride,
+                          long long dy_bstride, long long dy_cstride, float eps, int act, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

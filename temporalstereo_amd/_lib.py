@@ -172,6 +172,12 @@ SIGNATURES = {
     "ts_flow_corr_lookup_fwd": (c_int, [c_f32p] * 3 + [c_int] * 5 + [c_ptr]),
     "ts_flow_corr_lookup_bwd": (c_int, [c_f32p] * 5 + [c_int] * 6 + [c_ptr]),
     "ts_flow_corr_pyramid_bwd": (c_int, [c_f32p] * 5 + [c_int] * 5 + [c_ptr]),
+    "ts_spp3d_pool_fwd": (c_int, [c_f32p] * 2 + [c_int] * 10 + [ctypes.c_longlong] * 2 + [c_ptr]),
+    "ts_spp3d_pool_bwd": (c_int, [c_f32p] * 6 +[c_int] * 10 + [ctypes.c_longlong] * 4 + [c_ptr]),
+    "ts_spp3d_expand_fwd": (c_int, [c_f32p] * 6 + [c_int] * 11 + [ctypes.c_longlong] * 2 + [c_ptr]),
+    "ts_spp3d_expand_bwd": (c_int, [c_f32p] * 5 + [c_int] * 11 + [ctypes.c_longlong] * 2 + [c_ptr]),
+    "ts_depth_sum3_fwd": (c_int, [c_f32p] * 6 + [c_int] * 6 + [ctypes.c_longlong] * 8 + [c_ptr]),
+    "ts_bn_small_train_bwd": (c_int, [c_f32p] * 7 + [c_int] * 3 + [ctypes.c_longlong] * 6 + [c_float, c_int, c_ptr]),
     "ts_reproject_memory_workspace_bytes": (c_size, [c_int] * 5),
     "ts_reproject_memory_fwd": (c_int, [c_f32p, ctypes.c_longlong, c_int, c_int, c_f32p, c_f32p, c_int, c_f32p, c_int, c_int,
                                         c_f32p, c_int, c_f32p, c_f32p, c_f32p, c_float, c_float, c_f32p, c_f32p, c_f32p,

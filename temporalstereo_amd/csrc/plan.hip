@@ -109,6 +109,9 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_flow_corr_pyramid_fwd),   TS_PLAN_OP(ts_flow_corr_lookup_fwd),
     TS_PLAN_OP(ts_flow_corr_lookup_bwd),    TS_PLAN_OP(ts_flow_corr_pyramid_bwd),
     TS_PLAN_OP(ts_flow_metrics_fwd),        TS_PLAN_OP(ts_flow_render_fwd),         TS_PLAN_OP(ts_flow_u16_decode_fwd),
+    TS_PLAN_OP(ts_spp3d_pool_fwd),          TS_PLAN_OP(ts_spp3d_pool_bwd),
+    TS_PLAN_OP(ts_spp3d_expand_fwd),        TS_PLAN_OP(ts_spp3d_expand_bwd),        TS_PLAN_OP(ts_depth_sum3_fwd),
+    TS_PLAN_OP(ts_bn_small_train_bwd),
 };
 
 struct Call {

@@ -967,6 +967,7 @@ def _all_gather_flat(out, part, group):
 
 import os as _os
 _BN_FUSED = _os.environ.get("TS_BN_FUSED", "1") != "0"
+_BN_FEW_VALUES = 4096       # csrc/spp3d.hip kSmallBnMax
 _EXCHANGES = [0]            # SyncBatchNorm exchanges issued by this process (forward all_gathers + backward all_reduces; bench.py reports them per step)
 
 
@@ -987,7 +988,9 @@ class _ConvBNAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, family, geom, eps, momentum, act, training, group,
-                counter=None, may_fold=False, addend=None):
+                counter=None, may_fold=False, addend=None, few_values=False):
+        # few_values: with a single rank and at most 4096 values per channel the train-mode backward is ts_bn_small_train_bwd (fp64
+        # inside: SPP3D's coarse levels have down to two values per channel, where the gradient is what a cancellation leaves)
         # addend (family "hw" only): [B, Cout, 1, Ho, Wo], added to every depth plane of the raw convolution (first_layer_split)
         ctx.has_addend = addend is not None
         if addend is not None and family != "hw":
@@ -1001,11 +1004,15 @@ class _ConvBNAct(torch.autograd.Function):
                     return _hw_forward(x, weight, geom[0], geom[1], geom[2], None, fold, act, addend=addend)[1]
                 if family == "dc":
                     return _dc_forward(x, weight, None, fold, act)[1]
+                if family == "hw3":
+                    return _hw3_forward(x, weight, None, fold, act)[1]
                 return _d_forward(x, weight, geom[0], geom[1], geom[2], geom[3], None, fold, act)[1]
         if family == "hw":
             x, y, cg = _hw_forward(x, weight, geom[0], geom[1], geom[2], bias, addend=addend)
         elif family == "dc":
             x, y, cg = _dc_forward(x, weight, bias)
+        elif family == "hw3":
+            x, y, cg = _hw3_forward(x, weight, bias)
         else:
             x, y, cg = _d_forward(x, weight, geom[0], geom[1], geom[2], geom[3], bias)
         B, C = y.shape[0], y.shape[1]
@@ -1013,6 +1020,7 @@ class _ConvBNAct(torch.autograd.Function):
         L = _lib.lib()
         n_total = float(B * N)
         out = torch.empty_like(y)
+        ctx.few = bool(few_values) and training and group is None and 2 <= B * N <= _BN_FEW_VALUES
         if training and group is None and _BN_FUSED:
             # single rank: statistics and their use in two launches (ts_bn_train_fwd)
             mean = torch.empty(C, device=y.device, dtype=torch.float32)
@@ -1073,6 +1081,12 @@ class _ConvBNAct(torch.autograd.Function):
         L = _lib.lib()
         s1 = torch.empty(C, device=y.device, dtype=torch.float32)
         s2 = torch.empty_like(s1)
+        if ctx.few:
+            dy = torch.empty_like(y)
+            _lib.check(L.ts_bn_small_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy),
+                                               B, C, N, y.stride(0), y.stride(1), g.stride(0), g.stride(1), dy.stride(0), dy.stride(1),
+                                               eps, act, _stream()), "ts_bn_small_train_bwd")
+            return _ConvBNAct._conv_backward(ctx, x, weight, dy, family, cg, has_bias, (s2, s1) if gamma is not None else (None, None))
         ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
         if training and group is None and _BN_FUSED:
             dy = torch.empty_like(y)
@@ -1109,6 +1123,8 @@ class _ConvBNAct(torch.autograd.Function):
             dx, dw = _hw_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         elif family == "dc":
             dx, dw = _dc_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        elif family == "hw3":
+            dx, dw = _hw3_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         else:
             dx, dw = _d_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         gbias = None
@@ -1117,12 +1133,13 @@ class _ConvBNAct(torch.autograd.Function):
         gadd = None
         if ctx.has_addend and ctx.needs_input_grad[16]:
             gadd = dy.sum(dim=2, keepdim=True)                     # the D-invariant term reaches every depth plane
-        return dx, dw, gbias, gaffine[0], gaffine[1], None, None, None, None, None, None, None, None, None, None, None, gadd
+        return dx, dw, gbias, gaffine[0], gaffine[1], None, None, None, None, None, None, None, None, None, None, None, gadd, None
 
 
-def conv_bn_act(x, weight, bias, bn, activation, family, geom, transposed=False, addend=None):
+def conv_bn_act(x, weight, bias, bn, activation, family, geom, transposed=False, addend=None, few_values=False):
     """Fused wrapper forward (see _ConvBNAct).  `bn`: an nn.BatchNorm*d / dist.SyncBatchNorm module; `activation`: None | 'SiLU' |
-    'ReLU'; family 'hw' geom (stride, dilation, transposed) / family 'd' geom (stride, dilation, padding, transposed)."""
+    'ReLU'; family 'hw' geom (stride, dilation, transposed) / family 'd' geom (stride, dilation, padding, transposed) / family 'hw3'
+    (3x3x3, stride 1, padding 1: three (1,3,3) launches and a depth sum, see _hw3_forward) geom (1, 1, False)."""
     # parameters / buffers straight from the module's dictionaries: nn.Module.__getattr__ (the fallback every `bn.weight`,
     # `bn.running_mean` ... goes through) was ~10 lookups x 180 wrappers per frame
     if _WGRAD_DEFER is not None and weight.requires_grad and torch.is_grad_enabled():
@@ -1142,7 +1159,7 @@ def conv_bn_act(x, weight, bias, bn, activation, family, geom, transposed=False,
     may_fold = (not training) and (not torch.is_grad_enabled() or not any(
         t is not None and t.requires_grad for t in (x, weight, bias, gamma, beta, addend)))
     return _ConvBNAct.apply(x, weight, bias, gamma, beta, rmean, Bf.get("running_var"), family, geom, d["eps"], momentum,
-                            BN_ACT[activation], training, group, counter, may_fold, addend)
+                            BN_ACT[activation], training, group, counter, may_fold, addend, few_values)
 
 
 def conv3d_supported(weight_shape, stride, padding, dilation, groups, transposed=False, output_padding=(0, 0, 0)):
@@ -1200,6 +1217,264 @@ def conv_transpose3d(x, weight, bias=None, stride=(1, 2, 2), padding=(0, 1, 1), 
         raise NotImplementedError("conv_transpose3d: kernel %s stride %s padding %s output_padding %s has no HIP kernel"
                                   % (tuple(weight.shape[2:]), stride, padding, output_padding))
     return y if bias is None else y + bias.view(1, -1, 1, 1, 1)
+
+
+# ---------------------------------------------------------------------------------------------- SPP3D
+# (The slice launches are spelt out in _hw3_slice_conv rather than routed through _hw_forward / _hw_backward: those take a whole
+# (1,3,3) weight, allocate their own outputs and are shared by every layer of the model; the slice's weight layout goes through the
+# same WeightLayouts table, so a training step lays each slice out once.)
+# 3x3x3 convolution (stride 1, padding 1) as three (1,3,3) convolutions: y[d] = Z_0[d-1] + Z_1[d] + Z_2[d+1] with Z_kd the (1,3,3)
+# convolution of x with weight[:, :, kd] (family "hw3" of conv_bn_act; SPP3D.fuse[0], utils/SPP3D.py:34).  The slice of the weight is
+# never copied: element (ci, co, tap) of slice kd sits at kd * 9 + ci * 27 + co * Cin * 27 + tap of the parameter.
+def _hw3_check(x, weight):
+    _require_gpu(x, weight)
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[0] > 64 or x.dim() != 5 or x.shape[1] != weight.shape[1]:
+        raise ValueError("conv3d_k333: weight [Cout <= 64, Cin, 3, 3, 3] and x [B, Cin, D, H, W] (got %s and %s)"
+                         % (tuple(weight.shape), tuple(x.shape)))
+
+
+def _hw3_slice_conv(src, weight, kd, dst, B, Cin, Cout, D, H, W, backward):
+    """dst = (1,3,3) convolution of src with slice kd of the 3x3x3 `weight` [Cout, Cin, 3, 3, 3] (contiguous); backward: the data
+    gradient of that convolution (src = dy with Cout channels, dst with Cin, taps flipped in the plane)."""
+    L = _lib.lib()
+    wv = weight.detach().reshape(-1)[kd * 9:]
+    cin, cout = (Cout, Cin) if backward else (Cin, Cout)                # of the convolution that is launched
+    wspec = (Cin * 27, 27, 1, 1) if backward else (27, Cin * 27, 1, 0)
+    if _x6_conv(src, wv, wspec, dst, B, cin, cout, D, H, W, 1):
+        return
+    bpad = _cpad(cout)
+
+    def make(w, out=None):          # [cin][9][pad(cout)] of the slice, from its strides inside the parameter
+        if out is None:
+            out = torch.empty((cin, 9, bpad), device=w.device, dtype=torch.float32)
+        _lib.check(L.ts_conv_weight_layout(_lib.ptr(w.detach().reshape(-1)[kd * 9:]), _lib.ptr(out), cin, 9, cout, bpad, wspec[0], wspec[1], 1,
+                                           wspec[3], _stream()), "ts_conv_weight_layout")
+        return out
+    # kept and refreshed with the other layouts of a training step (WeightLayouts.get_custom), parameters only -- as _layout does
+    w_t = _LAYOUTS.get_custom(weight, "hw3/%d/%d" % (kd, int(backward)), make) if (_LAYOUTS is not None and weight.is_leaf) else make(weight)
+    if backward:
+        rc = L.ts_conv3d_hw_bwd_data(_lib.ptr(src), _lib.ptr(w_t), _lib.ptr(dst), B, Cin, Cout, D, H, W, 1, 1, 0, src.stride(0), src.stride(1),
+                                     dst.stride(0), dst.stride(1), _stream())
+        _lib.check(rc, "ts_conv3d_hw_bwd_data")
+        return
+    wsb = _q("ts_conv3d_hw_workspace_bytes", B, Cin, Cout, D, H, W, 1, 0)
+    ws = torch.empty(wsb, device=src.device, dtype=torch.uint8) if wsb else None
+    rc = L.ts_conv3d_hw_fwd(_lib.ptr(src), _lib.ptr(w_t), None, None, _lib.ptr(dst), B, Cin, Cout, D, H, W, 1, 1, 0, 0, 0.0,
+                            src.stride(0), src.stride(1), dst.stride(0), dst.stride(1), None, 0, _lib.ptr(ws), wsb, _stream())
+    _lib.check(rc, "ts_conv3d_hw_fwd")
+
+
+def _depth_sum3(z0, z1, z2, y, scale=None, shift=None, act=0):
+    B, C, D, H, W = y.shape
+    rc = _lib.lib().ts_depth_sum3_fwd(_lib.ptr(z0), _lib.ptr(z1), _lib.ptr(z2), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, D, H, W,
+                                      int(act), z0.stride(0), z0.stride(1), z1.stride(0), z1.stride(1), z2.stride(0), z2.stride(1),
+                                      y.stride(0), y.stride(1), _stream())
+    _lib.check(rc, "ts_depth_sum3_fwd")
+
+
+def _hw3_forward(x, weight, bias=None, fold=None, act=0):
+    """Raw Conv3d 3x3x3, stride 1, padding 1 (+ bias); `fold`: see _hw_forward (applied by the depth sum's epilogue)."""
+    _hw3_check(x, weight)
+    x = x.contiguous()
+    weight = weight if weight.is_contiguous() else weight.contiguous()
+    B, Cin, D, H, W = x.shape
+    Cout = weight.shape[0]
+    y = torch.empty((B, Cout, D, H, W), device=x.device, dtype=torch.float32)
+    _hw3_slice_conv(x, weight, 1, y, B, Cin, Cout, D, H, W, False)         # the centre slice straight into y
+    z0 = z2 = y                                                             # D == 1: neither neighbour is read
+    if D > 1:
+        z0, z2 = torch.empty_like(y), torch.empty_like(y)
+        _hw3_slice_conv(x, weight, 0, z0, B, Cin, Cout, D, H, W, False)
+        _hw3_slice_conv(x, weight, 2, z2, B, Cin, Cout, D, H, W, False)
+    sc, sh = fold if fold is not None else (None, bias.detach().contiguous() if bias is not None else None)
+    if D > 1 or sc is not None or sh is not None or act:
+        _depth_sum3(z0, y, z2, y, sc, sh, act)
+    return x, y, (B, Cin, Cout, D, H, W)
+
+
+def _hw3_backward(x, weight, dy, geom, need_x, need_w):
+    B, Cin, Cout, D, H, W = geom
+    dy = dy.contiguous()
+    weight = weight if weight.is_contiguous() else weight.contiguous()
+    L = _lib.lib()
+    dx = dw = None
+    if need_x:          # y[d] takes x[d + kd - 1] through slice kd, so dx[e] = G_0[e+1] + G_1[e] + G_2[e-1]: the same sum, ends exchanged
+        dx = torch.empty_like(x)
+        _hw3_slice_conv(dy, weight, 1, dx, B, Cin, Cout, D, H, W, True)
+        if D > 1:
+            g0, g2 = torch.empty_like(dx), torch.empty_like(dx)
+            _hw3_slice_conv(dy, weight, 0, g0, B, Cin, Cout, D, H, W, True)
+            _hw3_slice_conv(dy, weight, 2, g2, B, Cin, Cout, D, H, W, True)
+            _depth_sum3(g2, dx, g0, dx)
+    if need_w:          # slice kd: the (1,3,3) weight gradient of planes x[kd-1 ...] against dy[...]: depth-offset views, D - 1 planes
+        parts = torch.empty((3, Cout, Cin, 9), device=x.device, dtype=torch.float32)
+        ws, nws = _wgrad_workspace(Cin, Cout, 9, x.device)
+        plane = H * W * 4
+        for kd in range(3):
+            nd = D if kd == 1 else D - 1
+            if nd == 0:
+                parts[kd].zero_()
+                continue
+            xo, go = (plane if kd == 2 else 0), (plane if kd == 0 else 0)
+            rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(x) + xo, _lib.ptr(dy) + go, _lib.ptr(parts[kd]), B, Cin, Cout, nd, H, W, 1, 1,
+                                           x.stride(0), x.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(ws), nws, _stream())
+            _lib.check(rc, "ts_conv3d_hw_bwd_weight")
+        dw = parts.view(3, Cout, Cin, 3, 3).permute(1, 2, 0, 3, 4).contiguous()
+    return dx, dw
+
+
+class _Conv3dK333(torch.autograd.Function):
+    """Raw Conv3d 3x3x3, stride 1, padding 1, no bias: three (1,3,3) launches and ts_depth_sum3_fwd each way (see _hw3_forward)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        x, y, ctx.geom = _hw3_forward(x, weight)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        return _hw3_backward(x, weight, dy, ctx.geom, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+def conv3d_k333(x, weight):
+    """F.conv3d(x, weight, None, stride 1, padding 1) for a 3x3x3 kernel (groups 1, dilation 1, <= 64 output channels) on the (1,3,3)
+    HIP kernels.  `layers.Conv3d` does not choose it by itself (conv3d_supported is unchanged): SPP3D does."""
+    return _Conv3dK333.apply(x, weight)
+
+
+_SPP_MAX_LEVELS = 4            # csrc/spp3d.hip kMaxLevels
+
+
+def _spp_strides(strides):
+    s = tuple(int(v) for v in strides)
+    if not 1 <= len(s) <= _SPP_MAX_LEVELS or min(s) < 1:
+        raise ValueError("spp3d: 1..%d strides >= 1 (got %s)" % (_SPP_MAX_LEVELS, (s,)))
+    return s
+
+
+def spp3d_level_sizes(size, strides):
+    """[(n_d, n_h, n_w)] of the pooled levels of a (D, H, W) volume: box min(dim, s), floor(dim / box) cells (utils/SPP3D.py:42-43)."""
+    return [tuple(n // min(n, s) for n in size) for s in strides]
+
+
+def _spp_dense(t):
+    """The kernels take batch / channel strides; D*H*W itself is dense."""
+    D, H, W = t.shape[2:]
+    return t if tuple(t.stride()[2:]) == (H * W, W, 1) and t.stride(1) >= D * H * W and (t.shape[0] == 1 or t.stride(0) >= t.stride(1) * (t.shape[1] - 1) + D * H * W) \
+        else t.contiguous()
+
+
+class _Spp3dPool(torch.autograd.Function):
+    """Every avg_pool3d of SPP3D.forward (utils/SPP3D.py:41-43) in one launch (ts_spp3d_pool_fwd); backward ts_spp3d_pool_bwd, a gather.
+    `alias`: x is handed back as a second result; what flows into THAT (the concatenation's share of x's gradient) is added by the
+    same backward launch instead of a pass of autograd's own."""
+
+    @staticmethod
+    def forward(ctx, x, strides, alias):
+        _require_gpu(x)
+        if x.dim() != 5:
+            raise ValueError("spp3d_pool: x [B, C, D, H, W] (got %s)" % (tuple(x.shape),))
+        x = _spp_dense(x)
+        B, C, D, H, W = x.shape
+        sizes = spp3d_level_sizes((D, H, W), strides)
+        counts = [B * C * n[0] * n[1] * n[2] for n in sizes]
+        pooled = torch.empty(sum(counts), device=x.device, dtype=torch.float32)
+        s4 = strides + (0,) * (_SPP_MAX_LEVELS - len(strides))
+        _lib.check(_lib.lib().ts_spp3d_pool_fwd(_lib.ptr(x), _lib.ptr(pooled), B, C, D, H, W, len(strides), s4[0], s4[1], s4[2], s4[3],
+                                                x.stride(0), x.stride(1), _stream()), "ts_spp3d_pool_fwd")
+        ctx.geom = (B, C, D, H, W, strides, s4, sizes, alias)
+        outs, at = [], 0
+        for n, cnt in zip(sizes, counts):
+            outs.append(pooled[at:at + cnt].view(B, C, *n))
+            at += cnt
+        if alias:
+            outs.append(x.view_as(x))
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        B, C, D, H, W, strides, s4, sizes, alias = ctx.geom
+        dev = next(g for g in grads if g is not None).device
+        add = grads[len(strides)] if alias else None
+        if add is not None:
+            add = _spp_dense(add)
+        gl = [g.contiguous() if g is not None else torch.zeros((B, C) + n, device=dev, dtype=torch.float32)
+              for g, n in zip(grads[:len(strides)], sizes)]
+        gl += [None] * (_SPP_MAX_LEVELS - len(gl))
+        gx = torch.empty((B, C, D, H, W), device=dev, dtype=torch.float32)
+        rc = _lib.lib().ts_spp3d_pool_bwd(_lib.ptr(gl[0]), _lib.ptr(gl[1]), _lib.ptr(gl[2]), _lib.ptr(gl[3]), _lib.ptr(add), _lib.ptr(gx),
+                                          B, C, D, H, W, len(strides), s4[0], s4[1], s4[2], s4[3],
+                                          add.stride(0) if add is not None else 0, add.stride(1) if add is not None else 0,
+                                          gx.stride(0), gx.stride(1), _stream())
+        _lib.check(rc, "ts_spp3d_pool_bwd")
+        return gx, None, None
+
+
+def spp3d_pool(x, strides, alias=False):
+    """[avg_pool3d(x, k_s, k_s) for s in strides], k_s = (min(D,s), min(H,s), min(W,s)) (utils/SPP3D.py:41-43): one launch, the levels
+    are views of one buffer.  alias=True appends x itself (see _Spp3dPool) -- hand THAT to spp3d_expand."""
+    return list(_Spp3dPool.apply(x, _spp_strides(strides), bool(alias)))
+
+
+class _Spp3dExpand(torch.autograd.Function):
+    """cat([x] + [interpolate(l, (D,H,W), trilinear, align_corners=True) for l in levels], 1) (utils/SPP3D.py:45-47) in one launch;
+    backward: the levels' gradients by ts_spp3d_expand_bwd (a gather per coarse cell), x's is a view of the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, x, strides, *levels):
+        _require_gpu(x, *levels)
+        x = _spp_dense(x)
+        B, C, D, H, W = x.shape
+        sizes = spp3d_level_sizes((D, H, W), strides)
+        Cl = levels[0].shape[1]
+        for l, n in zip(levels, sizes):
+            if tuple(l.shape) != (B, Cl) + n:
+                raise ValueError("spp3d_expand: level %s where %s is expected" % (tuple(l.shape), (B, Cl) + n))
+        lv = [l.contiguous() for l in levels] + [None] * (_SPP_MAX_LEVELS - len(levels))
+        cat = torch.empty((B, C + Cl * len(levels), D, H, W), device=x.device, dtype=torch.float32)
+        s4 = strides + (0,) * (_SPP_MAX_LEVELS - len(strides))
+        rc = _lib.lib().ts_spp3d_expand_fwd(_lib.ptr(x), _lib.ptr(lv[0]), _lib.ptr(lv[1]), _lib.ptr(lv[2]), _lib.ptr(lv[3]), _lib.ptr(cat),
+                                            B, C, Cl, D, H, W, len(levels), s4[0], s4[1], s4[2], s4[3], x.stride(0), x.stride(1), _stream())
+        _lib.check(rc, "ts_spp3d_expand_fwd")
+        ctx.geom = (B, C, Cl, D, H, W, s4, sizes)
+        return cat
+
+    @staticmethod
+    def backward(ctx, g):
+        B, C, Cl, D, H, W, s4, sizes = ctx.geom
+        g = _spp_dense(g)
+        gl = [None] * _SPP_MAX_LEVELS
+        if any(ctx.needs_input_grad[2:]):
+            for i, n in enumerate(sizes):
+                gl[i] = torch.empty((B, Cl) + n, device=g.device, dtype=torch.float32)
+            rc = _lib.lib().ts_spp3d_expand_bwd(_lib.ptr(g), _lib.ptr(gl[0]), _lib.ptr(gl[1]), _lib.ptr(gl[2]), _lib.ptr(gl[3]), B, C, Cl, D, H, W,
+                                                len(sizes), s4[0], s4[1], s4[2], s4[3], g.stride(0), g.stride(1), _stream())
+            _lib.check(rc, "ts_spp3d_expand_bwd")
+        return (g[:, :C] if ctx.needs_input_grad[0] else None, None) + tuple(gl[:len(sizes)])
+
+
+def _spp_infer_strides(size, levels):
+    """A stride per level that gives the level's size (the kernels describe a level by its stride; the resize only needs its size)."""
+    out = []
+    for l in levels:
+        n = tuple(l.shape[2:])
+        s = next((s for s in range(1, max(size) + 1) if spp3d_level_sizes(size, (s,))[0] == n), None)
+        if s is None:
+            raise ValueError("spp3d_expand: no stride pools %s to %s" % (tuple(size), n))
+        out.append(s)
+    return tuple(out)
+
+
+def spp3d_expand(levels, x, strides=None):
+    """cat([x, resize(levels[0]), ...], 1) with the trilinear align_corners resize of utils/SPP3D.py:45; `levels` as spp3d_pool(x,
+    strides) lays them out (any channel count, the same for all).  Without `strides` they are inferred from the levels' sizes."""
+    levels = list(levels)
+    strides = _spp_strides(strides) if strides is not None else _spp_infer_strides(tuple(x.shape[2:]), levels)
+    if len(levels) != len(strides):
+        raise ValueError("spp3d_expand: %d levels for %d strides" % (len(levels), len(strides)))
+    return _Spp3dExpand.apply(x, strides, *levels)
 
 
 # --------------------------------------------------------------------------------------- element-wise glue of the levels

@@ -1740,6 +1740,119 @@ def flow_cases(M):
     print("\n".join(lines))
 
 
+def spp3d_cases(M):
+    """tests/golden/spp3d_*.npz: the reference's own SPP3D (aggregation/utils/SPP3D.py:8-49) on the CPU, in fp32 and fp64, forward and the
+    backward of a seeded cotangent; dev_* = how far its fp32 run lies from its fp64 run, stage by stage."""
+    from architecture.modeling.aggregation.utils.SPP3D import SPP3D as RefSPP3D
+    import spp3d_ref
+    strides = (2, 4, 8, 16)
+    L = len(strides)
+    shapes = [("a", (2, 8, 5, 6, 7), True), ("b", (1, 8, 18, 17, 35), True), ("c", (2, 32, 3, 9, 20), True), ("d", (1, 8, 1, 2, 2), False)]
+    lines = ["spp3d_*.npz: tools/gen_golden.py --only-spp3d, numpy %s, torch %s CPU -- the reference's own SPP3D" % (np.__version__, torch.__version__),
+             "(architecture/modeling/aggregation/utils/SPP3D.py:8-49), strides (2, 4, 8, 16), norm 'BN3d', activation 'ReLU', built and called on",
+             "seeded inputs in float32 and in float64, with the backward of a seeded cotangent in both (train mode; the eval fixture has no backward).",
+             "Inputs, all kept as their seed (tests/spp3d_ref.py fixture_input / fixture_state / fixture_cotangent draw them again):",
+             "x = N(0,1) noise + per (batch, channel) an offset N(0,1) + along every axis of more than one plane a ramp a * 2 * (i / (n - 1) - 0.5),",
+             "a uniform in [-2, 2] per (batch, channel, axis) (so the means over large boxes differ at order one: a BatchNorm over the two values a",
+             "channel has at the coarsest level divides by their distance); parameters and buffers by synth.state_values, except that the",
+             "convolution weights are doubled and every BatchNorm bias is sign * m * (that BatchNorm's weight), sign +-1 with equal chance and m",
+             "uniform in [1.5, 2.5] per channel (a channel's ReLU is mostly open or mostly shut, so few of a stage's ~10^5 pre-activations lie near",
+             "zero: with the plain N(0, 0.1) bias no seed in 2000 met the margin rule below); the cotangent k / 8 with k an integer in [-8, 8].",
+             "Train fixtures: the seed is drawn again until, at every ReLU (the L levels and fuse.0), the fp32 and the fp64 run have the same mask",
+             "and the smallest |pre-activation| of the fp64 run is >= 32 x that stage's max |fp32 - fp64|; every BatchNorm sees >= 2 values per",
+             "channel.  All three are asserted.",
+             "Stored: seed, shape, strides, training, keys (the reference's state-dict keys in order), out, pooled_<i> (the avg_pool3d results),",
+             "cat_idx / cat_val (the concatenation's level channels cat[:, C:]: all of them up to 8192 elements, else 8192 seeded flat",
+             "positions), grad_x, grad_<parameter key>, stat_<buffer key> (running statistics and num_batches_tracked after the step),",
+             "dev_out / dev_cat / dev_pooled_<i> / dev_stat_<key> = max |fp32 run - fp64 run|, rel_grad_<key> = relative L2 of the fp32 run's",
+             "gradient against the fp64 run's, min_pre_<j> / dev_pre_<j> = the margin figures per ReLU."]
+    total = 0
+    for tag, shape, training in shapes:
+        B, C, D, H, W = shape
+        base = synth.SEED0 + 11000 + 1000 * ord(tag)
+
+        def run(seed, dt):
+            ref = RefSPP3D(in_planes=C, strides=strides, norm='BN3d', activation='ReLU')
+            state = spp3d_ref.fixture_state(seed, C, L, dt)
+            missing = ref.load_state_dict(state, strict=True)
+            assert not missing.missing_keys and not missing.unexpected_keys
+            ref = ref.to(dt).train(training)
+            grab = dict(pre=[], pooled=[], cat=[])
+            hooks = []
+            for p in ref.pools:
+                hooks.append(p.register_forward_pre_hook(lambda m, a: grab["pooled"].append(a[0].detach().clone())))
+                hooks.append(p.norm.register_forward_hook(lambda m, a, o: grab["pre"].append(o.detach().clone())))
+            hooks.append(ref.fuse[0].register_forward_pre_hook(lambda m, a: grab["cat"].append(a[0].detach().clone())))
+            hooks.append(ref.fuse[0].norm.register_forward_hook(lambda m, a, o: grab["pre"].append(o.detach().clone())))
+            x = spp3d_ref.fixture_input(seed, shape, dt).requires_grad_(training)
+            out = ref(x)
+            grads = {}
+            if training:
+                out.backward(spp3d_ref.fixture_cotangent(seed, out.shape, dt))
+                grads = {k: p.grad.detach() for k, p in ref.named_parameters()}
+                grads["x"] = x.grad.detach()
+            for h in hooks:
+                h.remove()
+            stats = {k: v.detach().clone() for k, v in ref.state_dict().items() if "running_" in k or "num_batches" in k}
+            return out.detach(), grab, grads, stats, list(ref.state_dict().keys())
+
+        for attempt in range(2000):
+            seed = base + attempt
+            o32, g32, d32, s32, keys = run(seed, torch.float32)
+            o64, g64, d64, s64, _ = run(seed, torch.float64)
+            margins = []
+            ok = True
+            for j, (p32, p64) in enumerate(zip(g32["pre"], g64["pre"])):
+                dev = float((p32.double() - p64).abs().max())
+                low = float(p64.abs().min())
+                same = bool(((p32 > 0) == (p64 > 0)).all())
+                margins.append((low, dev))
+                ok = ok and same and low >= 32 * dev
+                if training:
+                    assert p64.numel() // p64.shape[1] >= 2, (tag, j)
+            if ok or not training:
+                break
+        assert ok or not training, tag
+        if training:
+            for low, dev in margins:
+                assert low >= 32 * dev
+        # the restatement stands where the reference stands
+        own = spp3d_ref.spp3d(spp3d_ref.fixture_input(seed, shape, torch.float64), spp3d_ref.fixture_state(seed, C, L, torch.float64), strides, training)
+        assert float((own["out"] - o64).abs().max()) <= 1e-10 * max(1.0, float(o64.abs().max())), (tag, float((own["out"] - o64).abs().max()))
+        cat32, cat64 = g32["cat"][0][:, C:], g64["cat"][0][:, C:]
+        n = cat32.numel()
+        idx = np.arange(n) if n <= 8192 else np.sort(np.random.RandomState(seed % (2 ** 32)).choice(n, 8192, replace=False))
+        arrs = dict(seed=seed, shape=np.array(shape), strides=np.array(strides), training=training, keys=np.array(keys), out=o32,
+                    cat_idx=idx.astype(np.int32), cat_val=spp3d_ref.sample(cat32, idx), dev_out=float((o32.double() - o64).abs().max()),
+                    dev_cat=float((cat32.double() - cat64).abs().max()), attempts=attempt + 1)
+        for i in range(L):
+            arrs["pooled_%d" % i] = g32["pooled"][i]
+            arrs["dev_pooled_%d" % i] = float((g32["pooled"][i].double() - g64["pooled"][i]).abs().max())
+        for j, (low, dev) in enumerate(margins):
+            arrs["min_pre_%d" % j], arrs["dev_pre_%d" % j] = low, dev
+        rels = []
+        for k in d32:
+            arrs["grad_" + k] = d32[k]
+            arrs["rel_grad_" + k] = float((d32[k].double() - d64[k]).norm() / d64[k].norm())
+            rels.append(arrs["rel_grad_" + k])
+        for k in s32:
+            arrs["stat_" + k] = s32[k]
+            arrs["dev_stat_" + k] = float((s32[k].double() - s64[k].double()).abs().max())
+        size = save_fixed("spp3d_" + tag, **arrs)
+        assert size <= 1024 * 1024, (tag, size)
+        total += size
+        lines.append("spp3d_%s  B=%d C=%d D=%d H=%d W=%d %s  seed %d (draw %d); levels %s; dev_out %.3g dev_cat %.3g dev_pooled <= %.3g; "
+                     "min |pre| / dev per ReLU %s; rel_grad %s; %.0f KB"
+                     % (tag, B, C, D, H, W, "train" if training else "eval", seed, attempt + 1, spp3d_ref.level_sizes((D, H, W), strides),
+                        arrs["dev_out"], arrs["dev_cat"], max(arrs["dev_pooled_%d" % i] for i in range(L)),
+                        " ".join("%.2e/%.1e" % m for m in margins),
+                        ("%.3g .. %.3g" % (min(rels), max(rels))) if rels else "-", size / 1024))
+    lines.append("total %.0f KB (out and grad_x of shape b, the one with a remainder on every axis, are 343 KB each)" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_spp3d.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def save_fixed(name, **arrs):
     """`save` with the archive's time stamps pinned, so that a fixture regenerates byte for byte."""
     import zipfile
@@ -2117,6 +2230,9 @@ def main():
         return
     if "--only-flow" in sys.argv:
         flow_cases(M)
+        return
+    if "--only-spp3d" in sys.argv:
+        spp3d_cases(M)
         return
     if "--only-flow-frame" in sys.argv:
         flow_frame_cases(M)
