@@ -420,6 +420,21 @@ int ts_topk_softargmax_fwd(const float* cost, const float* sample, const float* 
                            float* topk_disp, float* topk_cost, int* topk_index,
                            int B, int D, int H, int W, int k, void* stream);
 
+/* ABI 19 -- ts_topk_softargmax_fwd followed by ts_convex_upsample_candidates_fwd on its disparity, as one launch (the tail of the
+ * coarse and fine levels of an inference pass): mask [B,9*factor^2,H,W]; out / low / high [B,1,factor*H,factor*W] and the
+ * candidate planes exactly as ts_convex_upsample_candidates_fwd writes them.  The disparity at level resolution and the top-k
+ * planes are not written.  Results are bit-identical to the two launches.  factor <= 8. */
+int ts_regress_convex_upsample_fwd(const float* cost, const float* sample, const float* offset, const float* mask,
+                                   float* out, float* low, float* high, float* candidates, int B, int D, int H, int W,
+                                   int k, int factor, float disp_scale, float range, int channel_offset,
+                                   int channels_total, void* stream);
+
+/* ABI 19 -- ts_topk_softargmax_fwd followed by ts_resize_bilinear_pair_fwd of its top-k planes to (H/2, W/2) with value scales 0.5
+ * and 1 (the tail of the 1/4 level, precise.py:100-103), as one launch: disp [B,1,H,W]; mem_sample / mem_cost [B,k,H/2,W/2].  The
+ * full-size top-k planes are not written.  Bit-identical to the two launches.  Odd H or W: TS_ERR_UNSUPPORTED. */
+int ts_topk_softargmax_half_fwd(const float* cost, const float* sample, const float* offset, float* disp,
+                                float* mem_sample, float* mem_cost, int B, int D, int H, int W, int k, void* stream);
+
 int ts_topk_softargmax_bwd(const float* topk_disp, const float* topk_cost, const int* topk_index,
                            const float* disp, const float* grad_disp, const float* grad_topk_disp,
                            const float* grad_topk_cost, float* grad_cost, float* grad_sample,
@@ -786,6 +801,12 @@ int ts_conv3d_hw_x6s_weight_split(const float* w_t, void* w6, int Cin, int Cout,
 int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float* scale, const float* shift, float* y,
                          int B, int Cin, int Cout, int D, int H, int W, int mode, int act, float act_param,
                          long long in_bstride, long long in_cstride, long long out_bstride, long long out_cstride, void* stream);
+/* ABI 19 -- ts_conv3d_hw_x6s_fwd (mode 2, D = 1, no activation, 9 <= Cout <= 16) followed by ts_unet_upsample_fwd on its first nine
+ * output planes, as one launch: x [B,Cin,H,W] with H = 2h, W = 2w even; disp [B,1,h,w]; out [B,1,4h,4w].  The logit planes stay in
+ * the workgroup's LDS.  Bit-identical to the two launches.  Anything else: TS_ERR_UNSUPPORTED. */
+int ts_deconv2d_k4s2_unet_upsample_fwd(const float* x, const void* w6, const float* scale, const float* shift,
+                                       const float* disp, float* out, int B, int Cin, int Cout, int H, int W,
+                                       long long in_bstride, long long in_cstride, void* stream);
 int ts_conv3d_d_fwd(const float* x, const float* w_t, const float* scale, const float* shift, float* y,
                     int B, int Cin, int Cout, int Din, int H, int W, int k, int stride, int dilation,
                     int padding, int transposed, int act, float act_param,

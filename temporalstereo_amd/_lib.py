@@ -62,6 +62,8 @@ SIGNATURES = {
     "ts_clip_rmsprop_workspace_bytes": (c_size, [c_int]),
     "ts_clip_rmsprop_step": (c_int, [c_ptr, c_int] + [c_float] * 4 + [c_ptr, c_size, c_ptr]),
     "ts_topk_softargmax_fwd": (c_int, [c_f32p] * 7 + [c_int] * 5 + [c_ptr]),
+    "ts_regress_convex_upsample_fwd": (c_int, [c_f32p] * 8 + [c_int] * 6 + [c_float, c_float, c_int, c_int, c_ptr]),
+    "ts_topk_softargmax_half_fwd": (c_int, [c_f32p] * 6 + [c_int] * 5 + [c_ptr]),
     "ts_topk_softargmax_bwd": (c_int, [c_f32p] * 9 + [c_int] * 5 + [c_ptr]),
     "ts_softargmin_fwd": (c_int, [c_f32p] * 3 + [c_float, c_int] + [c_int] * 4 + [c_ptr]),
     "ts_softargmin_bwd": (c_int, [c_f32p] * 6 + [c_float, c_int] + [c_int] * 4 + [c_ptr]),
@@ -138,6 +140,7 @@ SIGNATURES = {
     "ts_conv3d_hw_x6s_weight_bytes": (c_size, [c_int] * 3),
     "ts_conv3d_hw_x6s_weight_split": (c_int, [c_f32p, c_ptr, c_int, c_int, c_int, c_int, c_ptr]),
     "ts_conv3d_hw_x6s_fwd": (c_int, [c_f32p, c_ptr, c_f32p, c_f32p, c_f32p] + [c_int] * 8 + [c_float] + [ctypes.c_longlong] * 4 + [c_ptr]),
+    "ts_deconv2d_k4s2_unet_upsample_fwd": (c_int, [c_f32p, c_ptr, c_f32p, c_f32p, c_f32p, c_f32p] + [c_int] * 5 + [ctypes.c_longlong] * 2 + [c_ptr]),
     "ts_conv3d_hw_x6_fwd": (c_int, [c_f32p, c_ptr, c_f32p, c_f32p, c_f32p] + [c_int] * 8 + [c_float] + [ctypes.c_longlong] * 4 +
                             [c_f32p, ctypes.c_longlong, c_ptr, c_size, c_ptr]),
     "ts_conv3d_hw_fwd": (c_int, [c_f32p] * 5 + [c_int] * 10 + [c_float] + [ctypes.c_longlong] * 4 +

@@ -13,6 +13,7 @@ aggregation/levels.py with NO framework op on the data path:
   heads            conv kernels with the tanh-offset epilogue                               (K3e)
   regression       ts_topk_softargmax_fwd         (K4a)
   upsamplers       ts_convex_upsample_fwd / ts_unet_upsample_fwd / ts_deconv2d_k4s2_fwd      (K5)
+  level tails      ts_regress_convex_upsample_fwd (K4a + K5 in one launch), ts_deconv2d_k4s2_unet_upsample_fwd (pipelined pass)
 
 Semantics are those of the reference modules in eval mode (citations in levels.py / blocks.py).
 """
@@ -550,6 +551,18 @@ FUSED_K1 = os.environ.get("TS_FUSED_K1", "1") != "0"
 # hands its consumers one [feature | spx4] tensor, instead of reading the two allocations in place (Split; A/B measurements, and
 # what NativePrecise falls back to when a *_split_supported query refuses the shape)
 SPLIT_INPUT = os.environ.get("TS_SPLIT_INPUT", "1") != "0"
+# TS_FUSED_TAILS=0: every level ends in the launches of rounds 1-6 -- regression, then upsampling, each handing the other a tensor that
+# nothing else reads -- instead of one launch for the pair (`convex`: ts_regress_convex_upsample_fwd at the coarse and fine levels;
+# `deconv`: in a pipelined pass ts_deconv2d_k4s2_unet_upsample_fwd at the 1/4 level).  Bit-identical either way (A/B measurements);
+# TS_FUSED_TAILS=convex | deconv switches one of the two on alone.  (ts_topk_softargmax_half_fwd, the 1/4 level's regression with the
+# memory resize, is not wired in: it measured within noise of the two launches in both schedules -- DESIGN section 9.)
+def _fused_tails(value):
+    if value == "0":
+        return frozenset()
+    return frozenset(("convex", "deconv")) if value in ("", "1") else frozenset(value.split(","))
+
+
+FUSED_TAILS = _fused_tails(os.environ.get("TS_FUSED_TAILS", "1"))
 
 
 def block_cost_corr(left, right, disp, scales):
@@ -782,6 +795,23 @@ class ConvexUp:
         _lib.check(rc, "ts_convex_upsample_candidates_fwd")
         return out, low, high, cand
 
+    def regress_with_candidates(self, feat, cost, samp, off, k, m, rng, extra_front=0):
+        """with_candidates on the top-k regression of (cost, samp, off), as one launch: the disparity at level resolution is not
+        made."""
+        B, _, H, W = cost.shape
+        if m is None:
+            m = self.mask(feat)
+        Ho, Wo = H * self.r, W * self.r
+        out = torch.empty((B, 1, Ho, Wo), device=cost.device, dtype=torch.float32)
+        low, high = torch.empty_like(out), torch.empty_like(out)
+        cand = torch.empty((B, extra_front + 5, Ho, Wo), device=cost.device, dtype=torch.float32)
+        cost, samp, off = _lib.contiguous(cost), _lib.contiguous(samp), _lib.contiguous(off)
+        rc = _lib.lib().ts_regress_convex_upsample_fwd(_lib.ptr(cost), _lib.ptr(samp), _lib.ptr(off), _lib.ptr(m), _lib.ptr(out),
+                                                       _lib.ptr(low), _lib.ptr(high), _lib.ptr(cand), B, cost.shape[1], H, W, int(k),
+                                                       self.r, float(self.r), float(rng), extra_front, extra_front + 5, _stream())
+        _lib.check(rc, "ts_regress_convex_upsample_fwd")
+        return out, low, high, cand
+
     def __call__(self, feat, disp, m=None):
         B, _, H, W = disp.shape
         if m is None:
@@ -886,6 +916,10 @@ class _MergingLevel(_LevelBase):
     def merge_fuse_predict(self, vol, samples, prev_info, feat, resize_memory, mask=None, next_range=None):
         cat4, samp = self.merge(vol, samples, prev_info, resize_memory)
         cost, off = self.heads(self.fuse(cat4))
+        if "convex" in FUSED_TAILS and next_range is not None and self.up.r <= 8:
+            if callable(mask):
+                mask = mask()
+            return self.up.regress_with_candidates(feat, cost, samp, off, self.topk, mask, *next_range), cost, off, samp
         disp, _, _ = TF.topk_softargmax(cost, samp, off, k=self.topk)
         if callable(mask):
             mask = mask()                    # produced on another stream: the callable joins it
@@ -942,6 +976,13 @@ class SplitBoth:
     def __getitem__(self, idx):
         """Rows of the [2B, 2Cf, H, W] tensor this stands for (a framework copy: diagnostics, never part of a pass)."""
         return torch.cat([s.cat() for s in self.pair()], 0)[idx]
+
+
+class DecoderHead:
+    """What a pipelined pass hands NativePrecise in place of the upsampling logits: the input of the last deconvolution."""
+
+    def __init__(self, g):
+        self.g = g
 
 
 class NativePrecise(_LevelBase):
@@ -1040,13 +1081,29 @@ class NativePrecise(_LevelBase):
 
     def unet_decode(self, st):
         """Second part: the decoder down to the 9-tap upsampling mask (module.py:484-491), needed by the last launch of a pass only."""
+        return self.unet_logits(self.unet_decode_head(st))
+
+    def unet_decode_head(self, st):
+        """The decoder down to the `concat` convolution: the input of the last deconvolution, [B, C, 2H, 2W]."""
         lcat, cat2, B, H, W = st
         f = self._c2d(self._c2d(lcat.unsqueeze(2), self.fuse[0], 1), self.fuse[1], 1).squeeze(2)
         self._deconv(_lib.contiguous(f), self.deconv4, cat2, cat2.stride(0))
-        g = _lib.contiguous(self._c2d(cat2.unsqueeze(2), self.concat, 1).squeeze(2))
-        mask = torch.empty((B, 9, 4 * H, 4 * W), device=lcat.device, dtype=torch.float32)
+        return _lib.contiguous(self._c2d(cat2.unsqueeze(2), self.concat, 1).squeeze(2))
+
+    def unet_logits(self, g):
+        """The last deconvolution: the nine upsampling logits at full resolution."""
+        B, _, H2, W2 = g.shape
+        mask = torch.empty((B, 9, 2 * H2, 2 * W2), device=g.device, dtype=torch.float32)
         self._deconv(g, self.deconv2, mask, mask.stride(0))
         return mask
+
+    def fused_upsample_ok(self, g):
+        """Whether ts_deconv2d_k4s2_unet_upsample_fwd takes the last deconvolution on `g`: where _deconv would pick the x6s kernel."""
+        B, Cin, H2, W2 = g.shape
+        f = self.deconv2
+        return bool("deconv" in FUSED_TAILS and X6 and X6S and f.act == ACT_NONE and 9 <= f.cout <= 16 and H2 % 2 == 0 and W2 % 2 == 0 and
+                    _lib.lib().ts_conv3d_hw_x6s_supported(Cin, f.cout, H2, W2, X6S_T4) and
+                    x6s_grid(B, f.cout, 1, H2, W2, X6S_T4) >= _X6S_MIN_GRID)
 
     def early(self, both, lterm, ds):
         """Cost volume + first layer + init3d of the 1/4 level (precise.py:88-93)."""
@@ -1067,8 +1124,16 @@ class NativePrecise(_LevelBase):
         cost, off = self.heads(vol)
         disp, mem_s, mem_c = TF.topk_softargmax(cost, ds, off, k=self.topk)
         full = torch.empty((B, 1, 4 * H, 4 * W), device=both.device, dtype=torch.float32)
-        rc = _lib.lib().ts_unet_upsample_fwd(_lib.ptr(mask), _lib.ptr(disp), _lib.ptr(full), B, H, W, 4 * H, 4 * W, _stream())
-        _lib.check(rc, "ts_unet_upsample_fwd")
+        if isinstance(mask, DecoderHead):          # a pipelined pass: the last deconvolution and the upsampling as one launch
+            g, f = mask.g, self.deconv2
+            Cin = g.shape[1]
+            rc = _lib.lib().ts_deconv2d_k4s2_unet_upsample_fwd(_lib.ptr(g), _lib.ptr(x6s_weights(f, X6S_T4)), _lib.ptr(f.scale),
+                                                               _lib.ptr(f.shift), _lib.ptr(disp), _lib.ptr(full), B, Cin, f.cout,
+                                                               2 * H, 2 * W, Cin * 4 * H * W, 4 * H * W, _stream())
+            _lib.check(rc, "ts_deconv2d_k4s2_unet_upsample_fwd")
+        else:
+            rc = _lib.lib().ts_unet_upsample_fwd(_lib.ptr(mask), _lib.ptr(disp), _lib.ptr(full), B, H, W, 4 * H, 4 * W, _stream())
+            _lib.check(rc, "ts_unet_upsample_fwd")
         prev_info['prev_disp'] = full
         mem_s, mem_c = resize_bilinear_pair(mem_s, mem_c, (H // 2, W // 2), 0.5, 1.0)                  # precise.py:100-103
         prev_info['cost_memory'] = {'disp_sample': mem_s, 'cost_volume': mem_c}
@@ -1208,7 +1273,8 @@ class NativeAggregator:
                 both, lterm, ust = self.precise.unet_encode(l4, r4, left_image, right_image)
             edge(S["unet"], S["unet2"])
             with on(S["unet2"]):
-                mask = self.precise.unet_decode(ust)
+                mask = self.precise.unet_decode_head(ust)
+                mask = DecoderHead(mask) if self.precise.fused_upsample_ok(mask) else self.precise.unet_logits(mask)
             edge(S["coarse"], S["coarse2"])
             with on(S["coarse2"]):
                 ds = self._coarse_level(l16, r16, prev_info, out, lambda: mc, vol=cvol)

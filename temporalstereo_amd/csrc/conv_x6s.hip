@@ -19,6 +19,7 @@
 //          along x: stored directly they would be 4-byte stores at an 8-byte pitch).
 // Needs W % 4 == 0 and Wo % 4 == 0 (aligned quads on both sides).
 #include "conv_common.hpp"
+#include "regress_tails.hpp"
 
 namespace {
 
@@ -78,10 +79,22 @@ weight_split6_g8_kernel(const float* __restrict__ w_t, u32x4* __restrict__ w6, i
   }
 }
 
-template <int MODE, int CB, int TR = 8>
+// What leaves a workgroup.  StoreRows: the channel rows, to y.  UnetUp (XS_T4, Cout <= 16): the channels are the nine logits of
+// UNet.upsample (module.py:468-482) and are consumed where they are staged -- each thread reads the logits of its output pixels
+// from LDS, takes the 4x4 disparity patch and stores ONE plane, out [B,1,Ho,Wo]; the logit planes (9 x 544 x 960 floats per
+// pass: 18.8 MB written by this kernel and read back by unet_upsample_kernel) never exist.
+struct StoreRows {};
+struct UnetUp {
+  const float* disp;      // [B,1,h,w], Ho = 4 h, Wo = 4 w
+  float* out;
+  int h, w;
+  float sh, sw;           // align_corners scales h -> Ho, w -> Wo (as ts_unet_upsample_fwd computes them)
+};
+
+template <int MODE, int CB, int TR = 8, class EP = StoreRows>
 __global__ void __launch_bounds__(256, TR == 4 ? 3 : 2)
 ig_conv_x6s_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, const float* __restrict__ scale,
-                   const float* __restrict__ shift, float* __restrict__ y, const IG p) {
+                   const float* __restrict__ shift, float* __restrict__ y, const IG p, const EP ep) {
   extern __shared__ __attribute__((aligned(16))) u32x4 lds6[];
   using G = XG<MODE, TR>;
   constexpr bool T = G::T;
@@ -291,9 +304,28 @@ ig_conv_x6s_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
       __builtin_amdgcn_raw_buffer_store_b128(val, yr, off, 0, 0);
     }
   } else {
+    // UnetUp: the scaled, zero-padded disparity under the tile, once per workgroup, behind the channel staging -- the tile's 2 TR x 64
+    // output pixels read 4x4 patches of at most (TR/2 + 4) x 20 source pixels (both scales are below 1/4); every thread would
+    // otherwise make its own 16 clamped reads and 16 divisions
+    constexpr int PR = TR / 2 + 5, PC = 21;
+    float* patch = epi + 16 * G::EPI;
+    int pyb = 0, pxb = 0;
+    if constexpr (std::is_same_v<EP, UnetUp>) {
+      int i1;
+      float l1;
+      ts_tail::lin_src(ep.sh, 2 * ty0, ep.h, pyb, i1, l1);       // the tile's first output row / column
+      ts_tail::lin_src(ep.sw, 2 * tx0, ep.w, pxb, i1, l1);
+    }
 #pragma unroll
     for (int pa = 0; pa < 2; ++pa) {
       __syncthreads();                                  // fragments / the previous half's rows are consumed
+      if constexpr (std::is_same_v<EP, UnetUp>) {
+        if (pa == 0) {
+          const float* dp = ep.disp + static_cast<size_t>(b) * ep.h * ep.w;
+          for (int i = threadIdx.x; i < PR * PC; i += 256)
+            patch[i] = ts_tail::unet_patch_value(dp, pyb - 1 + i / PC, pxb - 1 + i % PC, ep.h, ep.w, p.Wo);
+        }
+      }
 #pragma unroll
       for (int pbit = 0; pbit < 2; ++pbit)
 #pragma unroll
@@ -305,17 +337,43 @@ ig_conv_x6s_kernel(const float* __restrict__ x, const u32x4* __restrict__ w6, co
                 apply_act(acc[pa * 2 + pbit][0][pb][r] * esc[0][r] + esh[0][r], p.act, p.act_param, co);
           }
       __syncthreads();
+      if constexpr (std::is_same_v<EP, UnetUp>) {
+        // one output pixel per thread and pass: row `row` of the tile, output column 2 tx0 + c; a wave stores 256 contiguous bytes
 #pragma unroll
-      for (int it = 0; it < TR; ++it) {
-        const int idx = static_cast<int>(threadIdx.x) + 256 * it;
-        const int col = idx / (TR * 16), rem = idx % (TR * 16);
-        const int row = rem >> 4, q = rem & 15;
-        const int iy = ty0 + row, oy = 2 * iy + pa, ox = 2 * tx0 + 4 * q;
-        const u32x4 val = *reinterpret_cast<const u32x4*>(epi + col * G::EPI + row * 64 + q * 4);
-        const int co = co0 + col;
-        const unsigned off = (iy < p.H && oy < p.Ho && ox < p.Wo && co < p.Cout)
-            ? (obase + static_cast<unsigned>(oy) * p.Wo + ox) * 4u + static_cast<unsigned>(co) * ocs : kOOB;
-        __builtin_amdgcn_raw_buffer_store_b128(val, yr, off, 0, 0);
+        for (int it = 0; it < TR / 4; ++it) {
+          const int idx = static_cast<int>(threadIdx.x) + 256 * it;
+          const int row = idx >> 6, c = idx & 63;
+          const int iy = ty0 + row, oy = 2 * iy + pa, ox = 2 * tx0 + c;
+          if (iy >= p.H || ox >= p.Wo) continue;
+          float m[9];
+#pragma unroll
+          for (int k = 0; k < 9; ++k) m[k] = epi[k * G::EPI + row * 64 + c];
+          int y0, y1, x0, x1;
+          float ly, lx;
+          ts_tail::lin_src(ep.sh, oy, ep.h, y0, y1, ly);
+          ts_tail::lin_src(ep.sw, ox, ep.w, x0, x1, lx);
+          // (the clamp only keeps a read inside the staged patch: floor(s oy) - floor(s oy') <= TR/2 over a tile's rows, 16 over its columns)
+          const float* pp = patch + min(y0 - pyb, PR - 4) * PC + min(x0 - pxb, PC - 4);
+          float pd[4][4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) pd[r][cc] = pp[r * PC + cc];
+          ep.out[static_cast<size_t>(b) * hw_o + static_cast<size_t>(oy) * p.Wo + ox] = ts_tail::unet_combine(m, pd, lx, ly, x1 > x0, y1 > y0);
+        }
+      } else {
+#pragma unroll
+        for (int it = 0; it < TR; ++it) {
+          const int idx = static_cast<int>(threadIdx.x) + 256 * it;
+          const int col = idx / (TR * 16), rem = idx % (TR * 16);
+          const int row = rem >> 4, q = rem & 15;
+          const int iy = ty0 + row, oy = 2 * iy + pa, ox = 2 * tx0 + 4 * q;
+          const u32x4 val = *reinterpret_cast<const u32x4*>(epi + col * G::EPI + row * 64 + q * 4);
+          const int co = co0 + col;
+          const unsigned off = (iy < p.H && oy < p.Ho && ox < p.Wo && co < p.Cout)
+              ? (obase + static_cast<unsigned>(oy) * p.Wo + ox) * 4u + static_cast<unsigned>(co) * ocs : kOOB;
+          __builtin_amdgcn_raw_buffer_store_b128(val, yr, off, 0, 0);
+        }
       }
     }
   }
@@ -328,7 +386,7 @@ int launch_x6s(const float* x, const void* w6, const float* scale, const float* 
   constexpr size_t epi_b = G::T ? static_cast<size_t>(16) * G::EPI * 4 : static_cast<size_t>(CB) * 16 * kEpiS2 * 4;
   constexpr size_t lds = main_b > epi_b ? main_b : epi_b;
   static_assert(lds <= 64 * 1024, "ig_conv_x6s_kernel: LDS tile");
-  hipLaunchKernelGGL((ig_conv_x6s_kernel<MODE, CB, TR>), grid, dim3(256), lds, st, x, static_cast<const u32x4*>(w6), scale, shift, y, p);
+  hipLaunchKernelGGL((ig_conv_x6s_kernel<MODE, CB, TR>), grid, dim3(256), lds, st, x, static_cast<const u32x4*>(w6), scale, shift, y, p, StoreRows{});
   return ts::launched("ig_conv_x6s_kernel");
 }
 
@@ -361,19 +419,15 @@ extern "C" int ts_conv3d_hw_x6s_weight_split(const float* w_t, void* w6, int Cin
   return ts::launched("weight_split6_g8_kernel");
 }
 
-// x [B,Cin,D,H,W] -> y [B,Cout,D,Ho,Wo]: mode 0 -> Ho = (H-1)/2+1 (stride-2 convolution), modes 1, 2 -> Ho = 2H (transposed forms; mode 2 is the
-// 2-D 4x4 deconvolution, D = 1).  w6 from ts_conv3d_hw_x6s_weight_split; scale / shift [>= Cout] or null.  Strides in elements.
-extern "C" int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float* scale, const float* shift, float* y,
-                                    int B, int Cin, int Cout, int D, int H, int W, int mode, int act, float act_param,
-                                    long long in_bstride, long long in_cstride, long long out_bstride, long long out_cstride,
-                                    void* stream) {
-  TS_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "conv3d_hw_x6s: non-positive size");
+namespace {
+// argument checks and the kernel's parameter block, shared by the entries below
+int x6s_params(IG& p, const char* who, int B, int Cin, int Cout, int D, int H, int W, int mode, int act, float act_param,
+               long long in_bstride, long long in_cstride, long long out_bstride, long long out_cstride) {
+  TS_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
   TS_REQUIRE(ts_conv3d_hw_x6s_supported(Cin, Cout, H, W, mode), TS_ERR_UNSUPPORTED,
-             "conv3d_hw_x6s: needs Cin >= 16, Cout <= 512, W %% 4 == 0 and Wo %% 4 == 0 (Cin=%d Cout=%d W=%d mode=%d)", Cin, Cout, W, mode);
-  TS_REQUIRE(act >= 0 && act <= 4, TS_ERR_SHAPE, "conv3d_hw_x6s: unknown activation");
-  TS_REQUIRE(D <= 65535, TS_ERR_UNSUPPORTED, "conv3d_hw_x6s: grid too large");
-  TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w6); TS_REQUIRE_PTR(y);
-  IG p;
+             "%s: needs Cin >= 16, Cout <= 512, W %% 4 == 0 and Wo %% 4 == 0 (Cin=%d Cout=%d W=%d mode=%d)", who, Cin, Cout, W, mode);
+  TS_REQUIRE(act >= 0 && act <= 4, TS_ERR_SHAPE, "%s: unknown activation", who);
+  TS_REQUIRE(D <= 65535, TS_ERR_UNSUPPORTED, "%s: grid too large", who);
   p.Cin = Cin; p.Cout = Cout; p.coutp = coutp6(Cout); p.D = D; p.H = H; p.W = W; p.Do = D;
   if (mode == XS_S2) { p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1; }
   else { p.Ho = 2 * H; p.Wo = 2 * W; }
@@ -389,11 +443,24 @@ extern "C" int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float*
     const unsigned long long out_b = (static_cast<unsigned long long>(Cout - 1) * out_cstride + static_cast<unsigned long long>(D) * p.Ho * p.Wo) * 4ull;
     const unsigned long long w_b = ts_conv3d_hw_x6s_weight_bytes(Cin, Cout, mode);
     TS_REQUIRE(in_b < 0x7fffffffull && out_b < 0x7fffffffull && w_b < 0x7fffffffull && in_cstride >= 0 && out_cstride >= 0,
-               TS_ERR_UNSUPPORTED, "conv3d_hw_x6s: a batch element spans 2 GiB or more");
+               TS_ERR_UNSUPPORTED, "%s: a batch element spans 2 GiB or more", who);
     p.in_bytes = static_cast<unsigned>(in_b); p.out_bytes = static_cast<unsigned>(out_b); p.w_bytes = static_cast<unsigned>(w_b);
   }
+  TS_REQUIRE(static_cast<long long>(B) * ((p.coutp + 15) / 16) <= 65535, TS_ERR_UNSUPPORTED, "%s: batch x channel groups beyond the grid's z extent", who);
+  return TS_OK;
+}
+}  // namespace
+
+// x [B,Cin,D,H,W] -> y [B,Cout,D,Ho,Wo]: mode 0 -> Ho = (H-1)/2+1 (stride-2 convolution), modes 1, 2 -> Ho = 2H (transposed forms; mode 2 is the
+// 2-D 4x4 deconvolution, D = 1).  w6 from ts_conv3d_hw_x6s_weight_split; scale / shift [>= Cout] or null.  Strides in elements.
+extern "C" int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float* scale, const float* shift, float* y,
+                                    int B, int Cin, int Cout, int D, int H, int W, int mode, int act, float act_param,
+                                    long long in_bstride, long long in_cstride, long long out_bstride, long long out_cstride,
+                                    void* stream) {
+  IG p;
+  if (int rc = x6s_params(p, "conv3d_hw_x6s", B, Cin, Cout, D, H, W, mode, act, act_param, in_bstride, in_cstride, out_bstride, out_cstride)) return rc;
+  TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w6); TS_REQUIRE_PTR(y);
   hipStream_t st = ts::as_stream(stream);
-  TS_REQUIRE(static_cast<long long>(B) * ((p.coutp + 15) / 16) <= 65535, TS_ERR_UNSUPPORTED, "conv3d_hw_x6s: batch x channel groups beyond the grid's z extent");
   if (mode == XS_S2) {
     p.tiles_x = (p.Wo + 31) / 32;
     const int tiles = ((p.Ho + 3) / 4) * p.tiles_x;
@@ -419,4 +486,31 @@ extern "C" int ts_conv3d_hw_x6s_fwd(const float* x, const void* w6, const float*
   const int tiles = ((H + 7) / 8) * p.tiles_x;
   const dim3 grid(tiles, D, B * p.co_groups);
   return mode == XS_T4 ? launch_x6s<XS_T4, 1>(x, w6, scale, shift, y, p, grid, st) : launch_x6s<XS_T3, 1>(x, w6, scale, shift, y, p, grid, st);
+}
+
+// ts_conv3d_hw_x6s_fwd (mode 2: the 4x4 stride-2 deconvolution, no activation) followed by ts_unet_upsample_fwd on its nine output
+// planes, as one launch: x [B,Cin,H,W] (H = 2h, W = 2w) -> out [B,1,4h,4w]; disp [B,1,h,w].  The logit planes are never written.
+extern "C" int ts_deconv2d_k4s2_unet_upsample_fwd(const float* x, const void* w6, const float* scale, const float* shift,
+                                                  const float* disp, float* out, int B, int Cin, int Cout, int H, int W,
+                                                  long long in_bstride, long long in_cstride, void* stream) {
+  IG p;
+  if (int rc = x6s_params(p, "deconv2d_k4s2_unet_upsample", B, Cin, Cout, 1, H, W, XS_T4, 0, 0.f, in_bstride, in_cstride, 0, 0)) return rc;
+  TS_REQUIRE(Cout >= 9 && Cout <= 16, TS_ERR_UNSUPPORTED, "deconv2d_k4s2_unet_upsample: %d output channels (nine logits, one channel group)", Cout);
+  TS_REQUIRE(H % 2 == 0 && W % 2 == 0, TS_ERR_UNSUPPORTED, "deconv2d_k4s2_unet_upsample: the disparity is half the input's size (H=%d W=%d)", H, W);
+  TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w6); TS_REQUIRE_PTR(disp); TS_REQUIRE_PTR(out);
+  UnetUp ep;
+  ep.disp = disp; ep.out = out; ep.h = H / 2; ep.w = W / 2;
+  ep.sh = p.Ho > 1 ? static_cast<float>(ep.h - 1) / static_cast<float>(p.Ho - 1) : 0.f;     // ts_unet_upsample_fwd's ac_scale
+  ep.sw = p.Wo > 1 ? static_cast<float>(ep.w - 1) / static_cast<float>(p.Wo - 1) : 0.f;
+  p.tiles_x = (W + 31) / 32;
+  p.co_groups = 1;
+  // the 4-row tile: 150-160 VGPRs, three workgroups per CU; the 8-row form holds all four classes' accumulators at 226-236
+  using G = XG<XS_T4, 4>;
+  constexpr size_t main_b = (static_cast<size_t>(3) * G::NPIXP + 3 * G::NSLOT * 16 + 1) * 16;
+  constexpr size_t epi_b = (static_cast<size_t>(16) * G::EPI + (4 / 2 + 5) * 21) * 4;          // channel staging + disparity patch
+  constexpr size_t lds = main_b > epi_b ? main_b : epi_b;
+  const dim3 grid(((H + 3) / 4) * p.tiles_x, 1, B);
+  hipLaunchKernelGGL((ig_conv_x6s_kernel<XS_T4, 1, 4, UnetUp>), grid, dim3(256), lds, ts::as_stream(stream), x,
+                     static_cast<const u32x4*>(w6), scale, shift, static_cast<float*>(nullptr), p, ep);
+  return ts::launched("ig_conv_x6s_kernel<UnetUp>");
 }

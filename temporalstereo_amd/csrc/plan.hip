@@ -112,6 +112,8 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_spp3d_pool_fwd),          TS_PLAN_OP(ts_spp3d_pool_bwd),
     TS_PLAN_OP(ts_spp3d_expand_fwd),        TS_PLAN_OP(ts_spp3d_expand_bwd),        TS_PLAN_OP(ts_depth_sum3_fwd),
     TS_PLAN_OP(ts_bn_small_train_bwd),
+    TS_PLAN_OP(ts_regress_convex_upsample_fwd), TS_PLAN_OP(ts_topk_softargmax_half_fwd),
+    TS_PLAN_OP(ts_deconv2d_k4s2_unet_upsample_fwd),
 };
 
 struct Call {

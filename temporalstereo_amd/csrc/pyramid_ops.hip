@@ -12,6 +12,7 @@
 // All are bandwidth/latency-bound element kernels: W is the contiguous axis, consecutive lanes own
 // consecutive pixels, every tensor is read once and written once (the 5^3 pooling goes through an
 // LDS plane tile and a 5-deep register ring along D instead of 125 global taps per output).
+#include "regress_tails.hpp"
 #include "ts_common.hpp"
 
 namespace {
@@ -38,13 +39,7 @@ unsigned grid_for(long long n, int threads) {
 // one 256-thread workgroup per 256 elements, uncapped (kernels without a grid-stride loop)
 unsigned exact_grid(long long n) { return static_cast<unsigned>((n + 255) / 256); }
 
-// source index / weight of torch's align_corners=True linear interpolation
-__device__ __forceinline__ void lin_src(float scale, int dst, int in_size, int& i0, int& i1, float& l1) {
-  const float s = scale * static_cast<float>(dst);
-  i0 = static_cast<int>(s);
-  i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-  l1 = s - static_cast<float>(i0);
-}
+using ts_tail::lin_src;        // source index / weight of torch's align_corners=True linear interpolation
 
 inline float ac_scale(int in_size, int out_size) {
   return out_size > 1 ? static_cast<float>(in_size - 1) / static_cast<float>(out_size - 1) : 0.f;
@@ -255,32 +250,18 @@ convex_upsample_kernel(const float* __restrict__ mask, const float* __restrict__
     const int y = oy / r, ry = oy - y * r, x = ox / r, rx = ox - x * r;
     const float* mp = mask + (static_cast<size_t>(b) * 9 * r * r + ry * r + rx) * HW + static_cast<size_t>(y) * W + x;
     const float* dp = disp + static_cast<size_t>(b) * HW;
-    float m[9], mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { m[k] = mp[static_cast<size_t>(k) * r * r * HW]; mx = fmaxf(mx, m[k]); }
-    float den = 0.f, acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float e = expf(m[k] - mx);
-      den += e;
+    float m[9];
+    const float mx = ts_tail::convex_logits(mp, static_cast<size_t>(r) * r * HW, m);
+    const float dup = ts_tail::convex_combine(m, mx, [&](int k) {
       const int yy = y + k / 3 - 1, xx = x + k % 3 - 1;
       const float dv = dp[min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)];        // unconditional; zero padding by select
-      const float v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? dv * disp_scale : 0.f;
-      acc += e * v;
-    }
-    const float dup = acc / den;
+      return ts_tail::convex_tap_value(dv, yy >= 0 && yy < H && xx >= 0 && xx < W, disp_scale);
+    });
     out[i] = dup;
     if (low) {      // the next level's search range and candidates in the same pass (see range_candidates_kernel)
-      const float lo = dup - range, hi = dup + range;
-      low[i] = lo; high[i] = hi;
-      const float span = fabsf(hi - lo), base = fminf(lo, hi);
       const size_t HWo = static_cast<size_t>(Ho) * Wo;
-      float* c = cand + (static_cast<size_t>(b) * ctot + coff) * HWo + static_cast<size_t>(oy) * Wo + ox;
-      c[0] = span * 0.f + base;
-      c[HWo] = span * 0.375f + base;
-      c[2 * HWo] = span * 0.5f + base;
-      c[3 * HWo] = span * 0.625f + base;
-      c[4 * HWo] = span * 1.f + base;
+      ts_tail::convex_store_range(dup, range, low + i, high + i,
+                                  cand + (static_cast<size_t>(b) * ctot + coff) * HWo + static_cast<size_t>(oy) * Wo + ox, HWo);
     }
   }
 }
@@ -331,12 +312,7 @@ unet_upsample_kernel(const float* __restrict__ mask, const float* __restrict__ d
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int c = 0; c < 4 + XS; ++c) {
-        const int yy = y0 - 1 + r, xx = xb - 1 + c;
-        const float dv = dp[min(max(yy, 0), h - 1) * w + min(max(xx, 0), w - 1)];
-        // disp * w_out / w_in in the reference's evaluation order (module.py:478); zero padding of unfold
-        P[r][c] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? dv * static_cast<float>(Wo) / static_cast<float>(w) : 0.f;
-      }
+      for (int c = 0; c < 4 + XS; ++c) P[r][c] = ts_tail::unet_patch_value(dp, y0 - 1 + r, xb - 1 + c, h, w, Wo);
     float res[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -355,31 +331,12 @@ unet_upsample_kernel(const float* __restrict__ mask, const float* __restrict__ d
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const int yy = y0 - 1 + r, xx = x0 - 1 + c;
-            const float dv = dp[min(max(yy, 0), h - 1) * w + min(max(xx, 0), w - 1)];
-            pd[r][c] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? dv * static_cast<float>(Wo) / static_cast<float>(w) : 0.f;
-          }
+          for (int c = 0; c < 4; ++c) pd[r][c] = ts_tail::unet_patch_value(dp, y0 - 1 + r, x0 - 1 + c, h, w, Wo);
       }
-      float mx = -INFINITY;
+      float mv[9];
 #pragma unroll
-      for (int k = 0; k < 9; ++k) mx = fmaxf(mx, m[k][v]);
-      const bool ix = x1 > x0;
-      float den = 0.f, acc = 0.f;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const float e = expf(m[k][v] - mx);
-        den += e;
-        const int ry = k / 3, rx = k % 3;            // patch row / column of (y0 + dy, x0 + dx)
-        const float a00 = pd[ry][rx];
-        const float a01 = ix ? pd[ry][rx + 1] : a00;
-        const float a10 = iy ? pd[ry + 1][rx] : a00;
-        const float a11 = iy ? (ix ? pd[ry + 1][rx + 1] : pd[ry + 1][rx]) : a01;
-        const float top = (1.f - lx) * a00 + lx * a01;
-        const float bot = (1.f - lx) * a10 + lx * a11;
-        acc += e * ((1.f - ly) * top + ly * bot);
-      }
-      res[v] = acc / den;
+      for (int k = 0; k < 9; ++k) mv[k] = m[k][v];
+      res[v] = ts_tail::unet_combine(mv, pd, lx, ly, x1 > x0, iy);
     }
     float* op = out + static_cast<size_t>(b) * HWo + static_cast<size_t>(oy) * Wo + oxv;
     if constexpr (V == 4) *reinterpret_cast<float4*>(op) = make_float4(res[0], res[1], res[2], res[3]);
@@ -428,9 +385,7 @@ resize_bilinear_pair_kernel(const float* __restrict__ x0, const float* __restric
     lin_src(sh, oy, h, y0, y1, ly);
     lin_src(sw, ox, w, xa, xb, lx);
     const float* p = x + static_cast<size_t>(bc) * h * w;
-    const float top = (1.f - lx) * p[y0 * w + xa] + lx * p[y0 * w + xb];
-    const float bot = (1.f - lx) * p[y1 * w + xa] + lx * p[y1 * w + xb];
-    out[i] = ((1.f - ly) * top + ly * bot) * vscale;
+    out[i] = ts_tail::bilinear_value(p[y0 * w + xa], p[y0 * w + xb], p[y1 * w + xa], p[y1 * w + xb], ly, lx, vscale);
   }
 }
 
