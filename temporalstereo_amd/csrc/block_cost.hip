@@ -1782,6 +1782,8 @@ int launch_bwd(const float* left, const float* right, const float* disp, const f
   }
   const bool vec = (W % 4 == 0) && ts::aligned16(left) && ts::aligned16(right) && ts::aligned16(grad_out) &&
                    (!SAMPLED || ts::aligned16(disp));
+  // the row and tile kernels write grad_left / grad_right as 16-byte stores (block_cost_bwd_main adds element by element)
+  const bool grads16 = (!grad_left || ts::aligned16(grad_left)) && (!grad_right || ts::aligned16(grad_right));
   const size_t lds_bytes = static_cast<size_t>(GRP) * TR * 4 * s.Wqp * sizeof(float);
   const bool stage = lds_bytes <= 64 * 1024;
   const int nitems = s.nbx * D;
@@ -1793,8 +1795,7 @@ int launch_bwd(const float* left, const float* right, const float* disp, const f
     static const bool rows = ts::env_not_zero("TS_K1_BWD_ROWS");
     const int rthreads = static_cast<int>(ts::round_up(static_cast<size_t>(s.nbx) * 4, ts::kWave));
     const size_t rlds = (static_cast<size_t>(GRP) * TR * 4 * s.Wqp + static_cast<size_t>(GRP) * TR * 4 * s.Wq) * sizeof(float);   // R rows + [GRP/2][TR][Wl] doubles
-    if (SAMPLED && rows && vec && rthreads <= 512 && rlds <= 80 * 1024 && (!grad_left || ts::aligned16(grad_left)) &&
-        (!grad_right || ts::aligned16(grad_right))) {
+    if (SAMPLED && rows && vec && grads16 && rthreads <= 512 && rlds <= 80 * 1024) {
       if (rthreads <= 256) {
         auto kern = &block_cost_bwd_rows<256>;
         if (rlds > 64 * 1024)
@@ -1810,7 +1811,7 @@ int launch_bwd(const float* left, const float* right, const float* disp, const f
     }
   }
   if (tile) {
-    ts::dispatch_bool(vec, [&](auto V) {
+    ts::dispatch_bool(vec && grads16, [&](auto V) {   // (the scalar form reads aligned inputs just as well)
       hipLaunchKernelGGL((block_cost_bwd_tile<SAMPLED, V()>), grid, dim3(tile_threads), tile_lds, st, left, right, disp,
                          grad_out, dP1, dP2, grad_left, grad_right, grad_disp, s);
     });
