@@ -177,6 +177,11 @@ splat_grad_flow(const float* __restrict__ input, const float* __restrict__ flow,
     const float ax = ox - fx0, ay = oy - fy0;         // fractional parts
     const bool inw = inside(t.x0, t.y0, W, H), ine = inside(t.x0 + 1, t.y0, W, H);
     const bool isw = inside(t.x0, t.y0 + 1, W, H), ise = inside(t.x0 + 1, t.y0 + 1, W, H);
+    if (!(inw | ine | isw | ise)) {      // dropped by the forward (its `continue`): no gradient, and no 0 * NaN from an inf / NaN flow
+      gflow[static_cast<size_t>(b) * 2 * HW + p] = 0.f;
+      gflow[static_cast<size_t>(b) * 2 * HW + HW + p] = 0.f;
+      continue;
+    }
     const int q = t.y0 * W + t.x0;
     float gx = 0.f, gy = 0.f;
     for (int c = 0; c < C; ++c) {
