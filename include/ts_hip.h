@@ -629,6 +629,43 @@ int ts_bn_small_train_bwd(const float* y, const float* g, const float* gamma, co
                           int B, int C, int N, long long y_bstride, long long y_cstride, long long g_bstride, long long g_cstride,
                           long long dy_bstride, long long dy_cstride, float eps, int act, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * ConvGRU: the gated recurrent cell of layers/conv_gru.py:4-28 as two launches, fp32 throughout (ABI 20).
+ *   z = sigmoid(convz([h, x]))  r = sigmoid(convr([h, x]))  q = tanh(convq([r*h, x]))  hidden = (1 - z) * h + z * q
+ * h [B,Ch,H,W] and x [B,Cx,H,W] are read in place (batch / channel strides in elements, H*W dense): no concatenation is written.
+ * Every other plane is dense [B,Ch,H,W].  The three 3x3 convolutions (padding 1, bias) run on the f32-input MFMA: an fmaf chain.
+ * ts_conv_gru_weight_layout  wz, wr, wq [Ch][Ch+Cx][3][3] (the framework's, contiguous) -> w_l, ts_conv_gru_weight_bytes(Ch, Cx) bytes,
+ *                            16-byte aligned: the gate rows [z | r] and the candidate rows in the kernels' chunked order.
+ * ts_conv_gru_gates_fwd      z and rh = r * h OVERWRITTEN; r too unless it is NULL (only a backward pass reads it).
+ * ts_conv_gru_out_fwd        out = hidden OVERWRITTEN from rh, x, z, h; q too unless it is NULL.  h strides as in the gates call.
+ * ts_conv_gru_gate_bwd_a     dq_pre = dout z (1 - q^2) (dense), dz_pre = dout (q - h) z (1 - z) (strided: a half of the gates' [dz | dr]
+ *                            buffer), dh = dout (1 - z) (dense), all OVERWRITTEN; N = H*W.
+ * ts_conv_gru_gate_bwd_b     d_rh (strided: the first Ch channels of the candidate convolution's input gradient), r, h ->
+ *                            dr_pre = d_rh h r (1 - r) (strided) OVERWRITTEN, dh += d_rh r.
+ * ts_conv_gru_grad_sum       dcat_g / dcat_q [B,Ch+Cx,N] dense, the input gradients of the gate / candidate convolutions
+ *                            (ts_conv3d_hw_bwd_data, D = 1): dh += dcat_g[:, :Ch]; dx [B,Cx,N] = dcat_g[:, Ch:] + dcat_q[:, Ch:] OVERWRITTEN,
+ *                            skipped when dx is NULL.
+ * The weight and bias gradients run on ts_conv3d_hw_bwd_weight (per gate and per source) and ts_channel_sum_fwd.  No atomics: every
+ * entry is bit-reproducible.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, overlapping strides), then
+ * Ch > 64, Cx > 64, an axis >= 2^20, a grid that does not fit (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL; r, q, dx may be NULL).
+ * ---------------------------------------------------------------------------------------- */
+size_t ts_conv_gru_weight_bytes(int Ch, int Cx);
+int ts_conv_gru_weight_layout(const float* wz, const float* wr, const float* wq, float* w_l, int Ch, int Cx, void* stream);
+int ts_conv_gru_gates_fwd(const float* h, const float* x, const float* w_l, const float* bz, const float* br, float* z, float* rh,
+                          float* r, int B, int Ch, int Cx, int H, int W, long long h_bstride, long long h_cstride,
+                          long long x_bstride, long long x_cstride, void* stream);
+int ts_conv_gru_out_fwd(const float* rh, const float* x, const float* w_l, const float* bq, const float* z, const float* h, float* out,
+                        float* q, int B, int Ch, int Cx, int H, int W, long long h_bstride, long long h_cstride,
+                        long long x_bstride, long long x_cstride, void* stream);
+int ts_conv_gru_gate_bwd_a(const float* dout, const float* z, const float* q, const float* h, float* dq_pre, float* dz_pre, float* dh,
+                           int B, int Ch, long long N, long long h_bstride, long long h_cstride, long long dz_bstride,
+                           long long dz_cstride, void* stream);
+int ts_conv_gru_gate_bwd_b(const float* d_rh, const float* r, const float* h, float* dr_pre, float* dh, int B, int Ch, long long N,
+                           long long drh_bstride, long long drh_cstride, long long h_bstride, long long h_cstride,
+                           long long dr_bstride, long long dr_cstride, void* stream);
+int ts_conv_gru_grad_sum(const float* dcat_g, const float* dcat_q, float* dh, float* dx, int B, int Ch, int Cx, long long N,
+                         void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

@@ -181,6 +181,13 @@ SIGNATURES = {
     "ts_spp3d_expand_bwd": (c_int, [c_f32p] * 5 + [c_int] * 11 + [ctypes.c_longlong] * 2 + [c_ptr]),
     "ts_depth_sum3_fwd": (c_int, [c_f32p] * 6 + [c_int] * 6 + [ctypes.c_longlong] * 8 + [c_ptr]),
     "ts_bn_small_train_bwd": (c_int, [c_f32p] * 7 + [c_int] * 3 + [ctypes.c_longlong] * 6 + [c_float, c_int, c_ptr]),
+    "ts_conv_gru_weight_bytes": (c_size, [c_int] * 2),
+    "ts_conv_gru_weight_layout": (c_int, [c_f32p] * 4 + [c_int] * 2 + [c_ptr]),
+    "ts_conv_gru_gates_fwd": (c_int, [c_f32p] * 8 + [c_int] * 5 + [ctypes.c_longlong] * 4 + [c_ptr]),
+    "ts_conv_gru_out_fwd": (c_int, [c_f32p] * 8 + [c_int] * 5 + [ctypes.c_longlong] * 4 + [c_ptr]),
+    "ts_conv_gru_gate_bwd_a": (c_int, [c_f32p] * 7 + [c_int] * 2 + [ctypes.c_longlong] * 5 + [c_ptr]),
+    "ts_conv_gru_gate_bwd_b": (c_int, [c_f32p] * 5 + [c_int] * 2 + [ctypes.c_longlong] * 7 + [c_ptr]),
+    "ts_conv_gru_grad_sum": (c_int, [c_f32p] * 4 + [c_int] * 3 + [ctypes.c_longlong, c_ptr]),
     "ts_reproject_memory_workspace_bytes": (c_size, [c_int] * 5),
     "ts_reproject_memory_fwd": (c_int, [c_f32p, ctypes.c_longlong, c_int, c_int, c_f32p, c_f32p, c_int, c_f32p, c_int, c_int,
                                         c_f32p, c_int, c_f32p, c_f32p, c_f32p, c_float, c_float, c_f32p, c_f32p, c_f32p,

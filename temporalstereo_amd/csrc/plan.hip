@@ -114,6 +114,8 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_bn_small_train_bwd),
     TS_PLAN_OP(ts_regress_convex_upsample_fwd), TS_PLAN_OP(ts_topk_softargmax_half_fwd),
     TS_PLAN_OP(ts_deconv2d_k4s2_unet_upsample_fwd),
+    TS_PLAN_OP(ts_conv_gru_weight_layout),  TS_PLAN_OP(ts_conv_gru_gates_fwd),      TS_PLAN_OP(ts_conv_gru_out_fwd),
+    TS_PLAN_OP(ts_conv_gru_gate_bwd_a),     TS_PLAN_OP(ts_conv_gru_gate_bwd_b),     TS_PLAN_OP(ts_conv_gru_grad_sum),
 };
 
 struct Call {

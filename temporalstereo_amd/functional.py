@@ -2830,3 +2830,143 @@ class FlowCorrBlock:
         ys = torch.arange(0, h, device=device, dtype=torch.float).view(1, 1, h, 1).expand(b, 1, h, w)
         grid = torch.cat((xs, ys), dim=1).detach()
         return grid, (grid if flow_init is None else grid + flow_init)
+
+
+# ---- ConvGRU (reference: layers/conv_gru.py:4-28) --------------------------------------------------------------------------------------
+CONV_GRU_MAX_PLANES = 64          # the kernel path's envelope on either side (csrc/conv_gru.hip)
+
+
+def conv_gru_supported(hidden_planes, in_planes):
+    return 1 <= hidden_planes <= CONV_GRU_MAX_PLANES and 1 <= in_planes <= CONV_GRU_MAX_PLANES
+
+
+def _plane_view(t):
+    """A [B,C,H,W] tensor the kernels can read in place (dense planes, batch / channel strides that do not overlap), else a copy."""
+    B, C, H, W = t.shape
+    if t.stride(3) == 1 and t.stride(2) == W and t.stride(1) >= H * W and (B == 1 or t.stride(0) >= t.stride(1) * (C - 1) + H * W):
+        return t
+    return _lib.contiguous(t)
+
+
+def _gru_bwd_weight_layout(ws, Cin):
+    """[sum of rows][9][pad(Cin)] with the taps flipped: the array ts_conv3d_hw_bwd_data takes for the convolution whose output rows are
+    the rows of `ws` stacked (one ts_conv_weight_layout launch per weight, into its slice)."""
+    cp = _cpad(Cin)
+    rows = sum(w.shape[0] for w in ws)
+    out = torch.empty((rows, 9, cp), device=ws[0].device, dtype=torch.float32)
+    at = 0
+    for w in ws:
+        n = w.shape[0]
+        _lib.check(_lib.lib().ts_conv_weight_layout(_lib.ptr(w), _lib.ptr(out[at:]), n, 9, Cin, cp, Cin * 9, 9, 1, 1, _stream()),
+                   "ts_conv_weight_layout")
+        at += n
+    return out
+
+
+class _ConvGRU(torch.autograd.Function):
+    """hidden = (1 - z) * h + z * q of the gated recurrent cell in two launches (ts_conv_gru_gates_fwd, ts_conv_gru_out_fwd) after
+    one weight-layout launch; h and x are read in place.  r and q are kept only when a backward pass can ask for them.
+    backward: ts_conv_gru_gate_bwd_a -> candidate convolution's gradients -> ts_conv_gru_gate_bwd_b -> gate convolutions' gradients ->
+    ts_conv_gru_grad_sum; the convolutions' own gradients on ts_conv3d_hw_bwd_{data,weight} (D = 1), the biases' on ts_channel_sum_fwd."""
+
+    @staticmethod
+    def forward(ctx, h, x, wz, bz, wr, br, wq, bq, gates):
+        _require_gpu(h, x, wz, bz, wr, br, wq, bq)
+        if h.dim() != 4 or x.dim() != 4 or h.shape[0] != x.shape[0] or h.shape[2:] != x.shape[2:]:
+            raise ValueError("conv_gru: last_hidden [B,Ch,H,W] and x [B,Cx,H,W] expected, got %s and %s" % (tuple(h.shape), tuple(x.shape)))
+        B, Ch, H, W = h.shape
+        Cx = x.shape[1]
+        for w in (wz, wr, wq):
+            if tuple(w.shape) != (Ch, Ch + Cx, 3, 3):
+                raise ValueError("conv_gru: weights must be [%d, %d, 3, 3], got %s" % (Ch, Ch + Cx, tuple(w.shape)))
+        for b in (bz, br, bq):
+            if tuple(b.shape) != (Ch,):
+                raise ValueError("conv_gru: biases must be [%d], got %s" % (Ch, tuple(b.shape)))
+        h, x = _plane_view(h), _plane_view(x)
+        wz, wr, wq = (_lib.contiguous(w.detach()) for w in (wz, wr, wq))
+        bz, br, bq = (_lib.contiguous(b.detach()) for b in (bz, br, bq))
+        train = any(ctx.needs_input_grad[:8])
+        L = _lib.lib()
+        nbytes = _q("ts_conv_gru_weight_bytes", Ch, Cx)
+        if not nbytes:
+            raise RuntimeError("conv_gru: %d hidden / %d input planes are outside the kernel path (1..%d each)" % (Ch, Cx, CONV_GRU_MAX_PLANES))
+        w_l = torch.empty(nbytes // 4, device=h.device, dtype=torch.float32)
+        _lib.check(L.ts_conv_gru_weight_layout(_lib.ptr(wz), _lib.ptr(wr), _lib.ptr(wq), _lib.ptr(w_l), Ch, Cx, _stream()),
+                   "ts_conv_gru_weight_layout")
+        new = lambda: torch.empty((B, Ch, H, W), device=h.device, dtype=torch.float32)
+        keep = train or gates
+        z, rh, out = new(), new(), new()
+        r, q = (new(), new()) if keep else (None, None)
+        strides = (h.stride(0), h.stride(1), x.stride(0), x.stride(1))
+        _lib.check(L.ts_conv_gru_gates_fwd(_lib.ptr(h), _lib.ptr(x), _lib.ptr(w_l), _lib.ptr(bz), _lib.ptr(br), _lib.ptr(z), _lib.ptr(rh),
+                                           _lib.ptr(r), B, Ch, Cx, H, W, *strides, _stream()), "ts_conv_gru_gates_fwd")
+        _lib.check(L.ts_conv_gru_out_fwd(_lib.ptr(rh), _lib.ptr(x), _lib.ptr(w_l), _lib.ptr(bq), _lib.ptr(z), _lib.ptr(h), _lib.ptr(out),
+                                         _lib.ptr(q), B, Ch, Cx, H, W, *strides, _stream()), "ts_conv_gru_out_fwd")
+        if train:
+            ctx.save_for_backward(h, x, wz, wr, wq, z, r, q, rh)
+        if gates:
+            ctx.mark_non_differentiable(z, r, q)
+            return out, z, r, q
+        return out
+
+    @staticmethod
+    def backward(ctx, dout, *unused):
+        h, x, wz, wr, wq, z, r, q, rh = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        B, Ch, H, W = h.shape
+        Cx, C, N = x.shape[1], h.shape[1] + x.shape[1], H * W
+        L, st = _lib.lib(), _stream()
+        dout = _lib.contiguous(dout)
+        dev = h.device
+        new = lambda c: torch.empty((B, c, H, W), device=dev, dtype=torch.float32)
+        dq_pre, dgate, dh = new(Ch), new(2 * Ch), new(Ch)              # dgate = [dz_pre | dr_pre]: the gate convolution's cotangent
+        _lib.check(L.ts_conv_gru_gate_bwd_a(_lib.ptr(dout), _lib.ptr(z), _lib.ptr(q), _lib.ptr(h), _lib.ptr(dq_pre), _lib.ptr(dgate),
+                                            _lib.ptr(dh), B, Ch, N, h.stride(0), h.stride(1), 2 * Ch * N, N, st), "ts_conv_gru_gate_bwd_a")
+        dcat_q, dcat_g = new(C), new(C)
+        rc = L.ts_conv3d_hw_bwd_data(_lib.ptr(dq_pre), _lib.ptr(_gru_bwd_weight_layout((wq,), C)), _lib.ptr(dcat_q), B, C, Ch, 1, H, W, 1, 1, 0,
+                                     Ch * N, N, C * N, N, st)
+        _lib.check(rc, "ts_conv3d_hw_bwd_data")
+        dr_pre = dgate[:, Ch:]
+        _lib.check(L.ts_conv_gru_gate_bwd_b(_lib.ptr(dcat_q), _lib.ptr(r), _lib.ptr(h), _lib.ptr(dr_pre), _lib.ptr(dh), B, Ch, N, C * N, N,
+                                            h.stride(0), h.stride(1), 2 * Ch * N, N, st), "ts_conv_gru_gate_bwd_b")
+        rc = L.ts_conv3d_hw_bwd_data(_lib.ptr(dgate), _lib.ptr(_gru_bwd_weight_layout((wz, wr), C)), _lib.ptr(dcat_g), B, C, 2 * Ch, 1, H, W,
+                                     1, 1, 0, 2 * Ch * N, N, C * N, N, st)
+        _lib.check(rc, "ts_conv3d_hw_bwd_data")
+        dx = new(Cx) if need[1] else None
+        _lib.check(L.ts_conv_gru_grad_sum(_lib.ptr(dcat_g), _lib.ptr(dcat_q), _lib.ptr(dh), _lib.ptr(dx), B, Ch, Cx, N, st),
+                   "ts_conv_gru_grad_sum")
+
+        def wgrad(dy, dy_bs, src_h):
+            """dw [Ch, Ch + Cx, 3, 3] of one gate: ts_conv3d_hw_bwd_weight holds at most 64 output channels and reads one source, so it
+            runs per source and the two blocks are joined along the input channels."""
+            parts = []
+            for src, cin in ((src_h, Ch), (x, Cx)):
+                dw = torch.empty((Ch, cin, 3, 3), device=dev, dtype=torch.float32)
+                ws, nws = _wgrad_workspace(cin, Ch, 9, dev)
+                rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(src), _lib.ptr(dy), _lib.ptr(dw), B, cin, Ch, 1, H, W, 1, 1, src.stride(0), src.stride(1),
+                                               dy_bs, N, _lib.ptr(ws), nws, st)
+                _lib.check(rc, "ts_conv3d_hw_bwd_weight")
+                parts.append(dw)
+            return torch.cat(parts, 1)
+
+        dwz = wgrad(dgate, 2 * Ch * N, h) if need[2] else None
+        dwr = wgrad(dr_pre, 2 * Ch * N, h) if need[4] else None
+        dwq = wgrad(dq_pre, Ch * N, rh) if need[6] else None
+        dbz = dbr = dbq = None
+        if need[3] or need[5]:
+            both = _channel_sum(dgate)
+            dbz, dbr = (both[:Ch] if need[3] else None), (both[Ch:] if need[5] else None)
+        if need[7]:
+            dbq = _channel_sum(dq_pre)
+        return (dh if need[0] else None), dx, dwz, dbz, dwr, dbr, dwq, dbq, None
+
+
+def conv_gru(last_hidden, x, wz, bz, wr, br, wq, bq, return_gates=False):
+    """One step of the gated recurrent cell (layers/conv_gru.py:19-28) on the HIP kernels: z = sigmoid(convz([h, x])),
+    r = sigmoid(convr([h, x])), q = tanh(convq([r*h, x])), hidden = (1 - z) * h + z * q, the convolutions 3x3 with padding 1 and bias.
+    fp32 GPU tensors, 1..64 planes on either side; gradients for last_hidden, x and the six parameters.  return_gates=True returns
+    (hidden, z, r, q), the gates detached."""
+    args = (last_hidden, x, wz, bz, wr, br, wq, bq)
+    if not torch.is_grad_enabled():           # nothing can ask for a gradient: r and q are neither allocated nor stored
+        args = tuple(a.detach() for a in args)
+    return _ConvGRU.apply(*args, bool(return_gates))

@@ -1853,6 +1853,98 @@ def spp3d_cases(M):
     print("\n".join(lines))
 
 
+def conv_gru_cases(M):
+    """tests/golden/conv_gru_*.npz: the reference's own ConvGRU (layers/conv_gru.py:4-28) on the CPU, in fp32 and fp64: one step with
+    its gates, three chained steps, and the backward of a seeded cotangent; dev_* = how far its fp32 run lies from its fp64 run."""
+    import importlib.util
+    import conv_gru_ref
+    spec = importlib.util.spec_from_file_location("ref_conv_gru", os.path.join(ref_import.REFERENCE_ROOT, "architecture", "modeling", "layers",
+                                                                               "conv_gru.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    RefConvGRU = mod.ConvGRU
+    shapes = [("a", (2, 12, 5, 9, 37), True), ("b", (1, 32, 48, 17, 70), True), ("c", (2, 64, 64, 6, 20), True), ("d", (1, 8, 8, 1, 1), False)]
+    lines = ["conv_gru_*.npz: tools/gen_golden.py --only-convgru, numpy %s, torch %s CPU -- the reference's own ConvGRU" % (np.__version__, torch.__version__),
+             "(architecture/modeling/layers/conv_gru.py:4-28), built and called on seeded inputs in float32 and in float64: one step (the gates",
+             "taken from forward hooks on convz / convr / convq), three chained steps in which the output is the next last_hidden and x stays",
+             "the same, and the backward of a seeded cotangent of the third output in both (shape d: forward only).",
+             "Inputs, all kept as their seed (tests/conv_gru_ref.py fixture_state / fixture_input / fixture_cotangent draw them again):",
+             "convolution weights N(0,1) * 2 / sqrt(9 (Ch + Cx)), biases N(0, 0.5), last_hidden = tanh(N(0,1)), x = N(0,1), the cotangent k / 8",
+             "with k an integer in [-8, 8].  On shapes with at least 1000 gate values the seed is drawn again until z and r of the fp64 run each go",
+             "below 0.05 and above 0.95 (asserted).",
+             "Stored: seed, shape (B, Ch, Cx, H, W), keys (the reference's state-dict keys in order), z, r, q, out (one step, fp32), out3, grad_h,",
+             "grad_x, grad_<parameter key>; an array of more than %d elements is stored at %d seeded flat positions (conv_gru_ref.sample)." % (conv_gru_ref.SAMPLE, conv_gru_ref.SAMPLE),
+             "dev_<stage> = max |fp32 run - fp64 run| and rel_grad_<key> = relative L2 of the fp32 run's gradient against the fp64 run's, both over",
+             "the WHOLE arrays; max_<stage> = max |stage| of the fp64 run."]
+    total = 0
+    for tag, shape, backward in shapes:
+        B, Ch, Cx, H, W = shape
+        base = synth.SEED0 + 12000 + 1000 * ord(tag)
+
+        def run(seed, dt):
+            ref = RefConvGRU(Cx, Ch)
+            missing = ref.load_state_dict(conv_gru_ref.fixture_state(seed, Ch, Cx, dt), strict=True)
+            assert not missing.missing_keys and not missing.unexpected_keys
+            ref = ref.to(dt)
+            grab = {}
+            def keep(name):
+                def hook(m, a, o):
+                    grab[name] = o.detach().clone()           # (returns None: the output is not replaced)
+                return hook
+            hooks = [getattr(ref, n).register_forward_hook(keep(n)) for n in ("convz", "convr", "convq")]
+            h, x = conv_gru_ref.fixture_input(seed, shape, dt)
+            h.requires_grad_(backward)
+            x.requires_grad_(backward)
+            out = ref(h, x)
+            res = dict(z=torch.sigmoid(grab["convz"]), r=torch.sigmoid(grab["convr"]), q=torch.tanh(grab["convq"]), out=out.detach())
+            for hk in hooks:
+                hk.remove()
+            out3 = ref(ref(out, x), x)
+            res["out3"] = out3.detach()
+            if backward:
+                out3.backward(conv_gru_ref.fixture_cotangent(seed, out3.shape, dt))
+                res["grad_h"], res["grad_x"] = h.grad.detach(), x.grad.detach()
+                for k, p in ref.named_parameters():
+                    res["grad_" + k] = p.grad.detach()
+            return res, list(ref.state_dict().keys())
+
+        for attempt in range(200):
+            seed = base + attempt
+            r32, keys = run(seed, torch.float32)
+            r64, _ = run(seed, torch.float64)
+            wide = all(float(r64[g].min()) < 0.05 and float(r64[g].max()) > 0.95 for g in ("z", "r"))
+            if wide or r64["z"].numel() < 1000:
+                break
+        assert wide or r64["z"].numel() < 1000, tag
+        assert keys == list(conv_gru_ref.KEYS)
+        # the restatement stands where the reference stands
+        own = conv_gru_ref.run(seed, shape, torch.float64, backward)
+        for k in r64:
+            assert float((own[k] - r64[k]).abs().max()) <= 1e-10 * max(1.0, float(r64[k].abs().max())), (tag, k, float((own[k] - r64[k]).abs().max()))
+        arrs = dict(seed=seed, shape=np.array(shape), keys=np.array(keys), attempts=attempt + 1)
+        rels = []
+        for k in r32:
+            arrs[k] = conv_gru_ref.sample(r32[k], seed)
+            if k.startswith("grad_"):
+                arrs["rel_" + k] = float((r32[k].double() - r64[k]).norm() / r64[k].norm())
+                rels.append(arrs["rel_" + k])
+            else:
+                arrs["dev_" + k] = float((r32[k].double() - r64[k]).abs().max())
+                arrs["max_" + k] = float(r64[k].abs().max())
+        size = save_fixed("conv_gru_" + tag, **arrs)
+        assert size <= 754 * 1024, (tag, size)
+        total += size
+        lines.append("conv_gru_%s  B=%d Ch=%d Cx=%d H=%d W=%d  seed %d (draw %d); z %.3f .. %.3f, r %.3f .. %.3f; dev z %.3g r %.3g q %.3g out %.3g "
+                     "out3 %.3g; rel_grad %s; %.0f KB"
+                     % (tag, B, Ch, Cx, H, W, seed, attempt + 1, float(r64["z"].min()), float(r64["z"].max()), float(r64["r"].min()),
+                        float(r64["r"].max()), arrs["dev_z"], arrs["dev_r"], arrs["dev_q"], arrs["dev_out"], arrs["dev_out3"],
+                        ("%.3g .. %.3g" % (min(rels), max(rels))) if rels else "-", size / 1024))
+    lines.append("total %.0f KB" % (total / 1024))
+    with open(os.path.join(OUT, "PROVENANCE_conv_gru.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def save_fixed(name, **arrs):
     """`save` with the archive's time stamps pinned, so that a fixture regenerates byte for byte."""
     import zipfile
@@ -2233,6 +2325,9 @@ def main():
         return
     if "--only-spp3d" in sys.argv:
         spp3d_cases(M)
+        return
+    if "--only-convgru" in sys.argv:
+        conv_gru_cases(M)
         return
     if "--only-flow-frame" in sys.argv:
         flow_frame_cases(M)
