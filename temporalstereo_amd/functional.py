@@ -2385,19 +2385,73 @@ def inverse_warp(img, motion, mode='disparity', K=None, inv_K=None, T_target_to_
     return res[0], output
 
 
-# ----------------------------------------------------------------------------------- CorrBlock: the RAFT-Stereo correlation pyramid
-_RAFT_MAX_LEVELS = 7
+# ------------------------------------------- CorrBlock and FlowCorrBlock: the correlation pyramids of RAFT-Stereo (1-D) and RAFT (2-D)
+class _CorrKind:
+    """What differs on the host between the two correlation pyramids: CorrBlock's row correlation for disparity
+    (csrc/raft_corr.hip) and FlowCorrBlock's all-pairs cost for flow (csrc/flow_corr.hip).  Their C entries
+    ts_<prefix>_{pyramid,lookup}_{fwd,bwd} have the same signatures and conventions (include/ts_hip.h), so the buffer layout,
+    the level count of a buffer, the argument checks and the autograd Functions below are written once over a kind."""
+
+    def __init__(self, prefix, max_levels, motion, channels, level_shapes, level_ok, window_dims, map_name, refuse_levels):
+        self.prefix = prefix                    # of the C entries and of every message
+        self.max_levels = max_levels            # what one launch of the kind's build kernel pools
+        self.motion, self.channels = motion, channels       # the lookup's argument: its name and its channel count
+        self.level_shapes = level_shapes        # (H, W, num_levels) -> [(h_i, w_i)], the target map of every level
+        self.level_ok = level_ok                # (h_i, w_i) -> whether such a level exists
+        self.window_dims = window_dims          # a level's window has (2 * radius + 1) ** window_dims taps
+        self.map_name = map_name                # (H, W) -> what a message calls the target map
+        self.refuse_levels = refuse_levels      # (H, W, num_levels): raises the kind's own refusal of a map or a level
+        # The entries' names.  A caller resolves them on _lib.lib() when it calls, never sooner: a plan Recorder swaps its proxy
+        # in per thread.  (Spelled out at the call sites: the lookups are launch-bound and a helper's frame shows in their time.)
+        self.pyramid_fwd, self.pyramid_bwd, self.lookup_fwd, self.lookup_bwd = (
+            "ts_%s_%s" % (prefix, e) for e in ("pyramid_fwd", "pyramid_bwd", "lookup_fwd", "lookup_bwd"))
+
+    def level_views(self, pyramid, B, H, W, num_levels):
+        N, views, o = B * H * W, [], 0
+        for h, w in self.level_shapes(H, W, num_levels):
+            n = N * h * w
+            views.append(pyramid[o:o + n].view(N, 1, h, w))
+            o += n
+        return views
+
+    def levels_of(self, pyramid, N, H, W):
+        """num_levels of a pyramid buffer of N source pixels over an H x W map: its length decides (a level that does not exist
+        adds nothing to the length and is not counted)."""
+        if pyramid.dim() != 1 or N <= 0 or pyramid.numel() % N:
+            raise ValueError("%s_lookup: pyramid must be the 1-D buffer of %s_pyramid for %d pixels, got %s"
+                             % (self.prefix, self.prefix, N, tuple(pyramid.shape)))
+        per, s = pyramid.numel() // N, 0
+        for i, (h, w) in enumerate(self.level_shapes(H, W, self.max_levels)):
+            s += h * w
+            if s == per and self.level_ok(h, w):
+                return i + 1
+        raise ValueError("%s_lookup: a pyramid of %d floats per pixel is no pyramid of %s" % (self.prefix, per, self.map_name(H, W)))
+
+    def check_features(self, fmap1, fmap2, num_levels):
+        s1, s2 = tuple(fmap1.shape), tuple(fmap2.shape)
+        if len(s1) != 4 or len(s2) != 4:
+            raise ValueError("%s: fmap1 and fmap2 must be [B,C,H,W], got %s and %s" % (self.prefix, s1, s2))
+        if s1 != s2:
+            raise ValueError("%s: fmap1 and fmap2 differ in shape (%s and %s)" % (self.prefix, s1, s2))
+        if num_levels < 1:
+            raise ValueError("%s: num_levels must be >= 1, got %d" % (self.prefix, num_levels))
+        if num_levels > self.max_levels:
+            raise ValueError("%s: num_levels = %d, the HIP kernel pools at most %d levels" % (self.prefix, num_levels, self.max_levels))
+        self.refuse_levels(s1[2], s1[3], num_levels)
+        _require_gpu(fmap1, fmap2)
+
+    def check_motion(self, motion, radius, size=None):
+        shape = tuple(motion.shape)         # once: every `.shape` builds a new object, and the lookups are launch-bound
+        if len(shape) != 4 or shape[1] != self.channels:
+            raise ValueError("%s: %s must be [B,%d,H,W] (%d channel%s), got %s"
+                             % (self.prefix, self.motion, self.channels, self.channels, "s" * (self.channels > 1), shape))
+        if size is not None and (shape[0], shape[2], shape[3]) != size:
+            raise ValueError("%s: %s %s does not match the feature maps' (B, H, W) = %s" % (self.prefix, self.motion, shape, size))
+        if radius < 0:
+            raise ValueError("%s: radius must be >= 0, got %d" % (self.prefix, radius))
 
 
-def _raft_level_widths(W, num_levels):
-    return [W >> i for i in range(num_levels)]
-
-
-def _raft_check_levels(W, num_levels):
-    if num_levels < 1:
-        raise ValueError("raft_corr: num_levels must be >= 1, got %d" % num_levels)
-    if num_levels > _RAFT_MAX_LEVELS:
-        raise ValueError("raft_corr: num_levels = %d, the HIP kernel pools at most %d levels" % (num_levels, _RAFT_MAX_LEVELS))
+def _raft_refuse_levels(H, W, num_levels):
     if W < 2:
         raise ValueError("raft_corr: W = %d, need W >= 2 (the lookup divides by W - 1)" % W)
     if (W >> (num_levels - 1)) < 1:
@@ -2405,140 +2459,131 @@ def _raft_check_levels(W, num_levels):
                          "avg_pool2d raises there)" % (W, num_levels, num_levels - 1))
 
 
-def raft_corr_level_views(pyramid, B, H, W, num_levels):
-    """The levels of a pyramid buffer as the reference's `corr_pyramid` entries: [B*H*W, 1, 1, W >> i] views (no copies)."""
-    N, views, o = B * H * W, [], 0
-    for Wi in _raft_level_widths(W, num_levels):
-        views.append(pyramid[o:o + N * Wi].view(N, 1, 1, Wi))
-        o += N * Wi
-    return views
+def _flow_refuse_levels(H, W, num_levels):
+    for i in range(num_levels):
+        if (H >> i) < 2 or (W >> i) < 2:
+            raise ValueError("flow_corr: level %d of a %d x %d map is %d x %d, need >= 2 x 2 (the lookup divides by H_i - 1 and "
+                             "W_i - 1)" % (i, H, W, H >> i, W >> i))
 
 
-def _raft_levels_of(pyramid, N, W):
-    """num_levels of a pyramid buffer of N pixels and width W (its length decides: the level widths W >> i are positive)."""
-    if pyramid.dim() != 1 or N <= 0 or pyramid.numel() % N:
-        raise ValueError("raft_corr_lookup: pyramid must be the 1-D buffer of raft_corr_pyramid for %d pixels, got %s" % (N, tuple(pyramid.shape)))
-    per, s = pyramid.numel() // N, 0
-    for L in range(1, _RAFT_MAX_LEVELS + 1):
-        s += W >> (L - 1)
-        if s == per and (W >> (L - 1)) >= 1:
-            return L
-    raise ValueError("raft_corr_lookup: a pyramid of %d floats per pixel is no pyramid of width %d" % (per, W))
+# The level limits: 7 is kMaxLevels of csrc/corr_common.hpp, the deepest level the 64-wide tile of csrc/raft_corr.hip still pools by
+# itself (64 >> 6 == 1); csrc/flow_corr.hip pools levels 1..3 from an 8-row patch of the level-0 tile, hence 4.
+_RAFT = _CorrKind("raft_corr", 7, "disp", 1, lambda H, W, L: [(1, W >> i) for i in range(L)], lambda h, w: w >= 1, 1,
+                  lambda H, W: "width %d" % W, _raft_refuse_levels)
+_FLOW = _CorrKind("flow_corr", 4, "coords", 2, lambda H, W, L: [(H >> i, W >> i) for i in range(L)], lambda h, w: h >= 2 and w >= 2, 2,
+                  lambda H, W: "a %d x %d map" % (H, W), _flow_refuse_levels)
 
 
-class _RaftCorrPyramid(torch.autograd.Function):
-    """ts_raft_corr_pyramid_fwd / ts_raft_corr_pyramid_bwd (the cotangent keeps its levels: folded while it is staged)."""
+class _CorrPyramid(torch.autograd.Function):
+    """ts_*_corr_pyramid_fwd / ts_*_corr_pyramid_bwd (the cotangent keeps its levels: folded while it is staged)."""
 
     @staticmethod
-    def forward(ctx, fmap1, fmap2, num_levels):
+    def forward(ctx, kind, fmap1, fmap2, num_levels):
         B, C, H, W = fmap1.shape
-        pyr = torch.empty(B * H * W * sum(_raft_level_widths(W, num_levels)), device=fmap1.device, dtype=torch.float32)
-        p = _lib.ptr
-        _lib.check(_lib.lib().ts_raft_corr_pyramid_fwd(p(fmap1), p(fmap2), p(pyr), B, C, H, W, num_levels, _stream()),
-                   "ts_raft_corr_pyramid_fwd")
+        pyr = torch.empty(B * H * W * sum([h * w for h, w in kind.level_shapes(H, W, num_levels)]), device=fmap1.device, dtype=torch.float32)
+        p, entry = _lib.ptr, kind.pyramid_fwd
+        _lib.check(getattr(_lib.lib(), entry)(p(fmap1), p(fmap2), p(pyr), B, C, H, W, num_levels, _stream()), entry)
         ctx.save_for_backward(fmap1, fmap2)
-        ctx.num_levels = num_levels
+        ctx.geom = (kind, num_levels)
         return pyr
 
     @staticmethod
     def backward(ctx, g):
         fmap1, fmap2 = ctx.saved_tensors
+        kind, L = ctx.geom
         B, C, H, W = fmap1.shape
-        g1 = torch.empty_like(fmap1) if ctx.needs_input_grad[0] else None
-        g2 = torch.empty_like(fmap2) if ctx.needs_input_grad[1] else None
+        g1 = torch.empty_like(fmap1) if ctx.needs_input_grad[1] else None
+        g2 = torch.empty_like(fmap2) if ctx.needs_input_grad[2] else None
         if g1 is None and g2 is None:
-            return None, None, None
-        g = _lib.contiguous(g)
-        p = _lib.ptr
-        _lib.check(_lib.lib().ts_raft_corr_pyramid_bwd(p(g), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, ctx.num_levels, _stream()),
-                   "ts_raft_corr_pyramid_bwd")
-        return g1, g2, None
-
-
-def _raft_lookup_fwd(pyramid, disp, num_levels, radius):
-    B, _, H, W = disp.shape
-    out = torch.empty((B, num_levels * (2 * radius + 1), H, W), device=disp.device, dtype=torch.float32)
-    p = _lib.ptr
-    _lib.check(_lib.lib().ts_raft_corr_lookup_fwd(p(pyramid), p(disp), p(out), B, H, W, num_levels, radius, _stream()),
-               "ts_raft_corr_lookup_fwd")
-    return out
-
-
-class _RaftCorrLookup(torch.autograd.Function):
-    """ts_raft_corr_lookup_fwd / ts_raft_corr_lookup_bwd with fold = 0: the gradient with respect to a free pyramid, level by level."""
-
-    @staticmethod
-    def forward(ctx, pyramid, disp, num_levels, radius):
-        ctx.save_for_backward(pyramid, disp)
-        ctx.geom = (num_levels, radius)
-        return _raft_lookup_fwd(pyramid, disp, num_levels, radius)
-
-    @staticmethod
-    def backward(ctx, g):
-        pyramid, disp = ctx.saved_tensors
-        L, r = ctx.geom
-        B, _, H, W = disp.shape
-        gp = torch.empty_like(pyramid) if ctx.needs_input_grad[0] else None
-        gd = torch.empty_like(disp) if ctx.needs_input_grad[1] else None
-        if gp is None and gd is None:
             return None, None, None, None
         g = _lib.contiguous(g)
         p = _lib.ptr
-        _lib.check(_lib.lib().ts_raft_corr_lookup_bwd(p(pyramid), p(disp), p(g), p(gd), p(gp), B, H, W, L, r, 0, _stream()),
-                   "ts_raft_corr_lookup_bwd")
-        return gp, gd, None, None
+        _lib.check(getattr(_lib.lib(), kind.pyramid_bwd)(p(g), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, L, _stream()), kind.pyramid_bwd)
+        return None, g1, g2, None
 
 
-class _RaftCorrBlockLookup(torch.autograd.Function):
-    """The lookup of a CorrBlock, differentiable in the FEATURES the pyramid was built from: backward is ts_raft_corr_lookup_bwd
-    with fold = 1 (one [B*H*W, W] cotangent of level 0, written once) and ts_raft_corr_pyramid_bwd on it -- the per-level
-    cotangent of the pyramid is never materialised."""
+def _corr_lookup_fwd(kind, pyramid, motion, num_levels, radius):
+    B, _, H, W = motion.shape
+    out = torch.empty((B, num_levels * (2 * radius + 1) ** kind.window_dims, H, W), device=motion.device, dtype=torch.float32)
+    p, entry = _lib.ptr, kind.lookup_fwd
+    _lib.check(getattr(_lib.lib(), entry)(p(pyramid), p(motion), p(out), B, H, W, num_levels, radius, _stream()), entry)
+    return out
+
+
+class _CorrLookup(torch.autograd.Function):
+    """ts_*_corr_lookup_fwd / ts_*_corr_lookup_bwd with fold = 0: the gradient with respect to a free pyramid, level by level."""
 
     @staticmethod
-    def forward(ctx, fmap1, fmap2, pyramid, disp, num_levels, radius):
-        ctx.save_for_backward(fmap1, fmap2, pyramid, disp)
-        ctx.geom = (num_levels, radius)
-        return _raft_lookup_fwd(pyramid, disp, num_levels, radius)
+    def forward(ctx, kind, pyramid, motion, num_levels, radius):
+        ctx.save_for_backward(pyramid, motion)
+        ctx.geom = (kind, num_levels, radius)
+        return _corr_lookup_fwd(kind, pyramid, motion, num_levels, radius)
 
     @staticmethod
     def backward(ctx, g):
-        fmap1, fmap2, pyramid, disp = ctx.saved_tensors
-        L, r = ctx.geom
+        pyramid, motion = ctx.saved_tensors
+        kind, L, r = ctx.geom
+        B, _, H, W = motion.shape
+        gp = torch.empty_like(pyramid) if ctx.needs_input_grad[1] else None
+        gm = torch.empty_like(motion) if ctx.needs_input_grad[2] else None
+        if gp is None and gm is None:
+            return None, None, None, None, None
+        g = _lib.contiguous(g)
+        p = _lib.ptr
+        _lib.check(getattr(_lib.lib(), kind.lookup_bwd)(p(pyramid), p(motion), p(g), p(gm), p(gp), B, H, W, L, r, 0, _stream()), kind.lookup_bwd)
+        return None, gp, gm, None, None
+
+
+class _CorrBlockLookup(torch.autograd.Function):
+    """The lookup of a block, differentiable in the FEATURES the pyramid was built from: backward is ts_*_corr_lookup_bwd with
+    fold = 1 (one [B*H*W, h_0*w_0] cotangent of level 0, written once) and ts_*_corr_pyramid_bwd on it with levels = 1 -- the
+    per-level cotangent of the pyramid is never materialised."""
+
+    @staticmethod
+    def forward(ctx, kind, fmap1, fmap2, pyramid, motion, num_levels, radius):
+        ctx.save_for_backward(fmap1, fmap2, pyramid, motion)
+        ctx.geom = (kind, num_levels, radius)
+        return _corr_lookup_fwd(kind, pyramid, motion, num_levels, radius)
+
+    @staticmethod
+    def backward(ctx, g):
+        fmap1, fmap2, pyramid, motion = ctx.saved_tensors
+        kind, L, r = ctx.geom
         B, C, H, W = fmap1.shape
-        need1, need2, _, needd = ctx.needs_input_grad[:4]
-        if not (need1 or need2 or needd):
-            return (None,) * 6
+        _, need1, need2, _, needm = ctx.needs_input_grad[:5]
+        if not (need1 or need2 or needm):
+            return (None,) * 7
         g = _lib.contiguous(g)
         p = _lib.ptr
         feats = need1 or need2
-        G = torch.empty(B * H * W * W, device=g.device, dtype=torch.float32) if feats else None
-        gd = torch.empty_like(disp) if needd else None
-        _lib.check(_lib.lib().ts_raft_corr_lookup_bwd(p(pyramid), p(disp), p(g), p(gd), p(G), B, H, W, L, r, 1, _stream()),
-                   "ts_raft_corr_lookup_bwd")
+        (h0, w0), = kind.level_shapes(H, W, 1)
+        G = torch.empty(B * H * W * h0 * w0, device=g.device, dtype=torch.float32) if feats else None
+        gm = torch.empty_like(motion) if needm else None
+        _lib.check(getattr(_lib.lib(), kind.lookup_bwd)(p(pyramid), p(motion), p(g), p(gm), p(G), B, H, W, L, r, 1, _stream()), kind.lookup_bwd)
         g1 = torch.empty_like(fmap1) if need1 else None
         g2 = torch.empty_like(fmap2) if need2 else None
         if feats:
-            _lib.check(_lib.lib().ts_raft_corr_pyramid_bwd(p(G), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, 1, _stream()),
-                       "ts_raft_corr_pyramid_bwd")
-        return g1, g2, None, gd, None, None
+            _lib.check(getattr(_lib.lib(), kind.pyramid_bwd)(p(G), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, 1, _stream()), kind.pyramid_bwd)
+        return None, g1, g2, None, gm, None, None
 
 
-def _raft_check_features(fmap1, fmap2, num_levels):
-    if fmap1.dim() != 4 or fmap2.dim() != 4:
-        raise ValueError("raft_corr: fmap1 and fmap2 must be [B,C,H,W], got %s and %s" % (tuple(fmap1.shape), tuple(fmap2.shape)))
-    if fmap1.shape != fmap2.shape:
-        raise ValueError("raft_corr: fmap1 and fmap2 differ in shape (%s and %s)" % (tuple(fmap1.shape), tuple(fmap2.shape)))
-    _raft_check_levels(fmap1.shape[3], int(num_levels))
-    _require_gpu(fmap1, fmap2)
+def _corr_pyramid(kind, fmap1, fmap2, num_levels):
+    num_levels = int(num_levels)
+    kind.check_features(fmap1, fmap2, num_levels)
+    return _CorrPyramid.apply(kind, _lib.contiguous(fmap1), _lib.contiguous(fmap2), num_levels)
 
 
-def _raft_check_disp(disp, radius):
-    if disp.dim() != 4:
-        raise ValueError("raft_corr: disp must be [B,1,H,W], got %s" % (tuple(disp.shape),))
-    if disp.shape[1] != 1:
-        raise ValueError("raft_corr: disp must have 1 channel, got %d" % disp.shape[1])
-    if radius < 0:
-        raise ValueError("raft_corr: radius must be >= 0, got %d" % radius)
+def _corr_lookup(kind, pyramid, motion, radius, size=None):
+    """Refusals in one order for both kinds: the arguments' shapes and values, the buffer's length, then device and dtype."""
+    radius = int(radius)
+    kind.check_motion(motion, radius)
+    B, _, H, W = motion.shape
+    if size is not None and tuple(size) != (H, W):
+        raise ValueError("%s: %s %s does not match size = %s" % (kind.prefix, kind.motion, tuple(motion.shape), tuple(size)))
+    kind.refuse_levels(H, W, 1)
+    L = kind.levels_of(pyramid, B * H * W, H, W)
+    _require_gpu(pyramid, motion)
+    return _CorrLookup.apply(kind, _lib.contiguous(pyramid), _lib.contiguous(motion), L, radius)
 
 
 def raft_corr_pyramid(fmap1, fmap2, num_levels):
@@ -2546,8 +2591,7 @@ def raft_corr_pyramid(fmap1, fmap2, num_levels):
     level 0 is the all-pairs row correlation sum_c fmap1[b,c,y,x] fmap2[b,c,y,x'] / sqrt(C), level i the average of adjacent
     pairs of level i-1 along x' (an odd tail is dropped).  Returns ONE 1-D fp32 buffer: level i is [B*H*W, W >> i] contiguous
     at offset B*H*W * (W + (W >> 1) + ... + (W >> (i-1))) -- `raft_corr_level_views` slices it.  Differentiable in both maps."""
-    _raft_check_features(fmap1, fmap2, num_levels)
-    return _RaftCorrPyramid.apply(_lib.contiguous(fmap1), _lib.contiguous(fmap2), int(num_levels))
+    return _corr_pyramid(_RAFT, fmap1, fmap2, num_levels)
 
 
 def raft_corr_lookup(pyramid, disp, radius):
@@ -2555,207 +2599,12 @@ def raft_corr_lookup(pyramid, disp, radius):
     channel i*(2r+1)+k = (1 - 2^-(i+1)) * the linear interpolation (zeros outside) of level i's row of the pixel at
     ((x - disp) / 2^i + (k - r)) * (W >> i) / (W - 1) - 0.5.  `pyramid` is the buffer of raft_corr_pyramid for the same B, H, W
     (the number of levels follows from its length).  Differentiable in the pyramid (every level) and in disp."""
-    _raft_check_disp(disp, int(radius))
-    _require_gpu(pyramid, disp)
-    B, _, H, W = disp.shape
-    if W < 2:
-        raise ValueError("raft_corr: W = %d, need W >= 2 (the lookup divides by W - 1)" % W)
-    L = _raft_levels_of(pyramid, B * H * W, W)
-    return _RaftCorrLookup.apply(_lib.contiguous(pyramid), _lib.contiguous(disp), L, int(radius))
+    return _corr_lookup(_RAFT, pyramid, disp, radius)
 
 
-class CorrBlock:
-    """CorrBlock of the reference (aggregation/utils/raft_corr.py:4-67; same arguments and attributes), for disparity: the
-    all-pairs row correlation of fmap1 and fmap2 [B,C,H,W] as a pyramid of `num_levels` levels (one launch, one buffer), and
-    `__call__(disp)` with disp [B,1,H,W]: the (2*radius+1)-tap bilinear window around x - disp on every level,
-    [B, num_levels*(2*radius+1), H, W].  `corr_pyramid[i]` is the [B*H*W, 1, 1, W >> i] view of level i.
-
-    Gradients reach disp and the two feature maps through `__call__` (the pyramid's per-level cotangent is never materialised:
-    ts_raft_corr_lookup_bwd folds it into one level-0 cotangent, ts_raft_corr_pyramid_bwd contracts that); the `corr_pyramid`
-    views themselves carry no gradient.  No host reads: build and lookup can be captured."""
-
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
-        num_levels, radius = int(num_levels), int(radius)
-        _raft_check_features(fmap1, fmap2, num_levels)
-        if radius < 0:
-            raise ValueError("raft_corr: radius must be >= 0, got %d" % radius)
-        self.num_levels = num_levels
-        self.radius = radius
-        f1, f2 = _lib.contiguous(fmap1), _lib.contiguous(fmap2)
-        with torch.no_grad():
-            self._pyramid = _RaftCorrPyramid.apply(f1, f2, num_levels)
-        self._shape = tuple(fmap1.shape)
-        # the feature maps are kept only where a backward can ask for them (the reference keeps the pyramid alone)
-        self._fmaps = (f1, f2) if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad) else None
-        B, _, H, W = self._shape
-        self.corr_pyramid = raft_corr_level_views(self._pyramid, B, H, W, num_levels)
-
-    def __call__(self, disp):
-        _raft_check_disp(disp, self.radius)
-        _require_gpu(disp)
-        B, _, H, W = self._shape
-        if (disp.shape[0], disp.shape[2], disp.shape[3]) != (B, H, W):
-            raise ValueError("raft_corr: disp %s does not match the feature maps %s" % (tuple(disp.shape), self._shape))
-        disp = _lib.contiguous(disp)
-        if self._fmaps is None:
-            return _RaftCorrLookup.apply(self._pyramid, disp, self.num_levels, self.radius)
-        return _RaftCorrBlockLookup.apply(self._fmaps[0], self._fmaps[1], self._pyramid, disp, self.num_levels, self.radius)
-
-
-# ------------------------------------------------------------------- FlowCorrBlock: the 2-D all-pairs correlation pyramid of RAFT
-_FLOW_MAX_LEVELS = 4            # csrc/flow_corr.hip pools levels 1..3 from an 8-row patch of the level-0 tile
-
-
-def _flow_level_sizes(H, W, num_levels):
-    return [(H >> i, W >> i) for i in range(num_levels)]
-
-
-def _flow_check_levels(H, W, num_levels):
-    if num_levels < 1:
-        raise ValueError("flow_corr: num_levels must be >= 1, got %d" % num_levels)
-    if num_levels > _FLOW_MAX_LEVELS:
-        raise ValueError("flow_corr: num_levels = %d, the HIP kernel pools at most %d levels" % (num_levels, _FLOW_MAX_LEVELS))
-    for i, (Hi, Wi) in enumerate(_flow_level_sizes(H, W, num_levels)):
-        if Hi < 2 or Wi < 2:
-            raise ValueError("flow_corr: level %d of a %d x %d map is %d x %d, need >= 2 x 2 (the lookup divides by H_i - 1 and "
-                             "W_i - 1)" % (i, H, W, Hi, Wi))
-
-
-def flow_corr_level_views(pyramid, B, H, W, num_levels):
-    """The levels of a pyramid buffer as the reference's `corr_pyramid` entries: [B*H*W, 1, H >> i, W >> i] views (no copies)."""
-    N, views, o = B * H * W, [], 0
-    for Hi, Wi in _flow_level_sizes(H, W, num_levels):
-        views.append(pyramid[o:o + N * Hi * Wi].view(N, 1, Hi, Wi))
-        o += N * Hi * Wi
-    return views
-
-
-def _flow_levels_of(pyramid, N, H, W):
-    """num_levels of a pyramid buffer of N source pixels over an H x W map (its length decides)."""
-    if pyramid.dim() != 1 or N <= 0 or pyramid.numel() % N:
-        raise ValueError("flow_corr_lookup: pyramid must be the 1-D buffer of flow_corr_pyramid for %d pixels, got %s" % (N, tuple(pyramid.shape)))
-    per, s = pyramid.numel() // N, 0
-    for L in range(1, _FLOW_MAX_LEVELS + 1):
-        Hi, Wi = H >> (L - 1), W >> (L - 1)
-        s += Hi * Wi
-        if s == per and Hi >= 2 and Wi >= 2:
-            return L
-    raise ValueError("flow_corr_lookup: a pyramid of %d floats per pixel is no pyramid of a %d x %d map" % (per, H, W))
-
-
-class _FlowCorrPyramid(torch.autograd.Function):
-    """ts_flow_corr_pyramid_fwd / ts_flow_corr_pyramid_bwd (the cotangent keeps its levels: folded while it is staged)."""
-
-    @staticmethod
-    def forward(ctx, fmap1, fmap2, num_levels):
-        B, C, H, W = fmap1.shape
-        pyr = torch.empty(B * H * W * sum(h * w for h, w in _flow_level_sizes(H, W, num_levels)), device=fmap1.device, dtype=torch.float32)
-        p = _lib.ptr
-        _lib.check(_lib.lib().ts_flow_corr_pyramid_fwd(p(fmap1), p(fmap2), p(pyr), B, C, H, W, num_levels, _stream()),
-                   "ts_flow_corr_pyramid_fwd")
-        ctx.save_for_backward(fmap1, fmap2)
-        ctx.num_levels = num_levels
-        return pyr
-
-    @staticmethod
-    def backward(ctx, g):
-        fmap1, fmap2 = ctx.saved_tensors
-        B, C, H, W = fmap1.shape
-        g1 = torch.empty_like(fmap1) if ctx.needs_input_grad[0] else None
-        g2 = torch.empty_like(fmap2) if ctx.needs_input_grad[1] else None
-        if g1 is None and g2 is None:
-            return None, None, None
-        g = _lib.contiguous(g)
-        p = _lib.ptr
-        _lib.check(_lib.lib().ts_flow_corr_pyramid_bwd(p(g), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, ctx.num_levels, _stream()),
-                   "ts_flow_corr_pyramid_bwd")
-        return g1, g2, None
-
-
-def _flow_lookup_fwd(pyramid, coords, num_levels, radius):
-    B, _, H, W = coords.shape
-    out = torch.empty((B, num_levels * (2 * radius + 1) ** 2, H, W), device=coords.device, dtype=torch.float32)
-    p = _lib.ptr
-    _lib.check(_lib.lib().ts_flow_corr_lookup_fwd(p(pyramid), p(coords), p(out), B, H, W, num_levels, radius, _stream()),
-               "ts_flow_corr_lookup_fwd")
-    return out
-
-
-class _FlowCorrLookup(torch.autograd.Function):
-    """ts_flow_corr_lookup_fwd / ts_flow_corr_lookup_bwd with fold = 0: the gradient with respect to a free pyramid, level by level."""
-
-    @staticmethod
-    def forward(ctx, pyramid, coords, num_levels, radius):
-        ctx.save_for_backward(pyramid, coords)
-        ctx.geom = (num_levels, radius)
-        return _flow_lookup_fwd(pyramid, coords, num_levels, radius)
-
-    @staticmethod
-    def backward(ctx, g):
-        pyramid, coords = ctx.saved_tensors
-        L, r = ctx.geom
-        B, _, H, W = coords.shape
-        gp = torch.empty_like(pyramid) if ctx.needs_input_grad[0] else None
-        gc = torch.empty_like(coords) if ctx.needs_input_grad[1] else None
-        if gp is None and gc is None:
-            return None, None, None, None
-        g = _lib.contiguous(g)
-        p = _lib.ptr
-        _lib.check(_lib.lib().ts_flow_corr_lookup_bwd(p(pyramid), p(coords), p(g), p(gc), p(gp), B, H, W, L, r, 0, _stream()),
-                   "ts_flow_corr_lookup_bwd")
-        return gp, gc, None, None
-
-
-class _FlowCorrBlockLookup(torch.autograd.Function):
-    """The lookup of a FlowCorrBlock, differentiable in the FEATURES the pyramid was built from: backward is ts_flow_corr_lookup_bwd
-    with fold = 1 (one [B*H*W, H*W] cotangent of level 0, written once) and ts_flow_corr_pyramid_bwd on it -- the per-level
-    cotangent of the pyramid is never materialised."""
-
-    @staticmethod
-    def forward(ctx, fmap1, fmap2, pyramid, coords, num_levels, radius):
-        ctx.save_for_backward(fmap1, fmap2, pyramid, coords)
-        ctx.geom = (num_levels, radius)
-        return _flow_lookup_fwd(pyramid, coords, num_levels, radius)
-
-    @staticmethod
-    def backward(ctx, g):
-        fmap1, fmap2, pyramid, coords = ctx.saved_tensors
-        L, r = ctx.geom
-        B, C, H, W = fmap1.shape
-        need1, need2, _, needc = ctx.needs_input_grad[:4]
-        if not (need1 or need2 or needc):
-            return (None,) * 6
-        g = _lib.contiguous(g)
-        p = _lib.ptr
-        feats = need1 or need2
-        G = torch.empty(B * (H * W) ** 2, device=g.device, dtype=torch.float32) if feats else None
-        gc = torch.empty_like(coords) if needc else None
-        _lib.check(_lib.lib().ts_flow_corr_lookup_bwd(p(pyramid), p(coords), p(g), p(gc), p(G), B, H, W, L, r, 1, _stream()),
-                   "ts_flow_corr_lookup_bwd")
-        g1 = torch.empty_like(fmap1) if need1 else None
-        g2 = torch.empty_like(fmap2) if need2 else None
-        if feats:
-            _lib.check(_lib.lib().ts_flow_corr_pyramid_bwd(p(G), p(fmap1), p(fmap2), p(g1), p(g2), B, C, H, W, 1, _stream()),
-                       "ts_flow_corr_pyramid_bwd")
-        return g1, g2, None, gc, None, None
-
-
-def _flow_check_features(fmap1, fmap2, num_levels):
-    if fmap1.dim() != 4 or fmap2.dim() != 4:
-        raise ValueError("flow_corr: fmap1 and fmap2 must be [B,C,H,W], got %s and %s" % (tuple(fmap1.shape), tuple(fmap2.shape)))
-    if fmap1.shape != fmap2.shape:
-        raise ValueError("flow_corr: fmap1 and fmap2 differ in shape (%s and %s)" % (tuple(fmap1.shape), tuple(fmap2.shape)))
-    _flow_check_levels(fmap1.shape[2], fmap1.shape[3], int(num_levels))
-    _require_gpu(fmap1, fmap2)
-
-
-def _flow_check_coords(coords, radius, size=None):
-    if coords.dim() != 4 or coords.shape[1] != 2:
-        raise ValueError("flow_corr: coords must be [B,2,H,W], got %s" % (tuple(coords.shape),))
-    if size is not None and (coords.shape[0], coords.shape[2], coords.shape[3]) != tuple(size):
-        raise ValueError("flow_corr: coords %s does not match the feature maps' (B, H, W) = %s" % (tuple(coords.shape), tuple(size)))
-    if radius < 0:
-        raise ValueError("flow_corr: radius must be >= 0, got %d" % radius)
+def raft_corr_level_views(pyramid, B, H, W, num_levels):
+    """The levels of a pyramid buffer as the reference's `corr_pyramid` entries: [B*H*W, 1, 1, W >> i] views (no copies)."""
+    return _RAFT.level_views(pyramid, B, H, W, num_levels)
 
 
 def flow_corr_pyramid(fmap1, fmap2, num_levels):
@@ -2764,8 +2613,7 @@ def flow_corr_pyramid(fmap1, fmap2, num_levels):
     (the reference's full Gram matrices), level i the 2x2 average of level i-1 over m (an odd last row or column is dropped).
     Returns ONE 1-D fp32 buffer: level i is [B*H*W, (H >> i)*(W >> i)] contiguous, stored after the levels before it --
     `flow_corr_level_views` slices it.  Differentiable in both maps."""
-    _flow_check_features(fmap1, fmap2, num_levels)
-    return _FlowCorrPyramid.apply(_lib.contiguous(fmap1), _lib.contiguous(fmap2), int(num_levels))
+    return _corr_pyramid(_FLOW, fmap1, fmap2, num_levels)
 
 
 def flow_corr_lookup(pyramid, coords, radius, size=None):
@@ -2774,50 +2622,68 @@ def flow_corr_lookup(pyramid, coords, radius, size=None):
     row at (coords_x / 2^i + a - r, coords_y / 2^i + b - r): the first window index moves x, as the reference's does.  `pyramid`
     is the buffer of flow_corr_pyramid for the same B, H, W (`size` = (H, W), by default coords' own; the number of levels
     follows from the buffer's length).  Differentiable in the pyramid (every level) and in coords."""
-    _flow_check_coords(coords, int(radius))
-    B, _, H, W = coords.shape
-    if size is not None and tuple(size) != (H, W):
-        raise ValueError("flow_corr: coords %s does not match size = %s" % (tuple(coords.shape), tuple(size)))
-    L = _flow_levels_of(pyramid, B * H * W, H, W)
-    _require_gpu(pyramid, coords)
-    return _FlowCorrLookup.apply(_lib.contiguous(pyramid), _lib.contiguous(coords), L, int(radius))
+    return _corr_lookup(_FLOW, pyramid, coords, radius, size)
 
 
-class FlowCorrBlock:
-    """FlowCorrBlock of the reference (aggregation/utils/raft_corr.py:71-144; same arguments and attributes), for optical flow:
-    the all-pairs cost between every pixel of fmap1 and every pixel of fmap2 [B,C,H,W] as a pyramid of `num_levels` levels (one
-    launch, one buffer), and `__call__(coords)` with coords [B,2,H,W] (x, y): the (2*radius+1)^2 bilinear window around the
-    target coordinate on every level, [B, num_levels*(2*radius+1)^2, H, W].  `corr_pyramid[i]` is the [B*H*W, 1, H >> i, W >> i]
-    view of level i.
+def flow_corr_level_views(pyramid, B, H, W, num_levels):
+    """The levels of a pyramid buffer as the reference's `corr_pyramid` entries: [B*H*W, 1, H >> i, W >> i] views (no copies)."""
+    return _FLOW.level_views(pyramid, B, H, W, num_levels)
 
-    Gradients reach coords and the two feature maps through `__call__` (the pyramid's per-level cotangent is never materialised:
-    ts_flow_corr_lookup_bwd folds it into one level-0 cotangent, ts_flow_corr_pyramid_bwd contracts that); the `corr_pyramid`
-    views themselves carry no gradient.  No host reads: build and lookup can be captured."""
+
+class _CorrBlockBase:
+    """What CorrBlock and FlowCorrBlock share: the pyramid is built in one launch into one buffer, of which `corr_pyramid[i]` is
+    the view of level i, and a call looks the window up on every level in one launch.
+
+    Gradients reach the call's argument and the two feature maps through the call (the pyramid's per-level cotangent is never
+    materialised: ts_*_corr_lookup_bwd folds it into one level-0 cotangent, ts_*_corr_pyramid_bwd contracts that); the
+    `corr_pyramid` views themselves carry no gradient.  No host reads: build and lookup can be captured."""
+
+    _kind = None
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        kind = self._kind
         num_levels, radius = int(num_levels), int(radius)
         if radius < 0:
-            raise ValueError("flow_corr: radius must be >= 0, got %d" % radius)
-        _flow_check_features(fmap1, fmap2, num_levels)
+            raise ValueError("%s: radius must be >= 0, got %d" % (kind.prefix, radius))
+        kind.check_features(fmap1, fmap2, num_levels)
         self.num_levels = num_levels
         self.radius = radius
         f1, f2 = _lib.contiguous(fmap1), _lib.contiguous(fmap2)
         with torch.no_grad():
-            self._pyramid = _FlowCorrPyramid.apply(f1, f2, num_levels)
+            self._pyramid = _CorrPyramid.apply(kind, f1, f2, num_levels)
         self._shape = tuple(fmap1.shape)
         # the feature maps are kept only where a backward can ask for them (the reference keeps the pyramid alone)
         self._fmaps = (f1, f2) if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad) else None
         B, _, H, W = self._shape
-        self.corr_pyramid = flow_corr_level_views(self._pyramid, B, H, W, num_levels)
+        self.corr_pyramid = kind.level_views(self._pyramid, B, H, W, num_levels)
 
-    def __call__(self, coords):
+    def __call__(self, motion):
+        kind = self._kind
         B, _, H, W = self._shape
-        _flow_check_coords(coords, self.radius, (B, H, W))
-        _require_gpu(coords)
-        coords = _lib.contiguous(coords)
+        kind.check_motion(motion, self.radius, (B, H, W))
+        _require_gpu(motion)
+        motion = _lib.contiguous(motion)
         if self._fmaps is None:
-            return _FlowCorrLookup.apply(self._pyramid, coords, self.num_levels, self.radius)
-        return _FlowCorrBlockLookup.apply(self._fmaps[0], self._fmaps[1], self._pyramid, coords, self.num_levels, self.radius)
+            return _CorrLookup.apply(kind, self._pyramid, motion, self.num_levels, self.radius)
+        return _CorrBlockLookup.apply(kind, self._fmaps[0], self._fmaps[1], self._pyramid, motion, self.num_levels, self.radius)
+
+
+class CorrBlock(_CorrBlockBase):
+    """CorrBlock of the reference (aggregation/utils/raft_corr.py:4-67; same arguments and attributes), for disparity: the
+    all-pairs row correlation of fmap1 and fmap2 [B,C,H,W] as a pyramid of `num_levels` levels, and `__call__(disp)` with
+    disp [B,1,H,W]: the (2*radius+1)-tap bilinear window around x - disp on every level, [B, num_levels*(2*radius+1), H, W].
+    `corr_pyramid[i]` is the [B*H*W, 1, 1, W >> i] view of level i."""
+
+    _kind = _RAFT
+
+
+class FlowCorrBlock(_CorrBlockBase):
+    """FlowCorrBlock of the reference (aggregation/utils/raft_corr.py:71-144; same arguments and attributes), for optical flow:
+    the all-pairs cost between every pixel of fmap1 and every pixel of fmap2 [B,C,H,W] as a pyramid of `num_levels` levels, and
+    `__call__(coords)` with coords [B,2,H,W] (x, y): the (2*radius+1)^2 bilinear window around the target coordinate on every
+    level, [B, num_levels*(2*radius+1)^2, H, W].  `corr_pyramid[i]` is the [B*H*W, 1, H >> i, W >> i] view of level i."""
+
+    _kind = _FLOW
 
     @staticmethod
     def init_flow(size, device, flow_init=None):

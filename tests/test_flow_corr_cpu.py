@@ -138,14 +138,14 @@ def test_ops_refuse_cpu_tensors_and_bad_arguments():
 def test_pyramid_buffer_length_decides_the_level_count():
     from temporalstereo_amd import functional as Fn
     N, H, W = 2 * 8 * 16, 8, 16
-    assert Fn._flow_levels_of(torch.zeros(N * 128), N, H, W) == 1
-    assert Fn._flow_levels_of(torch.zeros(N * (128 + 32 + 8)), N, H, W) == 3
+    assert Fn._FLOW.levels_of(torch.zeros(N * 128), N, H, W) == 1
+    assert Fn._FLOW.levels_of(torch.zeros(N * (128 + 32 + 8)), N, H, W) == 3
     with pytest.raises(ValueError, match="no pyramid of a 8 x 16 map"):
-        Fn._flow_levels_of(torch.zeros(N * (128 + 32 + 8 + 2)), N, H, W)       # a fourth level would be 1 x 2
+        Fn._FLOW.levels_of(torch.zeros(N * (128 + 32 + 8 + 2)), N, H, W)       # a fourth level would be 1 x 2
     with pytest.raises(ValueError, match="no pyramid of a 8 x 16 map"):
-        Fn._flow_levels_of(torch.zeros(N * 127), N, H, W)
+        Fn._FLOW.levels_of(torch.zeros(N * 127), N, H, W)
     with pytest.raises(ValueError, match="1-D buffer"):
-        Fn._flow_levels_of(torch.zeros(N * 128 + 1), N, H, W)
+        Fn._FLOW.levels_of(torch.zeros(N * 128 + 1), N, H, W)
     views = Fn.flow_corr_level_views(torch.zeros(N * (128 + 32 + 8)), 2, H, W, 3)
     assert [tuple(v.shape) for v in views] == [(N, 1, 8, 16), (N, 1, 4, 8), (N, 1, 2, 4)]
 

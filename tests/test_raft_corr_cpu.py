@@ -94,6 +94,22 @@ def test_ops_refuse_cpu_tensors_and_bad_arguments():
         ts.raft_corr_pyramid(f, torch.zeros(1, 4, 2, 15), 2)
 
 
+def test_pyramid_buffer_length_decides_the_level_count():
+    from temporalstereo_amd import functional as Fn
+    N, H, W = 2 * 2 * 16, 2, 16
+    assert Fn._RAFT.levels_of(torch.zeros(N * 16), N, H, W) == 1
+    assert Fn._RAFT.levels_of(torch.zeros(N * (16 + 8 + 4)), N, H, W) == 3
+    assert Fn._RAFT.levels_of(torch.zeros(N * (16 + 8 + 4 + 2 + 1)), N, H, W) == 5      # a sixth level would be empty and adds nothing
+    with pytest.raises(ValueError, match="no pyramid of width 16"):
+        Fn._RAFT.levels_of(torch.zeros(N * 32), N, H, W)
+    with pytest.raises(ValueError, match="no pyramid of width 16"):
+        Fn._RAFT.levels_of(torch.zeros(N * 15), N, H, W)
+    with pytest.raises(ValueError, match="1-D buffer"):
+        Fn._RAFT.levels_of(torch.zeros(N * 16 + 1), N, H, W)
+    views = Fn.raft_corr_level_views(torch.zeros(N * (16 + 8 + 4)), 2, H, W, 3)
+    assert [tuple(v.shape) for v in views] == [(N, 1, 1, 16), (N, 1, 1, 8), (N, 1, 1, 4)]
+
+
 def test_entries_refuse_bad_sizes_without_gpu():
     """the library's own checks (before any launch): the statuses and messages of include/ts_hip.h"""
     from temporalstereo_amd import _lib
