@@ -666,6 +666,33 @@ int ts_conv_gru_gate_bwd_b(const float* d_rh, const float* r, const float* h, fl
 int ts_conv_gru_grad_sum(const float* dcat_g, const float* dcat_q, float* dh, float* dx, int B, int Ch, int Cx, long long N,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FeatureDecoder: the layers of the backbone's three-level decoder, backbone/TemporalStereo.py:78-90,125-138, fp32 throughout (ABI 21).
+ *   y = act(conv3x3(cat([resize(up), skip], 1)) * scale + shift)      stride 1, padding 1, on the f32-input MFMA: an fmaf chain
+ * ts_decoder_conv_fwd       up [B,Cu,h,w] is read THROUGH the align-corners bilinear resize to (H,W) (the coordinates of
+ *                           ts_resize_bilinear_fwd), skip [B,Cs,H,W] is read in place; neither the resized map nor the concatenation is
+ *                           written.  The zero padding applies to the resized map.  Channel order [up | skip].  Cu = 0 (up, h, w
+ *                           ignored) is the plain convolution; Cs > 0 always (skip sets the output plane).  y [B,Cout,H,W] OVERWRITTEN.
+ *                           act 0 none | 1 SiLU; scale / shift [Cout] may be NULL (1 / 0).  up, skip and y have batch / channel
+ *                           strides in elements, their planes dense.
+ * ts_decoder_weight_layout  w [Cout][Cin][3][3] (the framework's, contiguous), Cin = Cu + Cs -> w_l, ts_decoder_weight_bytes(Cin, Cout)
+ *                           bytes (0 outside the envelope), 16-byte aligned: the kernel's chunked order, one launch.
+ * ts_resize_bilinear_bwd    the adjoint of the align-corners bilinear resize (h,w) -> (H,W) as a gather: dx [B,C,h,w] OVERWRITTEN from
+ *                           dy [B,C,H,W], both with batch / channel strides.  Each coarse pixel sums, in a fixed order, the fine pixels
+ *                           whose two source indices include it.  No atomics: bit-reproducible.
+ * The other gradients run on ts_conv3d_hw_bwd_data (D = 1, over the concatenation's channels), ts_conv3d_hw_bwd_weight (per source and
+ * per slice of <= 64 output channels), ts_bn_* and ts_channel_sum_fwd.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive,
+ * an unknown activation, overlapping strides), then Cu + Cs > 512, Cout > 512, an axis >= 2^20, a grid that does not fit
+ * (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL; scale, shift, and up when Cu = 0 may be NULL).
+ * ---------------------------------------------------------------------------------------- */
+size_t ts_decoder_weight_bytes(int Cin, int Cout);
+int ts_decoder_weight_layout(const float* w, float* w_l, int Cin, int Cout, void* stream);
+int ts_decoder_conv_fwd(const float* up, const float* skip, const float* w_l, const float* scale, const float* shift, float* y, int B,
+                        int Cu, int Cs, int Cout, int h, int w, int H, int W, int act, long long up_bstride, long long up_cstride,
+                        long long skip_bstride, long long skip_cstride, long long y_bstride, long long y_cstride, void* stream);
+int ts_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int h, int w, int H, int W, long long dy_bstride,
+                           long long dy_cstride, long long dx_bstride, long long dx_cstride, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

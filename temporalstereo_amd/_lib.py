@@ -188,6 +188,10 @@ SIGNATURES = {
     "ts_conv_gru_gate_bwd_a": (c_int, [c_f32p] * 7 + [c_int] * 2 + [ctypes.c_longlong] * 5 + [c_ptr]),
     "ts_conv_gru_gate_bwd_b": (c_int, [c_f32p] * 5 + [c_int] * 2 + [ctypes.c_longlong] * 7 + [c_ptr]),
     "ts_conv_gru_grad_sum": (c_int, [c_f32p] * 4 + [c_int] * 3 + [ctypes.c_longlong, c_ptr]),
+    "ts_decoder_weight_bytes": (c_size, [c_int] * 2),
+    "ts_decoder_weight_layout": (c_int, [c_f32p] * 2 + [c_int] * 2 + [c_ptr]),
+    "ts_decoder_conv_fwd": (c_int, [c_f32p] * 6 + [c_int] * 9 + [ctypes.c_longlong] * 6 + [c_ptr]),
+    "ts_resize_bilinear_bwd": (c_int, [c_f32p] * 2 + [c_int] * 6 + [ctypes.c_longlong] * 4 + [c_ptr]),
     "ts_reproject_memory_workspace_bytes": (c_size, [c_int] * 5),
     "ts_reproject_memory_fwd": (c_int, [c_f32p, ctypes.c_longlong, c_int, c_int, c_f32p, c_f32p, c_int, c_f32p, c_int, c_int,
                                         c_f32p, c_int, c_f32p, c_f32p, c_f32p, c_float, c_float, c_f32p, c_f32p, c_f32p,

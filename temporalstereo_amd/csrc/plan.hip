@@ -116,6 +116,7 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_deconv2d_k4s2_unet_upsample_fwd),
     TS_PLAN_OP(ts_conv_gru_weight_layout),  TS_PLAN_OP(ts_conv_gru_gates_fwd),      TS_PLAN_OP(ts_conv_gru_out_fwd),
     TS_PLAN_OP(ts_conv_gru_gate_bwd_a),     TS_PLAN_OP(ts_conv_gru_gate_bwd_b),     TS_PLAN_OP(ts_conv_gru_grad_sum),
+    TS_PLAN_OP(ts_decoder_weight_layout),   TS_PLAN_OP(ts_decoder_conv_fwd),        TS_PLAN_OP(ts_resize_bilinear_bwd),
 };
 
 struct Call {

@@ -2836,3 +2836,261 @@ def conv_gru(last_hidden, x, wz, bz, wr, br, wq, bq, return_gates=False):
     if not torch.is_grad_enabled():           # nothing can ask for a gradient: r and q are neither allocated nor stored
         args = tuple(a.detach() for a in args)
     return _ConvGRU.apply(*args, bool(return_gates))
+
+
+# ---- FeatureDecoder (reference: backbone/TemporalStereo.py:78-90,125-138) ---------------------------------------------------------------
+DECODER_MAX_CHANNELS = 512        # the kernel path's envelope: Cu + Cs and Cout (csrc/feature_decoder.hip)
+_WGRAD_MAX_COUT = 64              # ts_conv3d_hw_bwd_weight holds at most 64 output channels
+
+
+def decoder_conv_supported(in_channels, out_channels):
+    return 1 <= in_channels <= DECODER_MAX_CHANNELS and 1 <= out_channels <= DECODER_MAX_CHANNELS
+
+
+def _decoder_weight_make(weight, out=None):
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    if out is None:
+        nbytes = _q("ts_decoder_weight_bytes", Cin, Cout)
+        if not nbytes:
+            raise RuntimeError("decoder_conv: %d input / %d output channels are outside the kernel path (1..%d each)"
+                               % (Cin, Cout, DECODER_MAX_CHANNELS))
+        out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
+    _lib.check(_lib.lib().ts_decoder_weight_layout(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, _stream()), "ts_decoder_weight_layout")
+    return out
+
+
+def _decoder_weight(weight):
+    """The kernel's chunked order of a [Cout, Cin, 3, 3] weight (ts_decoder_weight_layout); inside a `WeightLayouts` context a leaf is laid
+    out once per step and refreshed with the others."""
+    if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
+        return _LAYOUTS.get_custom(weight, "decoder", _decoder_weight_make)
+    return _decoder_weight_make(_lib.contiguous(weight.detach()))
+
+
+_DECODER_FOLDS = {}
+
+
+def _decoder_fold(gamma, beta, mean, var, bias, eps, cout):
+    """(scale, shift) of an eval-mode BatchNorm folded behind the convolution, from the CURRENT statistics: one ts_bn_fold_many launch
+    per call (the one-entry table is uploaded once per layer); inside a `BNFolds` context that context's entry.
+    Outside such a context the layer's scale / shift buffers are ONE pair per layer, kept here with its tensors (at most 256 layers, then
+    the table starts over) and rewritten by every call: calls of the same layer must be ordered on one stream, as the calls of a module
+    are.  Two streams that run the same layer concurrently each need their own `BNFolds` context."""
+    if _FOLDS is not None:
+        fold = _FOLDS.get(gamma, beta, mean, var, bias, eps, cout)
+        if fold is not None:
+            return fold
+    key = tuple(t.data_ptr() if t is not None else 0 for t in (gamma, beta, mean, var, bias)) + (int(cout),)
+    e = _DECODER_FOLDS.get(key)
+    if e is None:
+        if len(_DECODER_FOLDS) >= 256:
+            _DECODER_FOLDS.clear()
+        pad = _cpad(cout)
+        entry = [gamma, beta, mean, var, bias, torch.empty(pad, device=mean.device), torch.empty(pad, device=mean.device), int(cout), pad]
+        e = _DECODER_FOLDS[key] = (entry, BNFolds()._upload([entry]))
+    _lib.check(_lib.lib().ts_bn_fold_many(_lib.ptr(e[1]), 1, float(eps), _stream()), "ts_bn_fold_many")
+    return e[0][5], e[0][6]
+
+
+def _decoder_launch(up, skip, w_l, scale, shift, y, act):
+    B, Cout, H, W = y.shape
+    Cu, h, w = (up.shape[1], up.shape[2], up.shape[3]) if up is not None else (0, 0, 0)
+    Cs = skip.shape[1]
+    ub, uc = (up.stride(0), up.stride(1)) if up is not None else (0, 0)
+    sb, sc = skip.stride(0), skip.stride(1)
+    rc = _lib.lib().ts_decoder_conv_fwd(_lib.ptr(up), _lib.ptr(skip), _lib.ptr(w_l), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, Cu, Cs,
+                                        Cout, h, w, H, W, int(act), ub, uc, sb, sc, y.stride(0), y.stride(1), _stream())
+    _lib.check(rc, "ts_decoder_conv_fwd")
+
+
+def _decoder_check(up, skip, weight, bias):
+    if skip is None:
+        raise ValueError("decoder_conv: skip [B,Cs,H,W] is required (it sets the output plane)")
+    for name, t in (("up", up), ("skip", skip)):
+        if t is not None and t.dim() != 4:
+            raise ValueError("decoder_conv: %s must be [B,C,H,W], got %s" % (name, tuple(t.shape)))
+    if up is not None and up.shape[0] != skip.shape[0]:
+        raise ValueError("decoder_conv: up has batch %d, skip %d" % (up.shape[0], skip.shape[0]))
+    Cu = up.shape[1] if up is not None else 0
+    Cs = skip.shape[1]
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (Cu + Cs, 3, 3):
+        raise ValueError("decoder_conv: weight must be [Cout, %d, 3, 3], got %s" % (Cu + Cs, tuple(weight.shape)))
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError("decoder_conv: bias must be [%d], got %s" % (weight.shape[0], tuple(bias.shape)))
+    if min(skip.shape) < 1 or (up is not None and min(up.shape) < 1):
+        raise ValueError("decoder_conv: empty input")
+
+
+class _DecoderConv(torch.autograd.Function):
+    """act(BatchNorm(conv3x3(cat([resize(up), skip], 1)) + bias)) as ONE autograd node: ts_decoder_conv_fwd reads `up` through the
+    align-corners resize and `skip` in place (no resized map, no concatenation), then ts_bn_train_fwd / ts_bn_apply_act_fwd over the raw
+    convolution output; with may_fold the eval statistics go into the convolution's epilogue and nothing is kept.
+    backward: ts_bn_train_bwd (or the eval pair) -> ts_conv3d_hw_bwd_data over the concatenation's channels, whose [:, Cu:] slice is
+    grad_skip as a view and whose [:, :Cu] slice goes through ts_resize_bilinear_bwd -> ts_conv3d_hw_bwd_weight per source and per slice
+    of <= 64 output channels (the resized map recomputed by ts_resize_bilinear_fwd) -> ts_channel_sum_fwd.  No atomics."""
+
+    @staticmethod
+    def forward(ctx, up, skip, weight, bias, gamma, beta, running_mean, running_var, eps, momentum, act, training, counter, may_fold,
+                has_bn):
+        _require_gpu(*[t for t in (up, skip, weight, bias) if t is not None])
+        _decoder_check(up, skip, weight, bias)
+        up = _plane_view(up) if up is not None else None
+        skip = _plane_view(skip)
+        B, _, H, W = skip.shape
+        Cout = weight.shape[0]
+        w_l = _decoder_weight(weight)
+        y = torch.empty((B, Cout, H, W), device=skip.device, dtype=torch.float32)
+        bias_d = _lib.contiguous(bias.detach()) if bias is not None else None
+        needs = any(ctx.needs_input_grad[:6])
+        if not has_bn:
+            if act and needs:
+                raise RuntimeError("decoder_conv: an activation without BatchNorm has no backward on the kernel path")
+            _decoder_launch(up, skip, w_l, None, bias_d, y, act)
+            if needs:
+                ctx.save_for_backward(up, skip, weight)
+                ctx.meta = (False, 0.0, 0, False, bias is not None)
+            return y
+        if may_fold and not training:
+            scale, shift = _decoder_fold(gamma, beta, running_mean, running_var, bias_d, eps, Cout)
+            _decoder_launch(up, skip, w_l, scale, shift, y, act)
+            return y
+        _decoder_launch(up, skip, w_l, None, bias_d, y, 0)
+        N = H * W
+        L = _lib.lib()
+        out = torch.empty_like(y)
+        if training:
+            mean = torch.empty(Cout, device=y.device, dtype=torch.float32)
+            var = torch.empty_like(mean)
+            ws = torch.empty(_q("ts_bn_workspace_bytes", B, Cout, N), device=y.device, dtype=torch.uint8)
+            _lib.check(L.ts_bn_train_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                         float(momentum), _lib.ptr(counter), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out), _lib.ptr(ws),
+                                         B, Cout, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act), _stream()),
+                       "ts_bn_train_fwd")
+        else:
+            mean, var = running_mean, running_var
+            _lib.check(L.ts_bn_apply_act_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out),
+                                             B, Cout, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act),
+                                             _stream()), "ts_bn_apply_act_fwd")
+        if needs:
+            ctx.save_for_backward(up, skip, weight, y, mean, var, gamma, beta)
+            ctx.meta = (True, float(eps), int(act), bool(training), bias is not None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        has_bn, eps, act, training, has_bias = ctx.meta
+        if has_bn:
+            up, skip, weight, y, mean, var, gamma, beta = ctx.saved_tensors
+        else:
+            up, skip, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        L, st = _lib.lib(), _stream()
+        g = _lib.contiguous(g)
+        B, Cout, H, W = g.shape
+        N = H * W
+        dev = g.device
+        ggamma = gbeta = None
+        if has_bn:
+            s1 = torch.empty(Cout, device=dev, dtype=torch.float32)
+            s2 = torch.empty_like(s1)
+            ws = torch.empty(_q("ts_bn_workspace_bytes", B, Cout, N), device=dev, dtype=torch.uint8)
+            dy = torch.empty_like(y)
+            if training:
+                _lib.check(L.ts_bn_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                             _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy), _lib.ptr(ws), B, Cout, N, y.stride(0), y.stride(1),
+                                             g.stride(0), g.stride(1), eps, act, float(B * N), st), "ts_bn_train_bwd")
+            else:
+                _lib.check(L.ts_bn_act_bwd_reduce(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                                  _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ws), B, Cout, N, y.stride(0), y.stride(1), g.stride(0),
+                                                  g.stride(1), eps, act, st), "ts_bn_act_bwd_reduce")
+                _lib.check(L.ts_bn_act_bwd_apply(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                                 _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy), B, Cout, N, y.stride(0), y.stride(1), g.stride(0),
+                                                 g.stride(1), eps, act, 0, float(B * N), st), "ts_bn_act_bwd_apply")
+            ggamma, gbeta = (s2 if need[4] else None), (s1 if need[5] else None)
+        else:
+            dy = g
+        Cu = up.shape[1] if up is not None else 0
+        Cs = skip.shape[1]
+        Cin = Cu + Cs
+        gup = gskip = dw = gbias = None
+        if (need[0] and Cu) or need[1]:
+            dcat = torch.empty((B, Cin, H, W), device=dev, dtype=torch.float32)
+            w_b = _layout(weight, 0, 1, flip=True)                   # [co][t][ci], taps flipped
+            _lib.check(L.ts_conv3d_hw_bwd_data(_lib.ptr(dy), _lib.ptr(w_b), _lib.ptr(dcat), B, Cin, Cout, 1, H, W, 1, 1, 0, Cout * N, N,
+                                               Cin * N, N, st), "ts_conv3d_hw_bwd_data")
+            if need[1]:
+                gskip = dcat[:, Cu:]
+            if need[0] and Cu:
+                gup = torch.empty(up.shape, device=dev, dtype=torch.float32)
+                _lib.check(L.ts_resize_bilinear_bwd(_lib.ptr(dcat), _lib.ptr(gup), B, Cu, up.shape[2], up.shape[3], H, W, Cin * N, N,
+                                                    gup.stride(0), gup.stride(1), st), "ts_resize_bilinear_bwd")
+        if need[2]:
+            sources = []
+            if Cu:
+                up_d = _lib.contiguous(up)                  # ts_resize_bilinear_fwd reads a dense map: a sliced `up` is copied HERE (the forward reads it in place)
+                resized = torch.empty((B, Cu, H, W), device=dev, dtype=torch.float32)          # recomputed, never kept from the forward
+                _lib.check(L.ts_resize_bilinear_fwd(_lib.ptr(up_d), _lib.ptr(resized), B, Cu, up.shape[2], up.shape[3], H, W, 1.0, Cu * N, st),
+                           "ts_resize_bilinear_fwd")
+                sources.append((resized, Cu))
+            sources.append((skip, Cs))
+            rows = []
+            for co in range(0, Cout, _WGRAD_MAX_COUT):
+                n = min(_WGRAD_MAX_COUT, Cout - co)
+                dy_s = dy[:, co:co + n]
+                parts = []
+                for src, cin in sources:
+                    part = torch.empty((n, cin, 3, 3), device=dev, dtype=torch.float32)
+                    wsp, nws = _wgrad_workspace(cin, n, 9, dev)
+                    rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(src), _lib.ptr(dy_s), _lib.ptr(part), B, cin, n, 1, H, W, 1, 1, src.stride(0),
+                                                   src.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(wsp), nws, st)
+                    _lib.check(rc, "ts_conv3d_hw_bwd_weight")
+                    parts.append(part)
+                rows.append(parts[0] if len(parts) == 1 else torch.cat(parts, 1))
+            dw = rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+        if has_bias and need[3]:
+            gbias = _channel_sum(dy)
+        return gup, gskip, dw, gbias, ggamma, gbeta, None, None, None, None, None, None, None, None, None
+
+
+def bn_exchanges(bn):
+    """True when `bn` in its present mode needs other ranks' statistics: a train-mode SyncBatchNorm (anything with a `process_group`)
+    whose group spans more than one rank -- the test conv_bn_act applies before it exchanges."""
+    if bn is None or not bn.training or "process_group" not in bn.__dict__:
+        return False
+    import torch.distributed as dist
+    return bool(dist.is_available() and dist.is_initialized() and dist.get_world_size(bn.__dict__["process_group"]) > 1)
+
+
+def decoder_conv(up, skip, weight, bias=None, bn=None, activation=None):
+    """One layer of the backbone's decoder on the HIP kernels: activation(bn(conv3x3(cat([resize(up), skip], 1)) + bias)), the resize
+    bilinear with align_corners=True to skip's plane, the convolution with stride 1 and padding 1 -- without writing the resized map or
+    the concatenation.  up=None is the plain convolution of `skip`; skip is required.  bn: a BatchNorm (train mode: THIS rank's batch
+    statistics, the running ones updated; eval mode: the running ones, folded into the convolution's epilogue when nothing needs a
+    gradient) or None.  A SyncBatchNorm is accepted in eval mode and on a single rank; in train mode over more than one rank it is
+    refused (RuntimeError): the exchange lives in conv_bn_act, which FeatureDecoder._reference_forward goes through.
+    activation: None | 'SiLU'.  fp32 GPU tensors, Cu + Cs <= 512, Cout <= 512; gradients for up, skip, weight, bias and bn's affine pair."""
+    if activation not in (None, "SiLU"):
+        raise ValueError("decoder_conv: activation must be None or 'SiLU'")
+    act = BN_ACT[activation]
+    if bn is None:
+        gamma = beta = rmean = rvar = counter = None
+        eps, momentum, training = 0.0, 0.0, False
+    else:
+        if not isinstance(bn, torch.nn.modules.batchnorm._BatchNorm) or not bn.affine or not bn.track_running_stats:
+            raise ValueError("decoder_conv: bn must be a BatchNorm with affine parameters and running statistics")
+        if bn.momentum is None:
+            raise ValueError("decoder_conv: a BatchNorm with momentum=None (cumulative average) is not on the kernel path")
+        if bn_exchanges(bn):
+            raise RuntimeError("decoder_conv: a train-mode SyncBatchNorm over %d ranks needs the statistics exchange of conv_bn_act; "
+                               "this node computes per-rank statistics (FeatureDecoder routes such a module to _reference_forward)"
+                               % torch.distributed.get_world_size(bn.__dict__["process_group"]))
+        gamma, beta, rmean, rvar = bn.weight, bn.bias, bn.running_mean, bn.running_var
+        training = bn.training
+        eps, momentum = bn.eps, bn.momentum
+        counter = bn.num_batches_tracked if training else None
+    tensors = (up, skip, weight, bias, gamma, beta)
+    grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+    if not grad:
+        tensors = tuple(t.detach() if t is not None else None for t in tensors)
+    return _DecoderConv.apply(*tensors, rmean, rvar, eps, momentum, act, training, counter, not grad, bn is not None)

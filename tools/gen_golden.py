@@ -1945,6 +1945,123 @@ def conv_gru_cases(M):
     print("\n".join(lines))
 
 
+def reference_decoder():
+    """The reference's OWN decoder (architecture/modeling/backbone/TemporalStereo.py), compiled from its file's syntax tree -- the
+    module imports timm at the top, which this image does not have.  `build(self, norm, activation)` is the statements of `__init__`
+    from `channels = [...]` on (:74-90), run against the reference's own Conv2d; `decode(self, x4, x8, x16, x32)` is the statements of
+    `_forward` from `x32 = self.conv32(x32)` up to its return (:125-138)."""
+    import ast
+    import torch.nn as nn
+    import torch.nn.functional as F
+    from architecture.modeling.layers import Conv2d, ConvTranspose2d
+    path = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "modeling", "backbone", "TemporalStereo.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "TEMPORALSTEREO")
+    init = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "__init__")
+    fwd = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "_forward")
+
+    def targets(stmt):
+        return {ast.unparse(t) for t in stmt.targets} if isinstance(stmt, ast.Assign) else set()
+    at = next(i for i, s in enumerate(init.body) if "channels" in targets(s))
+    build = ast.parse("def build(self, norm, activation):\n    pass").body[0]
+    build.body = init.body[at:]
+    assert {"self.conv32", "self.deconv32_16", "self.deconv16_8", "self.deconv8_4"} <= set().union(*map(targets, build.body))
+    at = next(i for i, s in enumerate(fwd.body) if "x32" in targets(s) and "self.conv32" in ast.unparse(s))
+    assert isinstance(fwd.body[-1], ast.Return)
+    decode = ast.parse("def decode(self, x4, x8, x16, x32):\n    pass\n    return [x4, x8, x16]").body[0]
+    decode.body[0:1] = fwd.body[at:-1]
+    assert len(decode.body) == 11, len(decode.body)            # conv32, then three times (h, w / interpolate / cat + pair), return
+    ns = {"torch": torch, "nn": nn, "F": F, "Conv2d": Conv2d, "ConvTranspose2d": ConvTranspose2d}
+    exec(compile(ast.fix_missing_locations(ast.Module(body=[build, decode], type_ignores=[])), path, "exec"), ns)
+    return ns["build"], ns["decode"]
+
+
+def decoder_cases(M):
+    """tests/golden/decoder_*.npz: the reference's own decoder lines on submodules built by its own Conv2d, on the CPU, in fp32 and
+    fp64, train mode and eval mode; dev_* = how far its fp32 run lies from its fp64 run."""
+    import torch.nn as nn
+    import decoder_ref as R
+    build, decode = reference_decoder()
+    lines = ["decoder_*.npz: tools/gen_golden.py --only-decoder, numpy %s, torch %s CPU -- the reference's own decoder" % (np.__version__, torch.__version__),
+             "(architecture/modeling/backbone/TemporalStereo.py: the statements of __init__ :74-90 and of _forward :125-138, compiled from the",
+             "file's syntax tree; the submodules are built by the reference's own Conv2d with norm 'BN' and activation 'SiLU') on seeded inputs in",
+             "float32 and in float64, in train mode and in eval mode, with the backward of seeded cotangents of the three outputs.",
+             "Inputs, all kept as their seed (tests/decoder_ref.py fixture_state / fixture_input / fixture_cotangents draw them again): convolution",
+             "weights N(0,1) * 2 / sqrt(9 Cin), BatchNorm weight U(0.5, 1.5) and bias N(0, 0.1), running mean N(0, 0.1), running variance",
+             "U(0.5, 1.5), the four maps N(0,1), the cotangents k / 8 with k an integer in [-8, 8].",
+             "Stored: seed, keys and key_shapes (the reference's state-dict keys of the four submodules in order, their shapes padded with -1),",
+             "and per mode m in (train, eval) the deviations of EVERY output and gradient: dev_<m>_<x4|x8|x16> = max |fp32 run - fp64 run|,",
+             "max_<m>_<...> = max |output| of the fp64 run, rel_grad_<m>_<x4|x8|x16|x32|parameter key> = relative L2 of the fp32 run's gradient",
+             "against the fp64 run's, all over the WHOLE arrays.  Arrays (fp32 run; one of more than %d elements at %d seeded flat positions," % (R.SAMPLE, R.SAMPLE),
+             "decoder_ref.sample): train mode <m>_<output>, grad_<m>_<input>, grad_<m>_<parameter key>; eval mode eval_x4 alone -- the last",
+             "output, behind every layer.  The eval-mode arrays left out (two outputs, 17 gradients, ~440 KB per geometry) would take the two",
+             "files to 1.8 MB; the tests compare eval mode against the fp64 restatement, with the stored deviations as bars."]
+    total = 0
+    for tag in ("a", "b"):
+        seed = synth.SEED0 + 13000 + 1000 * ord(tag)
+        ins, outs = R.geometry_shapes(tag)
+
+        def run(dt, training):
+            me = nn.Module()
+            build(me, "BN", "SiLU")
+            keys = list(me.state_dict().keys())
+            shapes = [tuple(v.shape) for v in me.state_dict().values()]
+            res = me.load_state_dict(R.fixture_state(seed), strict=True)
+            assert not res.missing_keys and not res.unexpected_keys
+            me = me.to(dt).train(training)
+            maps = R.fixture_input(seed, tag, dt)
+            for t in maps.values():
+                t.requires_grad_(True)
+            got = dict(zip(R.OUTPUTS, decode(me, maps["x4"], maps["x8"], maps["x16"], maps["x32"])))
+            cots = R.fixture_cotangents(seed, tag, dt)
+            torch.autograd.backward([got[k] for k in R.OUTPUTS], [cots[k] for k in R.OUTPUTS])
+            out = {k: v.detach() for k, v in got.items()}
+            for k in R.INPUTS:
+                out["grad_" + k] = maps[k].grad.detach()
+            for k, p in me.named_parameters():
+                out["grad_" + k] = p.grad.detach()
+            return out, keys, shapes
+
+        arrs = dict(seed=seed)
+        note = []
+        for mode in R.MODES:
+            training = mode == "train"
+            r32, keys, shapes = run(torch.float32, training)
+            r64, _, _ = run(torch.float64, training)
+            assert keys == list(R.KEYS) and shapes == [s for _, s in R.key_shapes()]
+            assert {k[5:] for k in r32 if k.startswith("grad_")} == set(R.INPUTS) | set(R.PARAM_KEYS)
+            own = R.run(seed, tag, torch.float64, training)            # the restatement stands where the reference stands
+            for k in r64:
+                assert float((own[k] - r64[k]).abs().max()) <= 1e-10 * max(1.0, float(r64[k].abs().max())), (tag, mode, k)
+            devs, rels = [], []
+            for k in r32:
+                if k.startswith("grad_"):
+                    name = k[5:]
+                    arrs["rel_grad_%s_%s" % (mode, name)] = float((r32[k].double() - r64[k]).norm() / r64[k].norm())
+                    rels.append(arrs["rel_grad_%s_%s" % (mode, name)])
+                    if training:
+                        arrs["grad_%s_%s" % (mode, name)] = R.sample(r32[k], seed)
+                else:
+                    arrs["dev_%s_%s" % (mode, k)] = float((r32[k].double() - r64[k]).abs().max())
+                    arrs["max_%s_%s" % (mode, k)] = float(r64[k].abs().max())
+                    devs.append(arrs["dev_%s_%s" % (mode, k)])
+                    if training or k == "x4":
+                        arrs["%s_%s" % (mode, k)] = R.sample(r32[k], seed)
+            note.append("%s: dev %.3g .. %.3g, rel_grad %.3g .. %.3g" % (mode, min(devs), max(devs), min(rels), max(rels)))
+        arrs["keys"] = np.array(keys)
+        arrs["key_shapes"] = np.array([list(s) + [-1] * (4 - len(s)) for s in shapes], dtype=np.int64)
+        size = save_fixed("decoder_" + tag, **arrs)
+        total += size
+        B = R.GEOMETRIES[tag][0]
+        lines.append("decoder_%s  B=%d x32 %dx%d x16 %dx%d x8 %dx%d x4 %dx%d  seed %d; %s; %.0f KB"
+                     % ((tag, B) + tuple(v for p in R.GEOMETRIES[tag][1:] for v in p) + (seed, "; ".join(note), size / 1024)))
+    lines.append("total %.0f KB" % (total / 1024))
+    assert total < 1000 * 1000, total
+    with open(os.path.join(OUT, "PROVENANCE_decoder.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def save_fixed(name, **arrs):
     """`save` with the archive's time stamps pinned, so that a fixture regenerates byte for byte."""
     import zipfile
@@ -2328,6 +2445,9 @@ def main():
         return
     if "--only-convgru" in sys.argv:
         conv_gru_cases(M)
+        return
+    if "--only-decoder" in sys.argv:
+        decoder_cases(M)
         return
     if "--only-flow-frame" in sys.argv:
         flow_frame_cases(M)
