@@ -16,26 +16,12 @@
 // all-reduced [C] vectors: the kernels take mean / var / s1 / s2 / n as arguments.
 #include <cstdlib>
 
+#include "act_fast.hpp"
 #include "ts_common.hpp"
 
 namespace {
 
 enum { BN_ACT_NONE = 0, BN_ACT_SILU = 1, BN_ACT_RELU = 2 };
-
-// 1 / (1 + e^-z) as v_exp_f32 + v_rcp_f32 + one Newton step (conv_common.hpp silu_fast: the inference epilogues' form; ~1.5 ulp).  The
-// library expf + IEEE division are ~40 instructions per element: on a 32 x 272 x 480 layer that alone was 6.7 us of the 13.9 us
-// bn_finish_apply_act_kernel took (and of every backward kernel's, which evaluates it again for the derivative).  e^-z = inf
-// (z < -88.7): the unrefined reciprocal 0 is kept, the Newton step there would be inf * 0.
-__device__ __forceinline__ float sigmoid_fast(float z) {
-#ifdef TS_EXACT_SILU
-  return 1.f / (1.f + expf(-z));
-#else
-  const float d = 1.f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f);
-  const float r = __builtin_amdgcn_rcpf(d);
-  const float rn = fmaf(fmaf(-d, r, 1.f), r, r);
-  return d < 3.0e38f ? rn : r;
-#endif
-}
 
 __device__ __forceinline__ float act_fwd(float z, int act) {
   if (act == BN_ACT_SILU) return z * sigmoid_fast(z);

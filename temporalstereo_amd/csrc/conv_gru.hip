@@ -2,69 +2,32 @@
 //
 //   z = sigmoid(convz([h, x]))   r = sigmoid(convr([h, x]))   q = tanh(convq([r*h, x]))   hidden = (1 - z) * h + z * q
 //
-// gru_conv_kernel<MT, GATES> is one implicit-GEMM 3x3 convolution (padding 1) on v_mfma_f32_16x16x4_f32 -- bitwise an fmaf chain, so a
-// recurrence keeps fp32 rounding -- whose input channels come from TWO tensors read in place: channels [0, Ch) from `a` (h, or r*h),
-// channels [Ch, Ch + Cx) from x, each with its own batch / channel strides.  No concatenation is written.
+// gru_conv_kernel<MT, GATES> is conv_hw3.hpp's 3x3 convolution (geometry, staging and pitches: there) with ONE fmaf chain per output
+// -- a recurrence keeps fp32 rounding -- whose input channels come from TWO tensors read in place: channels [0, Ch) from `a` (h, or
+// r*h), channels [Ch, Ch + Cx) from x, each with its own batch / channel strides.  No concatenation is written.
 //   GATES:  2 Ch output rows (z rows, then r rows); epilogue bias + sigmoid; stores z, r*h and (training only) r.
 //   !GATES: Ch output rows; epilogue bias + tanh, reads z and h at the output pixel, stores hidden and (training only) q.
-// A workgroup (4 waves) owns a 2 x 32 pixel tile and MT blocks of 16 output rows: every row where the grid fills the chip, fewer rows
-// per workgroup and more workgroups along the rows where it would not (launch_conv).  A wave owns 16 pixels of one tile row and holds
-// MT accumulators.  K runs over chunks of 8 input channels x 9 taps; inside a chunk k = tap * 8 + channel, so a k-step of 4 has a
-// compile-time tap and the lane's kq picks the channel: the B operand is read straight from the staged halo tile (4 x 34 per channel),
-// no im2col image.  The source seam may fall anywhere in a chunk: the source is chosen per staged channel.  Every global read is
-// predicated on row, column and channel; the zero padding is what staging writes for the others.  An output's fmaf chain runs over
-// the input channels in order whatever MT is, so the bits do not depend on the launch geometry.
-// Staging is the plain form -- load, store, barrier, MFMAs -- and the workgroups resident on a compute unit (3 to 8) hide one another's
-// loads.  Two forms that keep a chunk in registers (loads issued together before the barrier; the next chunk loaded under the current
-// chunk's MFMAs) were measured and were 4-25 % slower at every benched shape: 90-117 VGPRs instead of 48-51, fewer resident waves.
-// Weights are pre-laid by gru_weight_layout_kernel as [chunk][tap][8][rows padded to 64] per convolution (zero rows / channels
-// included), so a chunk's weights are 72 row segments of 64 MT bytes.  LDS pitches follow corr_common.hpp: a [k][columns] image wants
-// pitch == 16 mod 32.
+// The weights of both convolutions are laid out by one launch: the gate image ([wz rows | wr rows]) and, behind it, the candidate's,
+// each with its rows padded to 64.
 //
 // Backward: the convolutions' gradients run on ts_conv3d_hw_bwd_data / ts_conv3d_hw_bwd_weight (D = 1); the three element kernels
 // here carry the gates' derivatives and the sums into dh / dx.  No atomics anywhere: bit-reproducible.
-#include "corr_common.hpp"
+#include "act_fast.hpp"
+#include "conv_hw3.hpp"
 
 namespace {
 
-using corr::v4f;
-
-constexpr int kCK = 8;                       // input channels per staged chunk
-constexpr int kKC = kCK * 9;                 // contraction elements per chunk
-constexpr int kTR = 2, kTW = 32;             // pixel tile
-constexpr int kRowP = 36;                    // halo row pitch (34 columns staged)
-constexpr int kChP = (kTR + 2) * kRowP;      // 144 == 16 mod 32: the two kq of a lane half land on disjoint banks
 constexpr int kMaxC = 64;
+constexpr int kGridCap = 2048;               // blocks of the grid-stride element kernels
+using ts::strides_ok;
 
-constexpr int w_pitch(int mt) { return (mt * 16) % 32 == 16 ? mt * 16 : mt * 16 + 16; }
-inline int mt_for(int rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : rows <= 64 ? 4 : 8; }      // 16-row blocks a workgroup holds, before the grid is looked at
 inline int pitch_for(int rows) { return (rows + 63) / 64 * 64; }                  // global pitch of a weight row: whole workgroups of any MT
-inline int chunks_for(int Ch, int Cx) { return (Ch + Cx + kCK - 1) / kCK; }
 
-__device__ __forceinline__ float rcp_newton(float d) {
-  const float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.f), r, r);
-}
-// 1 / (1 + e^-v) on v_exp_f32 + v_rcp_f32 + one Newton step (conv_common.hpp silu_fast).  Whole float range: below v = -88.7 e^-v is inf,
-// the reciprocal 0 and the Newton step inf * 0 -- the unrefined 0 is kept there.  d >= 1 and the refined quotient is one rounding of
-// r (2 - d r) <= 1 / d, so the result lies in [0, 1].  NaN stays NaN.
-__device__ __forceinline__ float sigmoid_fast(float v) {
-  const float d = 1.f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-  const float r = __builtin_amdgcn_rcpf(d);
-  const float rn = fmaf(fmaf(-d, r, 1.f), r, r);
-  return d < 3.0e38f ? rn : r;
-}
-// tanh(v) = sign(v) (1 - e) / (1 + e), e = e^(-2|v|) in [0, 1]: the denominator stays in [1, 2] (no overflow anywhere; 2|v| = inf gives
-// e = 0), both factors are <= 1, so |result| <= 1.
-__device__ __forceinline__ float tanh_fast(float v) {
-  const float e = __builtin_amdgcn_exp2f(fabsf(v) * -2.8853900817779268f);
-  return copysignf((1.f - e) * rcp_newton(1.f + e), v);
-}
-
+template <bool GATES>
 struct Gru {
+  hw3::Geom g;              // rows: 2 Ch (gates) or Ch (candidate)
   const float* a;           // source of channels [0, Ch): h (gates) or r*h (candidate)
   const float* x;           // source of channels [Ch, Ch + Cx)
-  const float* w;           // [chunks][9][8][rp]
   const float* b0;          // bias of rows [0, Ch)
   const float* b1;          // bias of rows [Ch, 2 Ch) (gates)
   const float* h;           // the hidden state the epilogue reads
@@ -72,124 +35,42 @@ struct Gru {
   float* o0;                // gates: z          candidate: hidden
   float* o1;                // gates: r * h      candidate: q or NULL
   float* o2;                // gates: r or NULL
-  int Ch, Cx, H, W, tiles_x, tiles_y;
-  int rp, groups;           // pitch of a weight row in global memory (rows padded to 64); workgroups along the output rows
+  int Ch;
   long long a_bs, a_cs, x_bs, x_cs, h_bs, h_cs;
+
+  // the lambdas hold copies of what they use, never `this`: a store through o0 / o1 / o2 then cannot be taken to change a field
+  __device__ __forceinline__ auto source(int b) const {
+    return [pa = a + b * a_bs, px = x + b * x_bs, Ch = Ch, a_cs = a_cs, x_cs = x_cs, W = g.W](int gc, int gy, int gx) {
+      const long long pix = hw3::pixel_at(gy, gx, W);
+      return gc < Ch ? pa[gc * a_cs + pix] : px[(gc - Ch) * x_cs + pix];          // the seam may fall anywhere in a chunk
+    };
+  }
+  __device__ __forceinline__ auto sink(int b, int gy, int gx) const {
+    const long long HW = static_cast<long long>(g.H) * g.W, pix = hw3::pixel_at(gy, gx, g.W);
+    return [HW, ph = h + b * h_bs + pix, ob = static_cast<long long>(b) * Ch * HW + pix, h_cs = h_cs, Ch = Ch, b0 = b0, b1 = b1, zin = zin,
+            o0 = o0, o1 = o1, o2 = o2](int row, float sum) {
+      if (GATES) {
+        if (row < Ch) {
+          o0[ob + row * HW] = sigmoid_fast(sum + b0[row]);
+        } else {
+          const int c = row - Ch;
+          const float gate = sigmoid_fast(sum + b1[c]);
+          if (o2) o2[ob + c * HW] = gate;
+          o1[ob + c * HW] = gate * ph[c * h_cs];
+        }
+      } else {
+        const long long at = ob + row * HW;
+        const float q = tanh_fast(sum + b0[row]);
+        const float z = zin[at], hv = ph[row * h_cs];
+        if (o1) o1[at] = q;
+        o0[at] = (1.f - z) * hv + z * q;
+      }
+    };
+  }
 };
 
 template <int MT, bool GATES>
-__global__ void __launch_bounds__(256) gru_conv_kernel(const Gru p) {
-  constexpr int PW = w_pitch(MT);
-  constexpr int kHalo = (kTR + 2) * (kTW + 2);                  // staged values per channel
-  __shared__ __attribute__((aligned(16))) float sW[kKC * PW];
-  __shared__ float sX[kCK * kChP];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, kq = lane >> 4;
-  unsigned blk = blockIdx.x;
-  const int rg = blk % p.groups; blk /= p.groups;               // neighbours share the input tile
-  const int tx = blk % p.tiles_x; blk /= p.tiles_x;
-  const int ty = blk % p.tiles_y;
-  const int b = blk / p.tiles_y;
-  const int x0 = tx * kTW, y0 = ty * kTR;
-  const int Cin = p.Ch + p.Cx;
-  const long long HW = static_cast<long long>(p.H) * p.W;
-  const float* pa = p.a + b * p.a_bs;
-  const float* px = p.x + b * p.x_bs;
-  const float* pw = p.w + rg * (16 * MT);
-  const int pr = wave >> 1, pc = (wave & 1) * 16 + j;
-
-  v4f acc[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) acc[t] = v4f{0.f, 0.f, 0.f, 0.f};
-
-  const int nchunks = (Cin + kCK - 1) / kCK;
-  for (int ch = 0; ch < nchunks; ++ch) {
-    __syncthreads();                                             // the previous chunk has been read
-    for (int i = tid; i < kKC * 4 * MT; i += 256) {              // this workgroup's columns of the chunk's 72 weight rows, 16 bytes a piece
-      const int row = i / (4 * MT), seg = i % (4 * MT);
-      *reinterpret_cast<float4*>(sW + row * PW + seg * 4) =
-          *reinterpret_cast<const float4*>(pw + (static_cast<size_t>(ch) * kKC + row) * p.rp + seg * 4);
-    }
-    for (int i = tid; i < kCK * kHalo; i += 256) {               // halo tile, 8 channels x 4 rows x 34 columns
-      const int c = i / kHalo, rem = i - c * kHalo;
-      const int row = rem / (kTW + 2), col = rem - row * (kTW + 2);
-      const int gc = ch * kCK + c, gy = y0 - 1 + row, gx = x0 - 1 + col;
-      float v = 0.f;
-      if (gc < Cin && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {      // every read predicated on channel, row and column
-        const long long pix = static_cast<long long>(gy) * p.W + gx;
-        v = gc < p.Ch ? pa[gc * p.a_cs + pix] : px[(gc - p.Ch) * p.x_cs + pix];
-      }
-      sX[c * kChP + row * kRowP + col] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int c = half * 4 + kq;
-        const float bv = sX[c * kChP + (pr + tap / 3) * kRowP + pc + tap % 3];
-        const float* wrow = sW + (tap * kCK + c) * PW + j;
-#pragma unroll
-        for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[16 * t], bv, acc[t], 0, 0, 0);
-      }
-    }
-  }
-
-  // epilogue: the lane holds rows 16 (MT rg + t) + 4 kq + r of pixel (y0 + pr, x0 + pc)
-  const int gy = y0 + pr, gx = x0 + pc;
-  if (gy >= p.H || gx >= p.W) return;
-  const long long pix = static_cast<long long>(gy) * p.W + gx;
-  const int rows = GATES ? 2 * p.Ch : p.Ch;
-  const float* ph = p.h + b * p.h_bs + pix;
-  const long long ob = static_cast<long long>(b) * p.Ch * HW + pix;
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * (MT * rg + t) + 4 * kq + r;
-      if (row >= rows) continue;
-      if (GATES) {
-        if (row < p.Ch) {
-          p.o0[ob + row * HW] = sigmoid_fast(acc[t][r] + p.b0[row]);
-        } else {
-          const int c = row - p.Ch;
-          const float g = sigmoid_fast(acc[t][r] + p.b1[c]);
-          if (p.o2) p.o2[ob + c * HW] = g;
-          p.o1[ob + c * HW] = g * ph[c * p.h_cs];
-        }
-      } else {
-        const float q = tanh_fast(acc[t][r] + p.b0[row]);
-        const float z = p.zin[ob + row * HW], hv = ph[row * p.h_cs];
-        if (p.o1) p.o1[ob + row * HW] = q;
-        p.o0[ob + row * HW] = (1.f - z) * hv + z * q;
-      }
-    }
-  }
-}
-
-// [chunk][tap][8][pitch] images of the gate weights ([wz rows | wr rows]) and, behind them, of the candidate weights;
-// w* are the framework's [Ch][Ch + Cx][3][3].
-__global__ void __launch_bounds__(256) gru_weight_layout_kernel(const float* __restrict__ wz, const float* __restrict__ wr,
-                                                                const float* __restrict__ wq, float* __restrict__ out, int Ch, int Cin,
-                                                                int pg, int pq, int nchunks) {
-  const int ng = nchunks * kKC * pg, total = ng + nchunks * kKC * pq;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const bool gates = i < ng;
-    const int e = gates ? i : i - ng, pitch = gates ? pg : pq;
-    const int col = e % pitch, k = e / pitch;
-    const int c = k % kCK, tap = (k / kCK) % 9, ci = (k / kKC) * kCK + c;
-    float v = 0.f;
-    if (ci < Cin) {
-      const int at = ci * 9 + tap;
-      if (gates) {
-        if (col < Ch) v = wz[static_cast<size_t>(col) * Cin * 9 + at];
-        else if (col < 2 * Ch) v = wr[static_cast<size_t>(col - Ch) * Cin * 9 + at];
-      } else if (col < Ch) {
-        v = wq[static_cast<size_t>(col) * Cin * 9 + at];
-      }
-    }
-    out[i] = v;
-  }
-}
+__global__ void __launch_bounds__(256) gru_conv_kernel(const Gru<GATES> p) { hw3::conv_tile<MT, 0>(p); }
 
 // element kernels of the backward pass: [B][Ch][N] planes, dense unless strides are given
 struct Idx {
@@ -245,22 +126,12 @@ __global__ void __launch_bounds__(256) gru_grad_sum_kernel(const float* __restri
   }
 }
 
-unsigned blocks_for(long long items) {
-  long long n = (items + 255) / 256;
-  if (n > 2048) n = 2048;
-  return static_cast<unsigned>(n < 1 ? 1 : n);
-}
-
-bool strides_ok(int B, int C, long long vol, long long bs, long long cs) {
-  return cs >= vol && (B == 1 || bs >= cs * (C - 1) + vol);
-}
-
 // sizes (TS_ERR_SHAPE), then the envelope (TS_ERR_UNSUPPORTED)
 int check_cell(const char* who, int B, int Ch, int Cx, int H, int W) {
   TS_REQUIRE(B > 0 && Ch > 0 && Cx > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
   TS_REQUIRE(Ch <= kMaxC && Cx <= kMaxC, TS_ERR_UNSUPPORTED, "%s: Ch=%d / Cx=%d above %d", who, Ch, Cx, kMaxC);
   TS_REQUIRE(B < (1 << 20) && H < (1 << 20) && W < (1 << 20), TS_ERR_UNSUPPORTED, "%s: an axis of 2^20 or more", who);
-  const unsigned long long blocks = static_cast<unsigned long long>((W + kTW - 1) / kTW) * ((H + kTR - 1) / kTR) * B * 8;      // at most 8 row groups
+  const unsigned long long blocks = 8ull * hw3::tiles_x(W) * hw3::tiles_y(H) * B;      // at most 8 row groups
   TS_REQUIRE(corr::grid_blocks(blocks) != 0, TS_ERR_UNSUPPORTED, "%s: grid too large", who);
   return TS_OK;
 }
@@ -271,32 +142,20 @@ int check_planes(const char* who, int B, int Ch, long long N) {
   return TS_OK;
 }
 
-// MT blocks of 16 output rows per workgroup, `groups` workgroups along the rows.  A grid that leaves compute units idle is cut finer
-// along the rows (the input tile is then staged by more workgroups, from L2).  The fmaf chain of an output does not depend on MT.
+// the grid is cut along the rows until every compute unit has a workgroup (hw3::launch_rule)
 template <bool GATES>
-int launch_conv(Gru& p, int rows, int B, hipStream_t st, const char* what) {
-  int mt = mt_for(rows);
-  const unsigned long long tiles = static_cast<unsigned long long>(p.tiles_x) * p.tiles_y * B;
-  auto groups = [&](int m) { return (rows + 16 * m - 1) / (16 * m); };
-  while (mt > 1 && tiles * groups(mt) < static_cast<unsigned long long>(ts::kNumCU)) mt /= 2;
-  p.groups = groups(mt);
-  p.rp = pitch_for(rows);
-  const unsigned blocks = corr::grid_blocks(tiles * p.groups);
-  TS_REQUIRE(blocks != 0, TS_ERR_UNSUPPORTED, "%s: grid too large", what);
-  const dim3 grid(blocks);
-  switch (mt) {
-    case 1: hipLaunchKernelGGL((gru_conv_kernel<1, GATES>), grid, dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((gru_conv_kernel<2, GATES>), grid, dim3(256), 0, st, p); break;
-    case 4: hipLaunchKernelGGL((gru_conv_kernel<4, GATES>), grid, dim3(256), 0, st, p); break;
-    default:
-      if constexpr (GATES) hipLaunchKernelGGL((gru_conv_kernel<8, true>), grid, dim3(256), 0, st, p);      // 65 .. 128 rows: the gates alone
-      break;
-  }
+int launch_conv(Gru<GATES>& p, int B, hipStream_t st, const char* what) {
+  const hw3::Launch l = hw3::launch_rule(p.g, B, ts::kNumCU);
+  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "%s: grid too large", what);
+  hw3::dispatch_mt(l.mt, [&](auto MT) {
+    if constexpr (GATES || MT() < 8)          // 65 .. 128 rows: the gates alone
+      hipLaunchKernelGGL((gru_conv_kernel<MT(), GATES>), dim3(l.blocks), dim3(256), 0, st, p);
+  });
   return ts::launched(what);
 }
 
-size_t gates_floats(int Ch, int Cx) { return static_cast<size_t>(chunks_for(Ch, Cx)) * kKC * pitch_for(2 * Ch); }
-size_t cand_floats(int Ch, int Cx) { return static_cast<size_t>(chunks_for(Ch, Cx)) * kKC * pitch_for(Ch); }
+size_t gates_floats(int Ch, int Cx) { return hw3::image_floats(Ch + Cx, pitch_for(2 * Ch)); }
+size_t cand_floats(int Ch, int Cx) { return hw3::image_floats(Ch + Cx, pitch_for(Ch)); }
 
 }  // namespace
 
@@ -310,10 +169,10 @@ extern "C" int ts_conv_gru_weight_layout(const float* wz, const float* wr, const
   TS_REQUIRE(Ch <= kMaxC && Cx <= kMaxC, TS_ERR_UNSUPPORTED, "conv_gru_weight_layout: Ch=%d / Cx=%d above %d", Ch, Cx, kMaxC);
   TS_REQUIRE_PTR(wz); TS_REQUIRE_PTR(wr); TS_REQUIRE_PTR(wq); TS_REQUIRE_PTR(w_l);
   TS_REQUIRE_ALIGNED(w_l);
-  const long long total = static_cast<long long>(gates_floats(Ch, Cx) + cand_floats(Ch, Cx));
-  hipLaunchKernelGGL(gru_weight_layout_kernel, dim3(blocks_for(total)), dim3(256), 0, ts::as_stream(stream), wz, wr, wq, w_l, Ch, Ch + Cx,
-                     pitch_for(2 * Ch), pitch_for(Ch), chunks_for(Ch, Cx));
-  return ts::launched("gru_weight_layout_kernel");
+  hw3::WeightImages im;          // [wz | wr] at the gates' pitch, then wq at the candidate's: one launch
+  im.wa = wz; im.ra = Ch; im.wb = wr; im.rb = Ch; im.p0 = pitch_for(2 * Ch);
+  im.wc = wq; im.rc = Ch; im.p1 = pitch_for(Ch);
+  return hw3::weight_layout(im, w_l, Ch + Cx, kGridCap, ts::as_stream(stream), "gru_weight_layout_kernel");
 }
 
 extern "C" int ts_conv_gru_gates_fwd(const float* h, const float* x, const float* w_l, const float* bz, const float* br, float* z,
@@ -325,11 +184,11 @@ extern "C" int ts_conv_gru_gates_fwd(const float* h, const float* x, const float
   TS_REQUIRE(strides_ok(B, Cx, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "conv_gru_gates_fwd: x strides %lld / %lld overlap", x_bstride, x_cstride);
   TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(bz); TS_REQUIRE_PTR(br); TS_REQUIRE_PTR(z); TS_REQUIRE_PTR(rh);
   TS_REQUIRE_ALIGNED(w_l);
-  Gru p;
-  p.a = h; p.x = x; p.w = w_l; p.b0 = bz; p.b1 = br; p.h = h; p.zin = nullptr; p.o0 = z; p.o1 = rh; p.o2 = r;
-  p.Ch = Ch; p.Cx = Cx; p.H = H; p.W = W; p.tiles_x = (W + kTW - 1) / kTW; p.tiles_y = (H + kTR - 1) / kTR;
+  Gru<true> p;
+  p.g = hw3::geom(w_l, Ch + Cx, 2 * Ch, H, W, pitch_for(2 * Ch));
+  p.a = h; p.x = x; p.b0 = bz; p.b1 = br; p.h = h; p.zin = nullptr; p.o0 = z; p.o1 = rh; p.o2 = r; p.Ch = Ch;
   p.a_bs = h_bstride; p.a_cs = h_cstride; p.x_bs = x_bstride; p.x_cs = x_cstride; p.h_bs = h_bstride; p.h_cs = h_cstride;
-  return launch_conv<true>(p, 2 * Ch, B, ts::as_stream(stream), "gru_conv_kernel<gates>");
+  return launch_conv(p, B, ts::as_stream(stream), "gru_conv_kernel<gates>");
 }
 
 extern "C" int ts_conv_gru_out_fwd(const float* rh, const float* x, const float* w_l, const float* bq, const float* z, const float* h,
@@ -341,11 +200,11 @@ extern "C" int ts_conv_gru_out_fwd(const float* rh, const float* x, const float*
   TS_REQUIRE(strides_ok(B, Cx, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "conv_gru_out_fwd: x strides %lld / %lld overlap", x_bstride, x_cstride);
   TS_REQUIRE_PTR(rh); TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(bq); TS_REQUIRE_PTR(z); TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(out);
   TS_REQUIRE_ALIGNED(w_l);
-  Gru p;
-  p.a = rh; p.x = x; p.w = w_l + gates_floats(Ch, Cx); p.b0 = bq; p.b1 = nullptr; p.h = h; p.zin = z; p.o0 = out; p.o1 = q; p.o2 = nullptr;
-  p.Ch = Ch; p.Cx = Cx; p.H = H; p.W = W; p.tiles_x = (W + kTW - 1) / kTW; p.tiles_y = (H + kTR - 1) / kTR;
+  Gru<false> p;
+  p.g = hw3::geom(w_l + gates_floats(Ch, Cx), Ch + Cx, Ch, H, W, pitch_for(Ch));
+  p.a = rh; p.x = x; p.b0 = bq; p.b1 = nullptr; p.h = h; p.zin = z; p.o0 = out; p.o1 = q; p.o2 = nullptr; p.Ch = Ch;
   p.a_bs = Ch * HW; p.a_cs = HW; p.x_bs = x_bstride; p.x_cs = x_cstride; p.h_bs = h_bstride; p.h_cs = h_cstride;
-  return launch_conv<false>(p, Ch, B, ts::as_stream(stream), "gru_conv_kernel<out>");
+  return launch_conv(p, B, ts::as_stream(stream), "gru_conv_kernel<out>");
 }
 
 extern "C" int ts_conv_gru_gate_bwd_a(const float* dout, const float* z, const float* q, const float* h, float* dq_pre, float* dz_pre,
@@ -355,7 +214,7 @@ extern "C" int ts_conv_gru_gate_bwd_a(const float* dout, const float* z, const f
   TS_REQUIRE(strides_ok(B, Ch, N, h_bstride, h_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_a: h strides %lld / %lld overlap", h_bstride, h_cstride);
   TS_REQUIRE(strides_ok(B, Ch, N, dz_bstride, dz_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_a: dz_pre strides %lld / %lld overlap", dz_bstride, dz_cstride);
   TS_REQUIRE_PTR(dout); TS_REQUIRE_PTR(z); TS_REQUIRE_PTR(q); TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(dq_pre); TS_REQUIRE_PTR(dz_pre); TS_REQUIRE_PTR(dh);
-  hipLaunchKernelGGL(gru_gate_bwd_a_kernel, dim3(blocks_for(static_cast<long long>(B) * Ch * N)), dim3(256), 0, ts::as_stream(stream), dout, z,
+  hipLaunchKernelGGL(gru_gate_bwd_a_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * Ch * N, kGridCap)), dim3(256), 0, ts::as_stream(stream), dout, z,
                      q, h, dq_pre, dz_pre, dh, B, Ch, N, h_bstride, h_cstride, dz_bstride, dz_cstride);
   return ts::launched("gru_gate_bwd_a_kernel");
 }
@@ -368,7 +227,7 @@ extern "C" int ts_conv_gru_gate_bwd_b(const float* d_rh, const float* r, const f
   TS_REQUIRE(strides_ok(B, Ch, N, h_bstride, h_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_b: h strides %lld / %lld overlap", h_bstride, h_cstride);
   TS_REQUIRE(strides_ok(B, Ch, N, dr_bstride, dr_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_b: dr_pre strides %lld / %lld overlap", dr_bstride, dr_cstride);
   TS_REQUIRE_PTR(d_rh); TS_REQUIRE_PTR(r); TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(dr_pre); TS_REQUIRE_PTR(dh);
-  hipLaunchKernelGGL(gru_gate_bwd_b_kernel, dim3(blocks_for(static_cast<long long>(B) * Ch * N)), dim3(256), 0, ts::as_stream(stream), d_rh, r,
+  hipLaunchKernelGGL(gru_gate_bwd_b_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * Ch * N, kGridCap)), dim3(256), 0, ts::as_stream(stream), d_rh, r,
                      h, dr_pre, dh, B, Ch, N, drh_bstride, drh_cstride, h_bstride, h_cstride, dr_bstride, dr_cstride);
   return ts::launched("gru_gate_bwd_b_kernel");
 }
@@ -379,7 +238,7 @@ extern "C" int ts_conv_gru_grad_sum(const float* dcat_g, const float* dcat_q, fl
   TS_REQUIRE(Cx > 0, TS_ERR_SHAPE, "conv_gru_grad_sum: non-positive size");
   TS_REQUIRE(Cx <= kMaxC, TS_ERR_UNSUPPORTED, "conv_gru_grad_sum: Cx=%d above %d", Cx, kMaxC);
   TS_REQUIRE_PTR(dcat_g); TS_REQUIRE_PTR(dcat_q); TS_REQUIRE_PTR(dh);
-  hipLaunchKernelGGL(gru_grad_sum_kernel, dim3(blocks_for(static_cast<long long>(B) * (Ch + Cx) * N)), dim3(256), 0, ts::as_stream(stream),
+  hipLaunchKernelGGL(gru_grad_sum_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * (Ch + Cx) * N, kGridCap)), dim3(256), 0, ts::as_stream(stream),
                      dcat_g, dcat_q, dh, dx, B, Ch, Cx, N);
   return ts::launched("gru_grad_sum_kernel");
 }

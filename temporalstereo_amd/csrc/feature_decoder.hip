@@ -3,148 +3,61 @@
 //
 //   x16 = deconv32_16(cat([resize(conv32(x32)), x16]))   x8 = deconv16_8(cat([resize(x16), x8]))   x4 = deconv8_4(cat([resize(x8), x4]))
 //
-// decoder_conv_kernel<MT> is one implicit-GEMM 3x3 convolution (stride 1, padding 1) on v_mfma_f32_16x16x4_f32 -- bitwise an fmaf
-// chain -- whose input channels come from TWO tensors, neither written anywhere first: channels [0, Cu) are `up` [B,Cu,h,w] read
-// THROUGH the align-corners bilinear resize to (H, W) (ts::lin_src, the coordinates of every other resize of the library; the four
-// taps are combined while the halo tile is staged), channels [Cu, Cu + Cs) are `skip` [B,Cs,H,W] read in place.  The convolution's
-// zero padding applies to the resized map: a halo position outside (H, W) is staged as 0.  Cu = 0 is the plain wide convolution.
-// The geometry is conv_gru.hip's: a workgroup (4 waves) owns a 2 x 32 pixel tile and MT blocks of 16 output rows, a wave 16 pixels
-// of one tile row and MT accumulators; output channels beyond 16 MT are tiled over the grid (neighbouring workgroups share the input
-// tile, so the second and later read it from L2).  K runs over chunks of 8 input channels x 9 taps, k = tap * 8 + channel inside a
-// chunk; the B operand is read straight from the staged halo tile (4 x 34 per channel), no im2col image.  The source seam may fall
-// anywhere in a chunk: the source is chosen per staged channel.  Every global read is predicated on row, column and channel.
-// K reaches 4608 here, and one fp32 fmaf chain of that length sits at four times the error of the framework's blocked sums: the
-// accumulators are added into a second set every kFlush chunks (a chain of 288 products, then a chain of at most 16 blocks).  An
-// output's chains run over the input channels in order whatever MT is, so the bits do not depend on the launch geometry.
+// decoder_conv_kernel<MT> is conv_hw3.hpp's 3x3 convolution (geometry, staging, pitches and the blocked summation: there) whose
+// input channels come from TWO tensors, neither written anywhere first: channels [0, Cu) are `up` [B,Cu,h,w] read THROUGH the
+// align-corners bilinear resize to (H, W) (ts::lin_src, the coordinates of every other resize of the library; the four taps are
+// combined while the halo tile is staged), channels [Cu, Cu + Cs) are `skip` [B,Cs,H,W] read in place.  The convolution's zero
+// padding applies to the resized map: a halo position outside (H, W) is staged as 0.  Cu = 0 is the plain wide convolution.
+// The accumulators are flushed every kFlush chunks: K reaches 4608 here.
 // Epilogue: act(y * scale + shift), act 0 none | 1 silu_fast; scale / shift may be NULL (1 / 0).
-// Weights are pre-laid by decoder_weight_layout_kernel as [chunk][tap][8][rows padded] (zero rows / channels included).
 //
 // resize_bilinear_bwd_kernel is the adjoint of the align-corners resize as a GATHER: a coarse pixel sums, rows then columns in
 // ascending order, the fine pixels whose two source indices (ts::lin_src again, evaluated per candidate: the forward's own
 // predicate) include it.  No atomics: bit-reproducible.
 #include "bilinear.hpp"
 #include "conv_common.hpp"
+#include "conv_hw3.hpp"
 
 namespace {
 
-constexpr int kCK = 8;                       // input channels per staged chunk
-constexpr int kKC = kCK * 9;                 // contraction elements per chunk
-constexpr int kTR = 2, kTW = 32;             // pixel tile
-constexpr int kRowP = 36;                    // halo row pitch (34 columns staged)
-constexpr int kChP = (kTR + 2) * kRowP;      // 144 == 16 mod 32: the two kq of a lane half land on disjoint banks
 constexpr int kMaxC = 512;                   // Cu + Cs and Cout
 constexpr int kFlush = 4;                    // chunks (32 input channels, 288 products) per block of the blocked summation
 constexpr int kMaxAxis = 1 << 20;
+constexpr int kGridCap = 4096;               // blocks of the grid-stride element kernels
+using ts::strides_ok;
 
-constexpr int w_pitch(int mt) { return (mt * 16) % 32 == 16 ? mt * 16 : mt * 16 + 16; }
-inline int mt_for(int rows) { return rows <= 16 ? 1 : rows <= 32 ? 2 : rows <= 64 ? 4 : 8; }
 inline int pitch_for(int rows) { return rows <= 64 ? 64 : (rows + 127) / 128 * 128; }      // whole workgroups of any MT
-inline int chunks_for(int Cin) { return (Cin + kCK - 1) / kCK; }
-inline size_t weight_floats(int Cin, int Cout) { return static_cast<size_t>(chunks_for(Cin)) * kKC * pitch_for(Cout); }
 
 struct Dec {
+  hw3::Geom g;              // rows: Cout
   const float* up;          // source of channels [0, Cu), [B,Cu,h,w], read through the resize
   const float* skip;        // source of channels [Cu, Cu + Cs), [B,Cs,H,W]
-  const float* w;           // [chunks][9][8][rp]
   const float* scale;
   const float* shift;
   float* y;
-  int Cu, Cs, Cout, h, w_in, H, W, tiles_x, tiles_y;
-  int rp, groups, act;
+  int Cu, h, w_in, act;
   float sh, sw;             // source steps of the resize
   long long up_bs, up_cs, skip_bs, skip_cs, y_bs, y_cs;
+
+  // the lambdas hold copies of what they use, never `this`: a store through y then cannot be taken to change a field
+  __device__ __forceinline__ auto source(int b) const {
+    return [pu = up + b * up_bs, ps = skip + b * skip_bs, Cu = Cu, up_cs = up_cs, skip_cs = skip_cs, h = h, w_in = w_in, sh = sh, sw = sw,
+            W = g.W](int gc, int gy, int gx) {
+      if (gc < Cu) return ts::rescaled_at<long long>(pu + gc * up_cs, w_in, 1, h, w_in, sh, sw, 1.f, gy, gx);
+      return ps[(gc - Cu) * skip_cs + hw3::pixel_at(gy, gx, W)];
+    };
+  }
+  __device__ __forceinline__ auto sink(int b, int gy, int gx) const {
+    return [py = y + b * y_bs + hw3::pixel_at(gy, gx, g.W), y_cs = y_cs, scale = scale, shift = shift, act = act](int row, float v) {
+      if (scale) v *= scale[row];
+      if (shift) v += shift[row];
+      py[row * y_cs] = act == ACT_SILU ? silu_fast(v) : v;
+    };
+  }
 };
 
 template <int MT>
-__global__ void __launch_bounds__(256) decoder_conv_kernel(const Dec p) {
-  constexpr int PW = w_pitch(MT);
-  constexpr int kHalo = (kTR + 2) * (kTW + 2);                  // staged values per channel
-  __shared__ __attribute__((aligned(16))) float sW[kKC * PW];
-  __shared__ float sX[kCK * kChP];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, kq = lane >> 4;
-  unsigned blk = blockIdx.x;
-  const int rg = blk % p.groups; blk /= p.groups;               // neighbours share the input tile
-  const int tx = blk % p.tiles_x; blk /= p.tiles_x;
-  const int ty = blk % p.tiles_y;
-  const int b = blk / p.tiles_y;
-  const int x0 = tx * kTW, y0 = ty * kTR;
-  const int Cin = p.Cu + p.Cs;
-  const float* pu = p.up + b * p.up_bs;
-  const float* ps = p.skip + b * p.skip_bs;
-  const float* pw = p.w + rg * (16 * MT);
-  const int pr = wave >> 1, pc = (wave & 1) * 16 + j;
-
-  v4f acc[MT], tot[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) acc[t] = tot[t] = v4f{0.f, 0.f, 0.f, 0.f};
-
-  const int nchunks = (Cin + kCK - 1) / kCK;
-  for (int ch = 0; ch < nchunks; ++ch) {
-    if (ch != 0 && ch % kFlush == 0) {                           // blocked summation: a chain of 288 products, then a chain of blocks
-#pragma unroll
-      for (int t = 0; t < MT; ++t) {
-        tot[t] += acc[t];
-        acc[t] = v4f{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-    __syncthreads();                                             // the previous chunk has been read
-    for (int i = tid; i < kKC * 4 * MT; i += 256) {              // this workgroup's columns of the chunk's 72 weight rows, 16 bytes a piece
-      const int row = i / (4 * MT), seg = i % (4 * MT);
-      *reinterpret_cast<float4*>(sW + row * PW + seg * 4) =
-          *reinterpret_cast<const float4*>(pw + (static_cast<size_t>(ch) * kKC + row) * p.rp + seg * 4);
-    }
-    for (int i = tid; i < kCK * kHalo; i += 256) {               // halo tile, 8 channels x 4 rows x 34 columns
-      const int c = i / kHalo, rem = i - c * kHalo;
-      const int row = rem / (kTW + 2), col = rem - row * (kTW + 2);
-      const int gc = ch * kCK + c, gy = y0 - 1 + row, gx = x0 - 1 + col;
-      float v = 0.f;
-      if (gc < Cin && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W) {      // every read predicated on channel, row and column
-        if (gc < p.Cu) v = ts::rescaled_at<long long>(pu + gc * p.up_cs, p.w_in, 1, p.h, p.w_in, p.sh, p.sw, 1.f, gy, gx);
-        else v = ps[(gc - p.Cu) * p.skip_cs + static_cast<long long>(gy) * p.W + gx];
-      }
-      sX[c * kChP + row * kRowP + col] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int c = half * 4 + kq;
-        const float bv = sX[c * kChP + (pr + tap / 3) * kRowP + pc + tap % 3];
-        const float* wrow = sW + (tap * kCK + c) * PW + j;
-#pragma unroll
-        for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wrow[16 * t], bv, acc[t], 0, 0, 0);
-      }
-    }
-  }
-
-  // epilogue: the lane holds rows 16 (MT rg + t) + 4 kq + r of pixel (y0 + pr, x0 + pc)
-  const int gy = y0 + pr, gx = x0 + pc;
-  if (gy >= p.H || gx >= p.W) return;
-  float* py = p.y + b * p.y_bs + static_cast<long long>(gy) * p.W + gx;
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * (MT * rg + t) + 4 * kq + r;
-      if (row >= p.Cout) continue;
-      float v = tot[t][r] + acc[t][r];
-      if (p.scale) v *= p.scale[row];
-      if (p.shift) v += p.shift[row];
-      py[row * p.y_cs] = p.act == ACT_SILU ? silu_fast(v) : v;
-    }
-  }
-}
-
-// w [Cout][Cin][3][3] (the framework's, contiguous) -> [chunk][tap][8][pitch]
-__global__ void __launch_bounds__(256) decoder_weight_layout_kernel(const float* __restrict__ w, float* __restrict__ out, int Cin,
-                                                                    int Cout, int pitch, int total) {
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int col = i % pitch, k = i / pitch;
-    const int c = k % kCK, tap = (k / kCK) % 9, ci = (k / kKC) * kCK + c;
-    out[i] = (ci < Cin && col < Cout) ? w[(static_cast<size_t>(col) * Cin + ci) * 9 + tap] : 0.f;
-  }
-}
+__global__ void __launch_bounds__(256) decoder_conv_kernel(const Dec p) { hw3::conv_tile<MT, kFlush>(p); }
 
 // candidate fine indices whose source interval can touch coarse index c: [lo, hi], one more on either side than the real range
 __device__ __forceinline__ void fine_range(float scale, int c, int out_size, int& lo, int& hi) {
@@ -193,22 +106,11 @@ __global__ void __launch_bounds__(256) resize_bilinear_bwd_kernel(const float* _
   }
 }
 
-unsigned blocks_for(long long items) {
-  long long n = (items + 255) / 256;
-  if (n > 4096) n = 4096;
-  return static_cast<unsigned>(n < 1 ? 1 : n);
-}
-
-bool strides_ok(int B, int C, long long vol, long long bs, long long cs) {
-  if (C == 0) return true;
-  return cs >= vol && (B == 1 || bs >= cs * (C - 1) + vol);
-}
-
 }  // namespace
 
 extern "C" size_t ts_decoder_weight_bytes(int Cin, int Cout) {
   if (Cin <= 0 || Cout <= 0 || Cin > kMaxC || Cout > kMaxC) return 0;
-  return weight_floats(Cin, Cout) * sizeof(float);
+  return hw3::image_floats(Cin, pitch_for(Cout)) * sizeof(float);
 }
 
 extern "C" int ts_decoder_weight_layout(const float* w, float* w_l, int Cin, int Cout, void* stream) {
@@ -216,10 +118,10 @@ extern "C" int ts_decoder_weight_layout(const float* w, float* w_l, int Cin, int
   TS_REQUIRE(Cin <= kMaxC && Cout <= kMaxC, TS_ERR_UNSUPPORTED, "decoder_weight_layout: Cin=%d / Cout=%d above %d", Cin, Cout, kMaxC);
   TS_REQUIRE_PTR(w); TS_REQUIRE_PTR(w_l);
   TS_REQUIRE_ALIGNED(w_l);
-  const int total = static_cast<int>(weight_floats(Cin, Cout));          // at most 64 x 72 x 512
-  hipLaunchKernelGGL(decoder_weight_layout_kernel, dim3(blocks_for(total)), dim3(256), 0, ts::as_stream(stream), w, w_l, Cin, Cout,
-                     pitch_for(Cout), total);
-  return ts::launched("decoder_weight_layout_kernel");
+  hw3::WeightImages im;          // one weight, one image
+  im.wa = w; im.ra = Cout; im.wb = nullptr; im.rb = 0; im.p0 = pitch_for(Cout);
+  im.wc = nullptr; im.rc = 0; im.p1 = 0;
+  return hw3::weight_layout(im, w_l, Cin, kGridCap, ts::as_stream(stream), "decoder_weight_layout_kernel");
 }
 
 extern "C" int ts_decoder_conv_fwd(const float* up, const float* skip, const float* w_l, const float* scale, const float* shift, float* y,
@@ -240,34 +142,23 @@ extern "C" int ts_decoder_conv_fwd(const float* up, const float* skip, const flo
   TS_REQUIRE(B < kMaxAxis && H < kMaxAxis && W < kMaxAxis && h < kMaxAxis && w < kMaxAxis, TS_ERR_UNSUPPORTED,
              "decoder_conv_fwd: an axis of 2^20 or more");
   Dec p;
-  p.tiles_x = (W + kTW - 1) / kTW; p.tiles_y = (H + kTR - 1) / kTR;
-  // MT blocks of 16 output rows per workgroup, `groups` workgroups along the rows.  A grid of fewer than two workgroups per compute
-  // unit is cut finer along the rows: a lone workgroup has nothing to hide its staging behind (measured at 1, 2 and 4 per compute unit:
-  // batch 2 of the 544 x 960 decoder 1385 / 1218 / 1187 us, batch 8 3194 / 3175 / 3239 us).  An output's chains do not depend on MT.
-  int mt = mt_for(Cout);
-  const unsigned long long tiles = static_cast<unsigned long long>(p.tiles_x) * p.tiles_y * B;
-  auto groups = [&](int m) { return (Cout + 16 * m - 1) / (16 * m); };
-  while (mt > 1 && tiles * groups(mt) < 2ull * ts::kNumCU) mt /= 2;
-  p.groups = groups(mt);
-  const unsigned long long nblocks = tiles * p.groups;
-  TS_REQUIRE(nblocks < 0x7fffffffull, TS_ERR_UNSUPPORTED, "decoder_conv_fwd: grid too large");
+  p.g = hw3::geom(w_l, Cu + Cs, Cout, H, W, pitch_for(Cout));
+  // A grid of fewer than two workgroups per compute unit is cut finer along the rows (hw3::launch_rule): a lone workgroup has nothing
+  // to hide its staging behind (measured at 1, 2 and 4 per compute unit: batch 2 of the 544 x 960 decoder 1385 / 1218 / 1187 us,
+  // batch 8 3194 / 3175 / 3239 us).
+  const hw3::Launch l = hw3::launch_rule(p.g, B, 2ull * ts::kNumCU);
+  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "decoder_conv_fwd: grid too large");
   if (Cu > 0) TS_REQUIRE_PTR(up);
   TS_REQUIRE_PTR(skip);
   TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(y);
   TS_REQUIRE_ALIGNED(w_l);
-  p.up = up; p.skip = skip; p.w = w_l; p.scale = scale; p.shift = shift; p.y = y;
-  p.Cu = Cu; p.Cs = Cs; p.Cout = Cout; p.h = Cu ? h : 1; p.w_in = Cu ? w : 1; p.H = H; p.W = W; p.act = act;
-  p.rp = pitch_for(Cout);
+  p.up = up; p.skip = skip; p.scale = scale; p.shift = shift; p.y = y;
+  p.Cu = Cu; p.h = Cu ? h : 1; p.w_in = Cu ? w : 1; p.act = act;
   p.sh = ts::ac_scale(p.h, H); p.sw = ts::ac_scale(p.w_in, W);
   p.up_bs = up_bstride; p.up_cs = up_cstride; p.skip_bs = skip_bstride; p.skip_cs = skip_cstride; p.y_bs = y_bstride; p.y_cs = y_cstride;
-  const dim3 grid(static_cast<unsigned>(nblocks));
-  hipStream_t st = ts::as_stream(stream);
-  switch (mt) {
-    case 1: hipLaunchKernelGGL((decoder_conv_kernel<1>), grid, dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((decoder_conv_kernel<2>), grid, dim3(256), 0, st, p); break;
-    case 4: hipLaunchKernelGGL((decoder_conv_kernel<4>), grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL((decoder_conv_kernel<8>), grid, dim3(256), 0, st, p); break;
-  }
+  hw3::dispatch_mt(l.mt, [&](auto MT) {
+    hipLaunchKernelGGL((decoder_conv_kernel<MT()>), dim3(l.blocks), dim3(256), 0, ts::as_stream(stream), p);
+  });
   return ts::launched("decoder_conv_kernel");
 }
 
@@ -281,7 +172,7 @@ extern "C" int ts_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, 
   TS_REQUIRE(B < kMaxAxis && C < kMaxAxis && h < kMaxAxis && w < kMaxAxis && H < kMaxAxis && W < kMaxAxis, TS_ERR_UNSUPPORTED,
              "resize_bilinear_bwd: an axis of 2^20 or more");
   TS_REQUIRE_PTR(dy); TS_REQUIRE_PTR(dx);
-  hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(blocks_for(static_cast<long long>(B) * C * h * w)), dim3(256), 0,
+  hipLaunchKernelGGL(resize_bilinear_bwd_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * C * h * w, kGridCap)), dim3(256), 0,
                      ts::as_stream(stream), dy, dx, B, C, h, w, H, W, ts::ac_scale(h, H), ts::ac_scale(w, W), dy_bstride, dy_cstride,
                      dx_bstride, dx_cstride);
   return ts::launched("resize_bilinear_bwd_kernel");

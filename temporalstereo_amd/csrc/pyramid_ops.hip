@@ -12,21 +12,11 @@
 // All are bandwidth/latency-bound element kernels: W is the contiguous axis, consecutive lanes own
 // consecutive pixels, every tensor is read once and written once (the 5^3 pooling goes through an
 // LDS plane tile and a 5-deep register ring along D instead of 125 global taps per output).
+#include "act_fast.hpp"
 #include "regress_tails.hpp"
 #include "ts_common.hpp"
 
 namespace {
-
-// (the inference forms; v_exp_f32 / v_rcp_f32 as conv_common.hpp's silu_fast)
-__device__ __forceinline__ float silu(float v) {
-#ifdef TS_EXACT_SILU
-  return v / (1.f + expf(-v));
-#endif
-  const float d = 1.f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f);
-  const float r = __builtin_amdgcn_rcpf(d);
-  const float rn = fmaf(fmaf(-d, r, 1.f), r, r);
-  return v * (d < 3.0e38f ? rn : r);          // d = inf: the Newton step would be inf * 0
-}
 
 unsigned grid_for(long long n, int threads) {
   long long blocks = (n + threads - 1) / threads;
@@ -78,7 +68,7 @@ resize_add_act_kernel(const float* __restrict__ a, const float* __restrict__ bsr
     const float v11 = (1.f - lx) * p1[y1 * p.Wa + x0] + lx * p1[y1 * p.Wa + x1];
     float v = (1.f - ld) * ((1.f - ly) * v00 + ly * v01) + ld * ((1.f - ly) * v10 + ly * v11);
     if (bp) v += bp[i];
-    op[i] = p.act == 1 ? silu(v) : v;
+    op[i] = p.act == 1 ? silu_fast(v) : v;
   }
 }
 
@@ -226,7 +216,7 @@ merge_candidates_kernel(const float* __restrict__ vol, const float* __restrict__
         float* ov = out_vol + static_cast<size_t>(b) * p.out_bstride + static_cast<size_t>(rank) * p.HW + px;
 #pragma unroll
         for (int cc = 0; cc < MERGE_CPB; ++cc) {
-          const float val = (j < p.D0) ? v[j][cc] : silu(w_[cc] * m[j] * sc_[cc] + sh_[cc]);
+          const float val = (j < p.D0) ? v[j][cc] : silu_fast(w_[cc] * m[j] * sc_[cc] + sh_[cc]);
           if (c0 + cc < p.C) ov[static_cast<size_t>(c0 + cc) * p.out_cstride] = val;
         }
       }

@@ -395,16 +395,8 @@ inline bool quad_ok(const void* p, long long a, long long b) {
   return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && a % 4 == 0 && b % 4 == 0;
 }
 
-unsigned blocks_for(long long items) {
-  long long n = (items + 255) / 256;
-  if (n > 2048) n = 2048;
-  return static_cast<unsigned>(n < 1 ? 1 : n);
-}
-
-// a strided [B][C][D*H*W] operand: every element the kernels touch lies inside what the strides describe
-bool strides_ok(int B, int C, long long vol, long long bs, long long cs) {
-  return cs >= vol && (B == 1 || bs >= cs * (C - 1) + vol);
-}
+constexpr int kGridCap = 2048;          // blocks of the grid-stride element kernels
+using ts::strides_ok;
 
 }  // namespace
 
@@ -489,7 +481,7 @@ extern "C" int ts_spp3d_pool_bwd(const float* g0, const float* g1, const float* 
   Spp p;
   fill_levels(p, B, C, D, H, W, num_levels, s);
   const bool v4 = W % 4 == 0 && quad_ok(grad_x, gx_bstride, gx_cstride) && (addend == nullptr || quad_ok(addend, addend_bstride, addend_cstride));
-  const dim3 grid(blocks_for(static_cast<long long>(D) * H * ((W + 3) / 4)), static_cast<unsigned>(B * C));
+  const dim3 grid(ts::blocks_for(static_cast<long long>(D) * H * ((W + 3) / 4), kGridCap), static_cast<unsigned>(B * C));
   ts::dispatch_bool(v4, [&](auto V) {
     hipLaunchKernelGGL(spp_pool_bwd_kernel<V()>, grid, dim3(256), 0, ts::as_stream(stream), grad_pooled, addend, grad_x, p, addend_bstride,
                        addend_cstride, gx_bstride, gx_cstride);
@@ -529,7 +521,7 @@ extern "C" int ts_spp3d_expand_fwd(const float* x, const float* lv0, const float
     }
   }
   const bool v4 = W % 4 == 0 && quad_ok(x, x_bstride, x_cstride) && (reinterpret_cast<uintptr_t>(cat) & 15u) == 0;
-  const dim3 grid(blocks_for(static_cast<long long>(D) * H * ((W + 3) / 4)), static_cast<unsigned>(B * (C + Cl * num_levels)));
+  const dim3 grid(ts::blocks_for(static_cast<long long>(D) * H * ((W + 3) / 4), kGridCap), static_cast<unsigned>(B * (C + Cl * num_levels)));
   ts::dispatch_bool(v4, [&](auto V) {
     hipLaunchKernelGGL(spp_expand_fwd_kernel<V()>, grid, dim3(256), 0, ts::as_stream(stream), x, cat, p, x_bstride, x_cstride);
   });

@@ -42,6 +42,19 @@ inline void dispatch_bool(bool b, F&& f) {
 inline long long env_ll(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
 inline bool env_not_zero(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
 
+// blocks of a 256-thread grid-stride grid over `items`, at most `cap`
+inline unsigned blocks_for(long long items, long long cap) {
+  long long n = (items + 255) / 256;
+  if (n > cap) n = cap;
+  return static_cast<unsigned>(n < 1 ? 1 : n);
+}
+
+// a strided [B][C][vol] operand: every element the kernels touch lies inside what the strides describe (C == 0: nothing is touched)
+inline bool strides_ok(int B, int C, long long vol, long long bs, long long cs) {
+  if (C == 0) return true;
+  return cs >= vol && (B == 1 || bs >= cs * (C - 1) + vol);
+}
+
 constexpr int kWave = 64;       // CDNA4 wavefront
 constexpr int kNumCU = 256;     // MI355X
 constexpr int kNumXCD = 8;

@@ -2729,6 +2729,32 @@ def _gru_bwd_weight_layout(ws, Cin):
     return out
 
 
+_WGRAD_MAX_COUT = 64              # ts_conv3d_hw_bwd_weight holds at most 64 output channels
+
+
+def _wgrad_by_source(sources, dy):
+    """dw [Cout, sum of channels, 3, 3] of a 3x3 convolution whose input channels come from several tensors: `sources` is the list of
+    (source [B,c,H,W], c) in channel order, dy a [B,Cout,H,W] view with a dense plane.  ts_conv3d_hw_bwd_weight holds at most 64 output
+    channels and reads one source, so it runs per slice of dy's channels and per source; the blocks are joined along the input channels,
+    then along the rows."""
+    L, st = _lib.lib(), _stream()
+    B, Cout, H, W = dy.shape
+    rows = []
+    for co in range(0, Cout, _WGRAD_MAX_COUT):
+        n = min(_WGRAD_MAX_COUT, Cout - co)
+        dy_s = dy[:, co:co + n]
+        parts = []
+        for src, cin in sources:
+            part = torch.empty((n, cin, 3, 3), device=dy.device, dtype=torch.float32)
+            ws, nws = _wgrad_workspace(cin, n, 9, dy.device)
+            rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(src), _lib.ptr(dy_s), _lib.ptr(part), B, cin, n, 1, H, W, 1, 1, src.stride(0),
+                                           src.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(ws), nws, st)
+            _lib.check(rc, "ts_conv3d_hw_bwd_weight")
+            parts.append(part)
+        rows.append(parts[0] if len(parts) == 1 else torch.cat(parts, 1))
+    return rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+
+
 class _ConvGRU(torch.autograd.Function):
     """hidden = (1 - z) * h + z * q of the gated recurrent cell in two launches (ts_conv_gru_gates_fwd, ts_conv_gru_out_fwd) after
     one weight-layout launch; h and x are read in place.  r and q are kept only when a backward pass can ask for them.
@@ -2802,22 +2828,9 @@ class _ConvGRU(torch.autograd.Function):
         _lib.check(L.ts_conv_gru_grad_sum(_lib.ptr(dcat_g), _lib.ptr(dcat_q), _lib.ptr(dh), _lib.ptr(dx), B, Ch, Cx, N, st),
                    "ts_conv_gru_grad_sum")
 
-        def wgrad(dy, dy_bs, src_h):
-            """dw [Ch, Ch + Cx, 3, 3] of one gate: ts_conv3d_hw_bwd_weight holds at most 64 output channels and reads one source, so it
-            runs per source and the two blocks are joined along the input channels."""
-            parts = []
-            for src, cin in ((src_h, Ch), (x, Cx)):
-                dw = torch.empty((Ch, cin, 3, 3), device=dev, dtype=torch.float32)
-                ws, nws = _wgrad_workspace(cin, Ch, 9, dev)
-                rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(src), _lib.ptr(dy), _lib.ptr(dw), B, cin, Ch, 1, H, W, 1, 1, src.stride(0), src.stride(1),
-                                               dy_bs, N, _lib.ptr(ws), nws, st)
-                _lib.check(rc, "ts_conv3d_hw_bwd_weight")
-                parts.append(dw)
-            return torch.cat(parts, 1)
-
-        dwz = wgrad(dgate, 2 * Ch * N, h) if need[2] else None
-        dwr = wgrad(dr_pre, 2 * Ch * N, h) if need[4] else None
-        dwq = wgrad(dq_pre, Ch * N, rh) if need[6] else None
+        dwz = _wgrad_by_source(((h, Ch), (x, Cx)), dgate[:, :Ch]) if need[2] else None          # Ch <= 64: one slice each
+        dwr = _wgrad_by_source(((h, Ch), (x, Cx)), dr_pre) if need[4] else None
+        dwq = _wgrad_by_source(((rh, Ch), (x, Cx)), dq_pre) if need[6] else None
         dbz = dbr = dbq = None
         if need[3] or need[5]:
             both = _channel_sum(dgate)
@@ -2840,7 +2853,6 @@ def conv_gru(last_hidden, x, wz, bz, wr, br, wq, bq, return_gates=False):
 
 # ---- FeatureDecoder (reference: backbone/TemporalStereo.py:78-90,125-138) ---------------------------------------------------------------
 DECODER_MAX_CHANNELS = 512        # the kernel path's envelope: Cu + Cs and Cout (csrc/feature_decoder.hip)
-_WGRAD_MAX_COUT = 64              # ts_conv3d_hw_bwd_weight holds at most 64 output channels
 
 
 def decoder_conv_supported(in_channels, out_channels):
@@ -3034,20 +3046,7 @@ class _DecoderConv(torch.autograd.Function):
                            "ts_resize_bilinear_fwd")
                 sources.append((resized, Cu))
             sources.append((skip, Cs))
-            rows = []
-            for co in range(0, Cout, _WGRAD_MAX_COUT):
-                n = min(_WGRAD_MAX_COUT, Cout - co)
-                dy_s = dy[:, co:co + n]
-                parts = []
-                for src, cin in sources:
-                    part = torch.empty((n, cin, 3, 3), device=dev, dtype=torch.float32)
-                    wsp, nws = _wgrad_workspace(cin, n, 9, dev)
-                    rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(src), _lib.ptr(dy_s), _lib.ptr(part), B, cin, n, 1, H, W, 1, 1, src.stride(0),
-                                                   src.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(wsp), nws, st)
-                    _lib.check(rc, "ts_conv3d_hw_bwd_weight")
-                    parts.append(part)
-                rows.append(parts[0] if len(parts) == 1 else torch.cat(parts, 1))
-            dw = rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+            dw = _wgrad_by_source(sources, dy)
         if has_bias and need[3]:
             gbias = _channel_sum(dy)
         return gup, gskip, dw, gbias, ggamma, gbeta, None, None, None, None, None, None, None, None, None

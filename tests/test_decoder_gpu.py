@@ -192,6 +192,38 @@ def test_weights_scaled_by_1e3():
                   max(4.0 * c["rel"][k], 1e-6))
 
 
+def test_bits_do_not_depend_on_the_batch_grouping():
+    """Sixteen images of Cu = 24 (from a 13 x 27 map), Cs = 20 on a 31 x 63 plane, a bias, no BatchNorm: Cin = 44 is six chunks (one
+    flush of the blocked summation is crossed, the source seam inside a chunk, a ragged last chunk), 32 pixel tiles per image, ragged
+    at the right and the bottom.  The calls of every grouping have the bits of the B = 16 call.  The launch rule (csrc/conv_hw3.hpp
+    launch_rule, at least 512 workgroups) sends the groupings to
+        (a) Cout = 128   B = 16  decoder_conv_kernel<8>    B = 8  <4>    B = 4  <2>    B = 2  <1>
+        (b) Cout = 130   B = 16  decoder_conv_kernel<8>, two row groups, the second with 2 live rows of 128    B = 2  <1>
+    -- every instantiation there is, where no LAYERS entry leaves <1>.  Observed in a kernel trace of this test (rocprofv3
+    --kernel-trace, a run of its own): profiles/hw3_grouping_kernel_trace.txt.  The B = 2 result also meets the fp64 restatement at
+    the stage bar."""
+    B, Cu, Cs, h, w, H, W = 16, 24, 20, 13, 27, 31, 63
+    t = lambda a: torch.from_numpy(np.asarray(a, dtype=np.float32))
+    for Cout, groupings in ((128, (16, 8, 4, 2)), (130, (16, 2))):
+        seed = 7100 + Cout
+        up, skip = t(synth.normal(seed, "up", (B, Cu, h, w))), t(synth.normal(seed, "skip", (B, Cs, H, W)))
+        weight = t(synth.normal(seed, "w", (Cout, Cu + Cs, 3, 3)).astype(np.float64) * (2.0 / np.sqrt(9.0 * (Cu + Cs))))
+        bias = t(synth.normal(seed, "bias", (Cout,), 0.1))
+        ud, sd, wd, bd = gpu(up), gpu(skip), gpu(weight), gpu(bias)
+
+        def grouped(n):
+            with torch.no_grad():
+                return torch.cat([TF.decoder_conv(ud[i:i + n], sd[i:i + n], wd, bd) for i in range(0, B, n)])
+        whole = grouped(groupings[0])
+        for n in groupings[1:]:
+            got = grouped(n)
+            assert same_bits(got, whole), "Cout = %d, B = %d" % (Cout, n)
+        assert n == 2
+        r64 = R.fused_layer(up[:2].double(), skip[:2].double(), weight.double(), bias.double())
+        r32 = R.fused_layer(up[:2], skip[:2], weight, bias)
+        check("grouping, Cout = %d, B = 2, first call" % Cout, got[:2], r64, stage_bar(float((r32.double() - r64).abs().max()), float(r64.abs().max())))
+
+
 # ------------------------------------------------------------------------------------------------------------------ the module
 GRADS = R.INPUTS + R.PARAM_KEYS
 

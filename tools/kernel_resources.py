@@ -1,4 +1,4 @@
-"""Register / scratch / occupancy table of every kernel in a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
+"""Register / scratch / occupancy / LDS table of every kernel in a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
 
     python tools/kernel_resources.py temporalstereo_amd/csrc/block_cost.hip [name filter]
     python tools/kernel_resources.py temporalstereo_amd/csrc/render.hip          (the rendering kernels: no scratch)
@@ -30,12 +30,12 @@ def main():
             if m and cur is not None:
                 cur[key] = int(m.group(1))
     names = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows), capture_output=True, text=True).stdout.splitlines()
-    print("%-90s %5s %5s %7s %4s" % ("kernel", "VGPR", "SGPR", "scratch", "occ"))
+    print("%-90s %5s %5s %7s %4s %6s" % ("kernel", "VGPR", "SGPR", "scratch", "occ", "LDS"))
     for r, n in zip(rows, names):
         n = re.sub(r"\(anonymous namespace\)::", "", n)
         n = re.sub(r"\(.*", "", n).replace("void ", "")
         if flt in n:
-            print("%-90s %5d %5d %7d %4d" % (n[:90], r.get("vgpr", -1), r.get("sgpr", -1), r.get("scratch", -1), r.get("occ", -1)))
+            print("%-90s %5d %5d %7d %4d %6d" % (n[:90], r.get("vgpr", -1), r.get("sgpr", -1), r.get("scratch", -1), r.get("occ", -1), r.get("lds", -1)))
 
 
 if __name__ == "__main__":
