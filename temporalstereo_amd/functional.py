@@ -503,9 +503,12 @@ def _x6_conv(x, weight, wspec, y, B, Cin, Cout, D, H, W, dilation, shift=None, s
     return True
 
 
-def _hw_forward(x, weight, stride, dilation, transposed, bias=None, fold=None, act=0, addend=None):
+def _hw_forward(x, weight, geom, bias=None, fold=None, act=0, addend=None):
     """Raw Conv3d (1,3,3) [padding == dilation] / ConvTranspose3d (1,3,3) stride 2, padding 1, output_padding 1 (+ bias); with
-    `fold` = (scale, shift) the epilogue applies act(y * scale + shift) (an eval-mode BatchNorm folded in, bias included)."""
+    `fold` = (scale, shift) the epilogue applies act(y * scale + shift) (an eval-mode BatchNorm folded in, bias included).
+    geom = (stride, dilation, transposed).  Replaces F.conv3d / F.conv_transpose3d inside layers.Conv3d / ConvTranspose3d
+    (reference: layers/basic_layers.py:194-235,340-388 reach cuDNN through the same two functionals)."""
+    stride, dilation, transposed = geom
     _require_gpu(x, weight)
     x = x.contiguous()
     B, Cin, D, H, W = x.shape
@@ -638,6 +641,36 @@ def _wgrad_workspace(cin, cout, taps, device):
     return torch.empty(n // 4, dtype=torch.float32, device=device), n
 
 
+def _wgrad_launch(launch, weight, ws, *args):
+    """rc of the weight-gradient call launch(*args) whose partial sums go to `ws`.  Inside a `WgradDefer` context a weight used once
+    in the step leaves its finish to that context's flush(), which keeps `ws` alive until then."""
+    defer = _WGRAD_DEFER if (_WGRAD_DEFER is not None and _WGRAD_DEFER.single_use(weight)) else None
+    if defer is None:
+        return launch(*args)
+    L = _lib.lib()
+    was = L.ts_conv_wgrad_defer(1)                   # (this thread: backward runs on autograd's own)
+    try:
+        return launch(*args)
+    finally:
+        L.ts_conv_wgrad_defer(was)
+        defer.keep.append(ws)
+
+
+def _bwd_data_layout(weight, stride, transposed):
+    """[co][t][ci] layout that ts_conv3d_{hw,d}_bwd_data reads."""
+    if transposed:
+        return _layout(weight, 1, 0)                 # = W_T[ci][co][t]
+    if stride == 2:
+        return _layout(weight, 0, 1)                 # taps as they are
+    return _layout(weight, 0, 1, flip=True)          # stride 1: the same convolution of dy with the taps flipped
+
+
+def _count_use(weight):
+    """Counts a forward use of `weight` for the active `WgradDefer`, where a backward will follow (no_grad frames do not count)."""
+    if _WGRAD_DEFER is not None and weight.requires_grad and torch.is_grad_enabled():
+        _WGRAD_DEFER.used(weight)
+
+
 def _hw_backward(x, weight, dy, geom, need_x, need_w):
     B, Cin, Cout, D, H, W, stride, dilation, transposed = geom
     dy = dy.contiguous()
@@ -648,56 +681,27 @@ def _hw_backward(x, weight, dy, geom, need_x, need_w):
         # stride 1: the input gradient is the same convolution of dy with the flipped taps, Cout -> Cin channels
         # (element (ci' = co, co' = ci, tap) of [Cout, Cin, 1, 3, 3]: ci' * Cin * 9 + co' * 9 + (8 - tap))
         if not (stride == 1 and not transposed and _x6_conv(dy, weight, (Cin * 9, 9, 1, 1), dx, B, Cout, Cin, D, H, W, dilation)):
-            if transposed:
-                w_b = _layout(weight, 1, 0)                                      # [co][t][ci] = W_T[ci][co][t]
-            elif stride == 2:
-                w_b = _layout(weight, 0, 1)                                      # [co][t][ci], taps as they are
-            else:
-                w_b = _layout(weight, 0, 1, flip=True)                           # taps flipped
+            w_b = _bwd_data_layout(weight, stride, transposed)
             rc = L.ts_conv3d_hw_bwd_data(_lib.ptr(dy), _lib.ptr(w_b), _lib.ptr(dx), B, Cin, Cout, D, H, W, stride, dilation,
                                          int(transposed), dy.stride(0), dy.stride(1), dx.stride(0), dx.stride(1), _stream())
             _lib.check(rc, "ts_conv3d_hw_bwd_data")
     if need_w:
         dw = torch.empty_like(weight)
         ws, nws = _wgrad_workspace(Cin, Cout, 9, x.device)
-        defer = _WGRAD_DEFER if (_WGRAD_DEFER is not None and _WGRAD_DEFER.single_use(weight)) else None
-        was = L.ts_conv_wgrad_defer(1) if defer is not None else 0      # (this thread: backward runs on autograd's own)
-        try:
-            if transposed:     # roles exchanged: a stride-2 convolution maps dy (2H x 2W) to x
-                rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), B, Cout, Cin, D, 2 * H, 2 * W, 2, 1,
-                                               dy.stride(0), dy.stride(1), x.stride(0), x.stride(1), _lib.ptr(ws), nws, _stream())
-            else:
-                rc = L.ts_conv3d_hw_bwd_weight(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), B, Cin, Cout, D, H, W, stride, dilation,
-                                               x.stride(0), x.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(ws), nws, _stream())
-        finally:
-            if defer is not None:
-                L.ts_conv_wgrad_defer(was)
-                defer.keep.append(ws)
+        if transposed:         # roles exchanged: a stride-2 convolution maps dy (2H x 2W) to x
+            rc = _wgrad_launch(L.ts_conv3d_hw_bwd_weight, weight, ws, _lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), B, Cout, Cin, D, 2 * H, 2 * W,
+                               2, 1, dy.stride(0), dy.stride(1), x.stride(0), x.stride(1), _lib.ptr(ws), nws, _stream())
+        else:
+            rc = _wgrad_launch(L.ts_conv3d_hw_bwd_weight, weight, ws, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), B, Cin, Cout, D, H, W,
+                               stride, dilation, x.stride(0), x.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(ws), nws, _stream())
         _lib.check(rc, "ts_conv3d_hw_bwd_weight")
     return dx, dw
 
 
-class _Conv3dHW(torch.autograd.Function):
-    """Raw Conv3d (1,3,3) [padding == dilation] / ConvTranspose3d (1,3,3) stride 2, padding 1, output_padding 1.
-    forward ts_conv3d_hw_fwd (no scale / shift / activation), backward ts_conv3d_hw_bwd_{data,weight}.
-    Replaces F.conv3d / F.conv_transpose3d inside layers.Conv3d / ConvTranspose3d
-    (reference: layers/basic_layers.py:194-235,340-388 reach cuDNN through the same two functionals)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, stride, dilation, transposed):
-        x, y, ctx.geom = _hw_forward(x, weight, stride, dilation, transposed)
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        dx, dw = _hw_backward(x, weight, dy, ctx.geom, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return dx, dw, None, None, None
-
-
-def _d_forward(x, weight, stride, dilation, padding, transposed, bias=None, fold=None, act=0):
-    """Raw Conv3d (k,1,1) / ConvTranspose3d (3,1,1) stride 2, padding 1, output_padding 1 along D (+ bias); `fold`: see _hw_forward."""
+def _d_forward(x, weight, geom, bias=None, fold=None, act=0, addend=None):
+    """Raw Conv3d (k,1,1) / ConvTranspose3d (3,1,1) stride 2, padding 1, output_padding 1 along D (+ bias in the kernel's epilogue);
+    `fold`: see _hw_forward.  geom = (stride, dilation, padding, transposed)."""
+    stride, dilation, padding, transposed = geom
     _require_gpu(x, weight)
     x = x.contiguous()
     B, Cin, Din, H, W = x.shape
@@ -725,12 +729,7 @@ def _d_backward(x, weight, dy, geom, need_x, need_w):
     L = _lib.lib()
     dx = dw = None
     if need_x:
-        if transposed:
-            w_b = _layout(weight, 1, 0)
-        elif stride == 2:
-            w_b = _layout(weight, 0, 1)
-        else:
-            w_b = _layout(weight, 0, 1, flip=True)
+        w_b = _bwd_data_layout(weight, stride, transposed)
         dx = torch.empty_like(x)
         rc = L.ts_conv3d_d_bwd_data(_lib.ptr(dy), _lib.ptr(w_b), _lib.ptr(dx), B, Cin, Cout, Din, H, W, k, stride, dilation,
                                     padding, int(transposed), dy.stride(0), dy.stride(1), dx.stride(0), dx.stride(1), _stream())
@@ -738,39 +737,14 @@ def _d_backward(x, weight, dy, geom, need_x, need_w):
     if need_w:
         dw = torch.empty_like(weight)
         ws, nws = _wgrad_workspace(Cin, Cout, k, x.device)
-        defer = _WGRAD_DEFER if (_WGRAD_DEFER is not None and _WGRAD_DEFER.single_use(weight)) else None
-        was = L.ts_conv_wgrad_defer(1) if defer is not None else 0
-        try:
-            if transposed:
-                rc = L.ts_conv3d_d_bwd_weight(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), B, Cout, Cin, 2 * Din, H, W, 3, 2, 1, 1,
-                                              dy.stride(0), dy.stride(1), x.stride(0), x.stride(1), _lib.ptr(ws), nws, _stream())
-            else:
-                rc = L.ts_conv3d_d_bwd_weight(_lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), B, Cin, Cout, Din, H, W, k, stride, dilation,
-                                              padding, x.stride(0), x.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(ws), nws, _stream())
-        finally:
-            if defer is not None:
-                L.ts_conv_wgrad_defer(was)
-                defer.keep.append(ws)
+        if transposed:
+            rc = _wgrad_launch(L.ts_conv3d_d_bwd_weight, weight, ws, _lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), B, Cout, Cin, 2 * Din, H, W,
+                               3, 2, 1, 1, dy.stride(0), dy.stride(1), x.stride(0), x.stride(1), _lib.ptr(ws), nws, _stream())
+        else:
+            rc = _wgrad_launch(L.ts_conv3d_d_bwd_weight, weight, ws, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw), B, Cin, Cout, Din, H, W, k,
+                               stride, dilation, padding, x.stride(0), x.stride(1), dy.stride(0), dy.stride(1), _lib.ptr(ws), nws, _stream())
         _lib.check(rc, "ts_conv3d_d_bwd_weight")
     return dx, dw
-
-
-class _Conv3dD(torch.autograd.Function):
-    """Raw Conv3d (k,1,1) / ConvTranspose3d (3,1,1) stride 2, padding 1, output_padding 1 along D (+ bias in the kernel's epilogue)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, stride, dilation, padding, transposed, bias=None):
-        x, y, ctx.geom = _d_forward(x, weight, stride, dilation, padding, transposed, bias)
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        dx, dw = _d_backward(x, weight, dy, ctx.geom, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        gb = _channel_sum(dy) if (ctx.has_bias and ctx.needs_input_grad[6]) else None
-        return dx, dw, None, None, None, None, gb
 
 
 _ONES = {}
@@ -803,9 +777,9 @@ def _dc_conv3_weight(weight, out=None):
     return out
 
 
-def _dc_forward(x, weight, bias=None, fold=None, act=0):
+def _dc_forward(x, weight, geom=None, bias=None, fold=None, act=0, addend=None):
     """Raw ConvTranspose2d(kernel 4, stride 2, padding 1) (+ bias) of UNet.deconv4 / deconv2 (module.py:453-457): ts_deconv2d_k4s2_fwd;
-    `fold`: see _hw_forward."""
+    `fold`: see _hw_forward.  The family has one geometry: geom is None."""
     _require_gpu(x, weight)
     x = x.contiguous()
     B, Cin, H, W = x.shape
@@ -860,30 +834,6 @@ def deconv2d_k4s2_supported(weight_shape, stride, padding, output_padding, dilat
     """True when a ConvTranspose2d runs on the HIP kernels: kernel 4, stride 2, padding 1, <= 32 output and <= 64 input channels."""
     return (len(weight_shape) == 4 and tuple(weight_shape[2:]) == (4, 4) and tuple(stride) == (2, 2) and tuple(padding) == (1, 1) and
             tuple(output_padding) == (0, 0) and tuple(dilation) == (1, 1) and groups == 1 and weight_shape[1] <= 32 and weight_shape[0] <= 64)
-
-
-class _Deconv2dK4S2(torch.autograd.Function):
-    """Raw ConvTranspose2d(4, stride 2, padding 1) + bias (UNet.deconv2, module.py:457): ts_deconv2d_k4s2_fwd forward, backward on the
-    (1,3,3) convolution kernels (see _dc_backward)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        x, y, ctx.geom = _dc_forward(x, weight, bias)
-        ctx.save_for_backward(x, weight)
-        ctx.has_bias = bias is not None
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        dx, dw = _dc_backward(x, weight, dy, ctx.geom, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        gb = _channel_sum(dy) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-        return dx, dw, gb
-
-
-def conv_transpose2d_k4s2(x, weight, bias=None):
-    """F.conv_transpose2d(x, weight, bias, stride 2, padding 1) for 4x4 kernels on the HIP kernels (forward and backward)."""
-    return _Deconv2dK4S2.apply(x, weight, bias)
 
 
 class BNFolds:
@@ -978,172 +928,163 @@ def _peer_group(group, n_floats):
     return peer.for_group(group, n_floats)
 
 
+def _bn_act_forward(y, gamma, beta, running_mean, running_var, eps, momentum, act, training, group, counter):
+    """(out, mean, var, n_total): out = act(BatchNorm(y)) over a raw convolution output y [B, C, ...], the BatchNorm tail of _ConvBNAct and
+    _DecoderConv.  Train mode: batch statistics, the running ones and `counter` updated by the statistics launch; over a `group` of
+    several ranks the statistics are exchanged (one all_gather) and n_total is 1 / (global count) as a device scalar.  Eval mode:
+    mean / var are the running statistics.  (mean, var, n_total) are what _bn_act_backward needs."""
+    B, C = y.shape[0], y.shape[1]
+    N = y.numel() // (B * C)
+    L = _lib.lib()
+    n_total = float(B * N)
+    out = torch.empty_like(y)
+    if training and group is None and _BN_FUSED:
+        # single rank: statistics and their use in two launches (ts_bn_train_fwd)
+        mean = torch.empty(C, device=y.device, dtype=torch.float32)
+        var = torch.empty_like(mean)
+        ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
+        _lib.check(L.ts_bn_train_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                     float(momentum), _lib.ptr(counter), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out), _lib.ptr(ws),
+                                     B, C, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act), _stream()),
+                   "ts_bn_train_fwd")
+        return out, mean, var, n_total
+    if training:
+        if group is not None:       # the statistics kernel writes straight into the record that is exchanged: [mean | var | count]
+            pack = torch.empty(2 * C + 1, device=y.device, dtype=torch.float32)
+            mean, var = pack[:C], pack[C:2 * C]
+        else:
+            mean = torch.empty(C, device=y.device, dtype=torch.float32)
+            var = torch.empty_like(mean)
+        ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
+        local_update = group is None and running_mean is not None
+        _lib.check(L.ts_bn_stats_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean if local_update else None),
+                                     _lib.ptr(running_var if local_update else None), float(momentum), _lib.ptr(counter),
+                                     _lib.ptr(ws), B, C, N, y.stride(0), y.stride(1), _stream()), "ts_bn_stats_fwd")
+        if group is not None:
+            # one all_gather of [mean | var | count], merged on the device (ts_bn_sync_merge); the total count stays there too
+            import torch.distributed as dist
+            world = dist.get_world_size(group)
+            pack[2 * C:].copy_(_count_const(n_total, y.device))
+            allp = torch.empty(world * (2 * C + 1), device=y.device, dtype=torch.float32)
+            pg = _peer_group(group, 2 * C + 1)
+            if pg is not None:      # one kernel over the peer-mapped mailboxes (csrc/peer.hip): no communicator launch, capturable
+                pg.all_gather(pack, allp)
+            else:
+                _all_gather_flat(allp, pack, group)
+            _EXCHANGES[0] += 1
+            mean, var = torch.empty_like(mean), torch.empty_like(var)
+            inv_n = torch.empty(1, device=y.device, dtype=torch.float32)
+            _lib.check(L.ts_bn_sync_merge(_lib.ptr(allp), world, C, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean), _lib.ptr(running_var),
+                                          float(momentum), _lib.ptr(inv_n), _stream()), "ts_bn_sync_merge")
+            n_total = inv_n                       # a device scalar from here on (backward scales its sums with it)
+    else:
+        mean, var = running_mean, running_var
+    _lib.check(L.ts_bn_apply_act_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out),
+                                     B, C, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act),
+                                     _stream()), "ts_bn_apply_act_fwd")
+    return out, mean, var, n_total
+
+
+def _bn_act_backward(y, g, mean, var, gamma, beta, eps, act, training, group, n_total, few):
+    """(dy, ggamma, gbeta) of _bn_act_forward for the output gradient g (contiguous); the pre-activation is recomputed from y.  ggamma /
+    gbeta are THIS rank's sums (a gradient exchange averages them), None without affine parameters; over a `group` the two sums that dy
+    needs are exchanged (one all_reduce).  few: ts_bn_small_train_bwd (fp64 inside), for a single rank and at most _BN_FEW_VALUES values
+    per channel -- SPP3D's coarse levels have down to two, where the gradient is what a cancellation leaves."""
+    B, C = y.shape[0], y.shape[1]
+    N = y.numel() // (B * C)
+    L = _lib.lib()
+    s1 = torch.empty(C, device=y.device, dtype=torch.float32)
+    s2 = torch.empty_like(s1)
+    ggamma, gbeta = (s2, s1) if gamma is not None else (None, None)
+    if few:
+        dy = torch.empty_like(y)
+        _lib.check(L.ts_bn_small_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy),
+                                           B, C, N, y.stride(0), y.stride(1), g.stride(0), g.stride(1), dy.stride(0), dy.stride(1),
+                                           eps, act, _stream()), "ts_bn_small_train_bwd")
+        return dy, ggamma, gbeta
+    ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
+    if training and group is None and _BN_FUSED:
+        dy = torch.empty_like(y)
+        _lib.check(L.ts_bn_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                     _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy), _lib.ptr(ws), B, C, N, y.stride(0), y.stride(1),
+                                     g.stride(0), g.stride(1), eps, act, n_total, _stream()), "ts_bn_train_bwd")
+        return dy, ggamma, gbeta
+    _lib.check(L.ts_bn_act_bwd_reduce(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                      _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ws), B, C, N, y.stride(0), y.stride(1), g.stride(0),
+                                      g.stride(1), eps, act, _stream()), "ts_bn_act_bwd_reduce")
+    t1, t2 = s1, s2
+    count = n_total
+    if training and group is not None:
+        import torch.distributed as dist
+        pack = torch.cat([s1, s2])
+        pg = _peer_group(group, 2 * C)
+        if pg is not None:
+            pg.all_reduce_sum(pack, scale=n_total)               # summed in rank order and scaled inside the exchange kernel
+        else:
+            dist.all_reduce(pack, op=dist.ReduceOp.SUM, group=group)
+            pack = pack * n_total                                # n_total is 1 / (global count) on the device here: pre-scaled sums,
+        t1, t2, count = pack[:C], pack[C:], 1.0                  # the kernel's own division is by 1 (no host read of a count)
+        _EXCHANGES[0] += 1
+    dy = torch.empty_like(y)
+    _lib.check(L.ts_bn_act_bwd_apply(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
+                                     _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(dy), B, C, N, y.stride(0), y.stride(1), g.stride(0),
+                                     g.stride(1), eps, act, int(training), count, _stream()), "ts_bn_act_bwd_apply")
+    return dy, ggamma, gbeta
+
+
 class _ConvBNAct(torch.autograd.Function):
     """conv -> BatchNorm -> activation of the reference's wrappers (layers/basic_layers.py:194-235: conv, then `self.norm`, then
-    `self.activation`) as ONE autograd node on HIP kernels: the convolution of _Conv3dHW / _Conv3dD (bias in its epilogue),
-    ts_bn_stats_fwd (train mode: batch statistics, running statistics updated in the same launch), ts_bn_apply_act_fwd; backward
-    ts_bn_act_bwd_{reduce,apply} (the pre-activation is recomputed from the raw convolution output: nothing but that output is
-    kept), then the convolution's data / weight gradients.  `group`: a torch.distributed process group -- statistics and the two
-    backward sums are exchanged across its ranks (SyncBatchNorm of dist.py, one all_gather forward, one all_reduce backward)."""
+    `self.activation`) as ONE autograd node on HIP kernels: the convolution of the family's _FAMILIES entry (bias in its epilogue), then
+    _bn_act_forward; backward _bn_act_backward (nothing but the raw convolution output is kept), then the family's data / weight
+    gradients.  `group`: a torch.distributed process group -- statistics and the two backward sums are exchanged across its ranks
+    (SyncBatchNorm of dist.py, one all_gather forward, one all_reduce backward)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, family, geom, eps, momentum, act, training, group,
-                counter=None, may_fold=False, addend=None, few_values=False):
-        # few_values: with a single rank and at most 4096 values per channel the train-mode backward is ts_bn_small_train_bwd (fp64
-        # inside: SPP3D's coarse levels have down to two values per channel, where the gradient is what a cancellation leaves)
-        # addend (family "hw" only): [B, Cout, 1, Ho, Wo], added to every depth plane of the raw convolution (first_layer_split)
-        ctx.has_addend = addend is not None
-        if addend is not None and family != "hw":
+    def forward(ctx, x, weight, bias, gamma, beta, addend, spec):
+        # backward returns one gradient per argument, in this order: (x, weight, bias, gamma, beta, addend, spec -> None).
+        # spec: everything that takes no gradient, packed by conv_bn_act.
+        # addend (families with the flag only): [B, Cout, 1, Ho, Wo], added to every depth plane of the raw convolution (first_layer_split)
+        # few_values: see _bn_act_backward (train mode on a single rank only)
+        family, geom, running_mean, running_var, counter, eps, momentum, act, training, group, may_fold, few_values = spec
+        fam = _FAMILIES[family]
+        if addend is not None and not fam.takes_addend:
             raise ValueError("conv_bn_act: an addend needs the (1,3,3) family")
         # may_fold is decided by conv_bn_act in the CALLER's grad mode (inside Function.forward grad mode is always off): the folded
         # path keeps nothing for backward, so it is for calls through which no gradient can flow
         if _FOLDS is not None and not training and may_fold and running_mean is not None:
-            fold = _FOLDS.get(gamma, beta, running_mean, running_var, bias, eps, weight.shape[1] if (family == "dc" or geom[-1]) else weight.shape[0])
+            fold = _FOLDS.get(gamma, beta, running_mean, running_var, bias, eps, fam.cout(weight, geom))
             if fold is not None:        # eval frame of a training step: conv -> BatchNorm -> activation in the convolution's epilogue
-                if family == "hw":
-                    return _hw_forward(x, weight, geom[0], geom[1], geom[2], None, fold, act, addend=addend)[1]
-                if family == "dc":
-                    return _dc_forward(x, weight, None, fold, act)[1]
-                if family == "hw3":
-                    return _hw3_forward(x, weight, None, fold, act)[1]
-                return _d_forward(x, weight, geom[0], geom[1], geom[2], geom[3], None, fold, act)[1]
-        if family == "hw":
-            x, y, cg = _hw_forward(x, weight, geom[0], geom[1], geom[2], bias, addend=addend)
-        elif family == "dc":
-            x, y, cg = _dc_forward(x, weight, bias)
-        elif family == "hw3":
-            x, y, cg = _hw3_forward(x, weight, bias)
-        else:
-            x, y, cg = _d_forward(x, weight, geom[0], geom[1], geom[2], geom[3], bias)
-        B, C = y.shape[0], y.shape[1]
-        N = y.numel() // (B * C)
-        L = _lib.lib()
-        n_total = float(B * N)
-        out = torch.empty_like(y)
-        ctx.few = bool(few_values) and training and group is None and 2 <= B * N <= _BN_FEW_VALUES
-        if training and group is None and _BN_FUSED:
-            # single rank: statistics and their use in two launches (ts_bn_train_fwd)
-            mean = torch.empty(C, device=y.device, dtype=torch.float32)
-            var = torch.empty_like(mean)
-            ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
-            _lib.check(L.ts_bn_train_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                         float(momentum), _lib.ptr(counter), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out), _lib.ptr(ws),
-                                         B, C, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act), _stream()),
-                       "ts_bn_train_fwd")
-            ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
-            ctx.meta = (family, cg, float(eps), int(act), bool(training), group, n_total, bias is not None)
-            return out
-        if training:
-            if group is not None:       # the statistics kernel writes straight into the record that is exchanged: [mean | var | count]
-                pack = torch.empty(2 * C + 1, device=y.device, dtype=torch.float32)
-                mean, var = pack[:C], pack[C:2 * C]
-            else:
-                mean = torch.empty(C, device=y.device, dtype=torch.float32)
-                var = torch.empty_like(mean)
-            ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
-            local_update = group is None and running_mean is not None
-            _lib.check(L.ts_bn_stats_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean if local_update else None),
-                                         _lib.ptr(running_var if local_update else None), float(momentum), _lib.ptr(counter),
-                                         _lib.ptr(ws), B, C, N, y.stride(0), y.stride(1), _stream()), "ts_bn_stats_fwd")
-            if group is not None:
-                # one all_gather of [mean | var | count], merged on the device (ts_bn_sync_merge); the total count stays there too
-                import torch.distributed as dist
-                world = dist.get_world_size(group)
-                pack[2 * C:].copy_(_count_const(n_total, y.device))
-                allp = torch.empty(world * (2 * C + 1), device=y.device, dtype=torch.float32)
-                pg = _peer_group(group, 2 * C + 1)
-                if pg is not None:      # one kernel over the peer-mapped mailboxes (csrc/peer.hip): no communicator launch, capturable
-                    pg.all_gather(pack, allp)
-                else:
-                    _all_gather_flat(allp, pack, group)
-                _EXCHANGES[0] += 1
-                mean, var = torch.empty_like(mean), torch.empty_like(var)
-                inv_n = torch.empty(1, device=y.device, dtype=torch.float32)
-                _lib.check(L.ts_bn_sync_merge(_lib.ptr(allp), world, C, _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                              float(momentum), _lib.ptr(inv_n), _stream()), "ts_bn_sync_merge")
-                n_total = inv_n                       # a device scalar from here on (backward scales its sums with it)
-        else:
-            mean, var = running_mean, running_var
-        _lib.check(L.ts_bn_apply_act_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out),
-                                         B, C, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act),
-                                         _stream()), "ts_bn_apply_act_fwd")
+                return fam.forward(x, weight, geom, None, fold, act, addend)[1]
+        x, y, cg = fam.forward(x, weight, geom, bias, None, 0, addend)
+        out, mean, var, n_total = _bn_act_forward(y, gamma, beta, running_mean, running_var, eps, momentum, act, training, group, counter)
+        few = bool(few_values) and training and group is None and 2 <= y.numel() // y.shape[1] <= _BN_FEW_VALUES
         ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
-        ctx.meta = (family, cg, float(eps), int(act), bool(training), group, n_total, bias is not None)
+        ctx.meta = (fam, cg, float(eps), int(act), bool(training), group, n_total, few, bias is not None, addend is not None)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, weight, y, mean, var, gamma, beta = ctx.saved_tensors
-        family, cg, eps, act, training, group, n_total, has_bias = ctx.meta
-        g = g.contiguous()
-        B, C = y.shape[0], y.shape[1]
-        N = y.numel() // (B * C)
-        L = _lib.lib()
-        s1 = torch.empty(C, device=y.device, dtype=torch.float32)
-        s2 = torch.empty_like(s1)
-        if ctx.few:
-            dy = torch.empty_like(y)
-            _lib.check(L.ts_bn_small_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy),
-                                               B, C, N, y.stride(0), y.stride(1), g.stride(0), g.stride(1), dy.stride(0), dy.stride(1),
-                                               eps, act, _stream()), "ts_bn_small_train_bwd")
-            return _ConvBNAct._conv_backward(ctx, x, weight, dy, family, cg, has_bias, (s2, s1) if gamma is not None else (None, None))
-        ws = torch.empty(_q("ts_bn_workspace_bytes", B, C, N), device=y.device, dtype=torch.uint8)
-        if training and group is None and _BN_FUSED:
-            dy = torch.empty_like(y)
-            _lib.check(L.ts_bn_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                         _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy), _lib.ptr(ws), B, C, N, y.stride(0), y.stride(1),
-                                         g.stride(0), g.stride(1), eps, act, n_total, _stream()), "ts_bn_train_bwd")
-            return _ConvBNAct._conv_backward(ctx, x, weight, dy, family, cg, has_bias, (s2, s1) if gamma is not None else (None, None))
-        _lib.check(L.ts_bn_act_bwd_reduce(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                          _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ws), B, C, N, y.stride(0), y.stride(1), g.stride(0),
-                                          g.stride(1), eps, act, _stream()), "ts_bn_act_bwd_reduce")
-        ggamma, gbeta = (s2, s1) if gamma is not None else (None, None)          # local sums: the gradient exchange averages them
-        t1, t2 = s1, s2
-        count = n_total
-        if training and group is not None:
-            import torch.distributed as dist
-            pack = torch.cat([s1, s2])
-            pg = _peer_group(group, 2 * C)
-            if pg is not None:
-                pg.all_reduce_sum(pack, scale=n_total)               # summed in rank order and scaled inside the exchange kernel
-            else:
-                dist.all_reduce(pack, op=dist.ReduceOp.SUM, group=group)
-                pack = pack * n_total                                # n_total is 1 / (global count) on the device here: pre-scaled sums,
-            t1, t2, count = pack[:C], pack[C:], 1.0                  # the kernel's own division is by 1 (no host read of a count)
-            _EXCHANGES[0] += 1
-        dy = torch.empty_like(y)
-        _lib.check(L.ts_bn_act_bwd_apply(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                         _lib.ptr(t1), _lib.ptr(t2), _lib.ptr(dy), B, C, N, y.stride(0), y.stride(1), g.stride(0),
-                                         g.stride(1), eps, act, int(training), count, _stream()), "ts_bn_act_bwd_apply")
-        return _ConvBNAct._conv_backward(ctx, x, weight, dy, family, cg, has_bias, (ggamma, gbeta))
-
-    @staticmethod
-    def _conv_backward(ctx, x, weight, dy, family, cg, has_bias, gaffine):
-        if family == "hw":
-            dx, dw = _hw_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        elif family == "dc":
-            dx, dw = _dc_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        elif family == "hw3":
-            dx, dw = _hw3_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        else:
-            dx, dw = _d_backward(x, weight, dy, cg, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        gbias = None
-        if has_bias and ctx.needs_input_grad[2]:
+        fam, cg, eps, act, training, group, n_total, few, has_bias, has_addend = ctx.meta
+        need_x, need_w, need_bias, _, _, need_addend, _ = ctx.needs_input_grad
+        dy, ggamma, gbeta = _bn_act_backward(y, g.contiguous(), mean, var, gamma, beta, eps, act, training, group, n_total, few)
+        dx, dw = fam.backward(x, weight, dy, cg, need_x, need_w)
+        gbias = gadd = None
+        if has_bias and need_bias:
             gbias = _channel_sum(dy)                               # == 0 up to rounding in train mode (BatchNorm removes the mean)
-        gadd = None
-        if ctx.has_addend and ctx.needs_input_grad[16]:
+        if has_addend and need_addend:
             gadd = dy.sum(dim=2, keepdim=True)                     # the D-invariant term reaches every depth plane
-        return dx, dw, gbias, gaffine[0], gaffine[1], None, None, None, None, None, None, None, None, None, None, None, gadd, None
+        return dx, dw, gbias, ggamma, gbeta, gadd, None
 
 
 def conv_bn_act(x, weight, bias, bn, activation, family, geom, transposed=False, addend=None, few_values=False):
     """Fused wrapper forward (see _ConvBNAct).  `bn`: an nn.BatchNorm*d / dist.SyncBatchNorm module; `activation`: None | 'SiLU' |
     'ReLU'; family 'hw' geom (stride, dilation, transposed) / family 'd' geom (stride, dilation, padding, transposed) / family 'hw3'
-    (3x3x3, stride 1, padding 1: three (1,3,3) launches and a depth sum, see _hw3_forward) geom (1, 1, False)."""
+    (3x3x3, stride 1, padding 1: three (1,3,3) launches and a depth sum, see _hw3_forward) geom (1, 1, False) / family 'dc'
+    (ConvTranspose2d kernel 4, stride 2, padding 1) geom None: the keys of _FAMILIES."""
     # parameters / buffers straight from the module's dictionaries: nn.Module.__getattr__ (the fallback every `bn.weight`,
     # `bn.running_mean` ... goes through) was ~10 lookups x 180 wrappers per frame
-    if _WGRAD_DEFER is not None and weight.requires_grad and torch.is_grad_enabled():
-        _WGRAD_DEFER.used(weight)          # (counted where a backward will follow: no_grad frames do not count)
+    _count_use(weight)
     d, P, Bf = bn.__dict__, bn._parameters, bn._buffers
     rmean = Bf.get("running_mean")
     training = d["training"] or rmean is None
@@ -1158,8 +1099,8 @@ def conv_bn_act(x, weight, bias, bn, activation, family, geom, transposed=False,
     gamma, beta = P["weight"], P["bias"]
     may_fold = (not training) and (not torch.is_grad_enabled() or not any(
         t is not None and t.requires_grad for t in (x, weight, bias, gamma, beta, addend)))
-    return _ConvBNAct.apply(x, weight, bias, gamma, beta, rmean, Bf.get("running_var"), family, geom, d["eps"], momentum,
-                            BN_ACT[activation], training, group, counter, may_fold, addend, few_values)
+    return _ConvBNAct.apply(x, weight, bias, gamma, beta, addend, (family, geom, rmean, Bf.get("running_var"), counter, d["eps"], momentum,
+                                                                   BN_ACT[activation], training, group, may_fold, few_values))
 
 
 def conv3d_supported(weight_shape, stride, padding, dilation, groups, transposed=False, output_padding=(0, 0, 0)):
@@ -1192,12 +1133,11 @@ def conv3d_supported(weight_shape, stride, padding, dilation, groups, transposed
 def conv3d(x, weight, bias=None, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1)):
     """F.conv3d on the HIP kernels for the (1,3,3) / (k,1,1) families (fp32, GPU)."""
     kind = conv3d_supported(tuple(weight.shape), stride, padding, dilation, 1)
-    if _WGRAD_DEFER is not None and weight.requires_grad and torch.is_grad_enabled():
-        _WGRAD_DEFER.used(weight)
+    _count_use(weight)
     if kind == "hw":
-        y = _Conv3dHW.apply(x, weight, stride[1], dilation[1], False)
+        y = _ConvRaw.apply(x, weight, None, "hw", (stride[1], dilation[1], False))
     elif kind == "d":
-        return _Conv3dD.apply(x, weight, stride[0], dilation[0], padding[0], False, bias)       # bias in the epilogue
+        return _ConvRaw.apply(x, weight, bias, "d", (stride[0], dilation[0], padding[0], False))       # bias in the epilogue
     else:
         raise NotImplementedError("conv3d: kernel %s stride %s padding %s dilation %s has no HIP kernel"
                                   % (tuple(weight.shape[2:]), stride, padding, dilation))
@@ -1207,12 +1147,11 @@ def conv3d(x, weight, bias=None, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(
 def conv_transpose3d(x, weight, bias=None, stride=(1, 2, 2), padding=(0, 1, 1), output_padding=(0, 1, 1)):
     """F.conv_transpose3d on the HIP kernels: (1,3,3) stride (1,2,2) or (3,1,1) stride (2,1,1), padding 1, output_padding 1."""
     kind = conv3d_supported(tuple(weight.shape), stride, padding, (1, 1, 1), 1, True, output_padding)
-    if _WGRAD_DEFER is not None and weight.requires_grad and torch.is_grad_enabled():
-        _WGRAD_DEFER.used(weight)
+    _count_use(weight)
     if kind == "hw":
-        y = _Conv3dHW.apply(x, weight, 2, 1, True)
+        y = _ConvRaw.apply(x, weight, None, "hw", (2, 1, True))
     elif kind == "d":
-        y = _Conv3dD.apply(x, weight, 2, 1, 1, True, None)
+        y = _ConvRaw.apply(x, weight, None, "d", (2, 1, 1, True))
     else:
         raise NotImplementedError("conv_transpose3d: kernel %s stride %s padding %s output_padding %s has no HIP kernel"
                                   % (tuple(weight.shape[2:]), stride, padding, output_padding))
@@ -1272,8 +1211,9 @@ def _depth_sum3(z0, z1, z2, y, scale=None, shift=None, act=0):
     _lib.check(rc, "ts_depth_sum3_fwd")
 
 
-def _hw3_forward(x, weight, bias=None, fold=None, act=0):
-    """Raw Conv3d 3x3x3, stride 1, padding 1 (+ bias); `fold`: see _hw_forward (applied by the depth sum's epilogue)."""
+def _hw3_forward(x, weight, geom=None, bias=None, fold=None, act=0, addend=None):
+    """Raw Conv3d 3x3x3, stride 1, padding 1 (+ bias): three (1,3,3) launches and ts_depth_sum3_fwd each way; `fold`: see _hw_forward
+    (applied by the depth sum's epilogue).  The family has one geometry: geom is not read."""
     _hw3_check(x, weight)
     x = x.contiguous()
     weight = weight if weight.is_contiguous() else weight.contiguous()
@@ -1323,27 +1263,74 @@ def _hw3_backward(x, weight, dy, geom, need_x, need_w):
     return dx, dw
 
 
-class _Conv3dK333(torch.autograd.Function):
-    """Raw Conv3d 3x3x3, stride 1, padding 1, no bias: three (1,3,3) launches and ts_depth_sum3_fwd each way (see _hw3_forward)."""
+# ---------------------------------------------------------------------------------------------- convolution families
+class _ConvFamily:
+    """One convolution family of the raw node (_ConvRaw) and of the fused node (_ConvBNAct):
+    forward(x, weight, geom, bias, fold, act, addend) -> (x as the kernels read it, y, saved_geom)
+    backward(x, weight, dy, saved_geom, need_x, need_w) -> (dx, dw)
+    cout(weight, geom): output channels, from the weight alone (what a BatchNorm fold is sized by before anything runs)
+    takes_addend: whether forward accepts a per-item plane added to the raw sum (first_layer_split).
+    `geom` is the caller's tuple, named by the family's forward; `saved_geom` is the forward's own record for its backward."""
+    __slots__ = ("forward", "backward", "cout", "takes_addend")
+
+    def __init__(self, forward, backward, cout, takes_addend=False):
+        self.forward, self.backward, self.cout, self.takes_addend = forward, backward, cout, takes_addend
+
+
+def _cout_dim0(weight, geom):
+    return weight.shape[0]
+
+
+def _cout_dim1(weight, geom):
+    return weight.shape[1]
+
+
+def _cout_by_geom(weight, geom):            # geom[-1]: transposed, weight [Cin, Cout, ...]
+    return weight.shape[1] if geom[-1] else weight.shape[0]
+
+
+_FAMILIES = {
+    "hw": _ConvFamily(_hw_forward, _hw_backward, _cout_by_geom, takes_addend=True),     # (1,3,3); geom (stride, dilation, transposed)
+    "d": _ConvFamily(_d_forward, _d_backward, _cout_by_geom),                           # (k,1,1); geom (stride, dilation, padding, transposed)
+    "dc": _ConvFamily(_dc_forward, _dc_backward, _cout_dim1),                           # ConvTranspose2d kernel 4, stride 2; geom None
+    "hw3": _ConvFamily(_hw3_forward, _hw3_backward, _cout_dim0),                        # 3x3x3 as three (1,3,3) slices; geom not read
+}
+
+
+class _ConvRaw(torch.autograd.Function):
+    """A raw convolution of any family (no scale / shift / activation; `bias`, where given, in the family's epilogue) as one autograd
+    node: the family's forward, its data / weight gradients, ts_channel_sum_fwd for the bias."""
 
     @staticmethod
-    def forward(ctx, x, weight):
-        x, y, ctx.geom = _hw3_forward(x, weight)
+    def forward(ctx, x, weight, bias, family, geom):
+        ctx.family = fam = _FAMILIES[family]
+        x, y, ctx.geom = fam.forward(x, weight, geom, bias, None, 0, None)
         ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
-        return _hw3_backward(x, weight, dy, ctx.geom, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        need_x, need_w, need_bias, _, _ = ctx.needs_input_grad
+        dx, dw = ctx.family.backward(x, weight, dy, ctx.geom, need_x, need_w)
+        gb = _channel_sum(dy) if (ctx.has_bias and need_bias) else None
+        return dx, dw, gb, None, None
+
+
+def conv_transpose2d_k4s2(x, weight, bias=None):
+    """F.conv_transpose2d(x, weight, bias, stride 2, padding 1) for 4x4 kernels on the HIP kernels (forward and backward; UNet.deconv2,
+    module.py:457)."""
+    return _ConvRaw.apply(x, weight, bias, "dc", None)
 
 
 def conv3d_k333(x, weight):
     """F.conv3d(x, weight, None, stride 1, padding 1) for a 3x3x3 kernel (groups 1, dilation 1, <= 64 output channels) on the (1,3,3)
     HIP kernels.  `layers.Conv3d` does not choose it by itself (conv3d_supported is unchanged): SPP3D does."""
-    return _Conv3dK333.apply(x, weight)
+    return _ConvRaw.apply(x, weight, None, "hw3", None)
 
 
+# ---------------------------------------------------------------------------------------------- SPP3D: pooling and expansion
 _SPP_MAX_LEVELS = 4            # csrc/spp3d.hip kMaxLevels
 
 
@@ -1734,7 +1721,7 @@ def first_layer_split(conv, left, volume):
     C = left.shape[1]
     w1, w2 = _SplitWeight.apply(conv._parameters["weight"], C)
     dil = conv.dilation[1]
-    lt = _Conv3dHW.apply(left.unsqueeze(2), w1, 1, dil, False)                  # [B, Cout, 1, H, W], raw
+    lt = _ConvRaw.apply(left.unsqueeze(2), w1, None, "hw", (1, dil, False))     # [B, Cout, 1, H, W], raw
     act = conv._fusable()
     if act is False or conv.stride[1] != 1:
         raise NotImplementedError("first_layer_split: a stride-1 (1,3,3) convolution + BatchNorm (+ SiLU / ReLU)")
@@ -2935,9 +2922,9 @@ def _decoder_check(up, skip, weight, bias):
 
 class _DecoderConv(torch.autograd.Function):
     """act(BatchNorm(conv3x3(cat([resize(up), skip], 1)) + bias)) as ONE autograd node: ts_decoder_conv_fwd reads `up` through the
-    align-corners resize and `skip` in place (no resized map, no concatenation), then ts_bn_train_fwd / ts_bn_apply_act_fwd over the raw
+    align-corners resize and `skip` in place (no resized map, no concatenation), then _bn_act_forward (single rank) over the raw
     convolution output; with may_fold the eval statistics go into the convolution's epilogue and nothing is kept.
-    backward: ts_bn_train_bwd (or the eval pair) -> ts_conv3d_hw_bwd_data over the concatenation's channels, whose [:, Cu:] slice is
+    backward: _bn_act_backward -> ts_conv3d_hw_bwd_data over the concatenation's channels, whose [:, Cu:] slice is
     grad_skip as a view and whose [:, :Cu] slice goes through ts_resize_bilinear_bwd -> ts_conv3d_hw_bwd_weight per source and per slice
     of <= 64 output channels (the resized map recomputed by ts_resize_bilinear_fwd) -> ts_channel_sum_fwd.  No atomics."""
 
@@ -2967,22 +2954,7 @@ class _DecoderConv(torch.autograd.Function):
             _decoder_launch(up, skip, w_l, scale, shift, y, act)
             return y
         _decoder_launch(up, skip, w_l, None, bias_d, y, 0)
-        N = H * W
-        L = _lib.lib()
-        out = torch.empty_like(y)
-        if training:
-            mean = torch.empty(Cout, device=y.device, dtype=torch.float32)
-            var = torch.empty_like(mean)
-            ws = torch.empty(_q("ts_bn_workspace_bytes", B, Cout, N), device=y.device, dtype=torch.uint8)
-            _lib.check(L.ts_bn_train_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(running_mean), _lib.ptr(running_var),
-                                         float(momentum), _lib.ptr(counter), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out), _lib.ptr(ws),
-                                         B, Cout, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act), _stream()),
-                       "ts_bn_train_fwd")
-        else:
-            mean, var = running_mean, running_var
-            _lib.check(L.ts_bn_apply_act_fwd(_lib.ptr(y), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(out),
-                                             B, Cout, N, y.stride(0), y.stride(1), out.stride(0), out.stride(1), float(eps), int(act),
-                                             _stream()), "ts_bn_apply_act_fwd")
+        out, mean, var, _ = _bn_act_forward(y, gamma, beta, running_mean, running_var, eps, momentum, act, training, None, counter)
         if needs:
             ctx.save_for_backward(up, skip, weight, y, mean, var, gamma, beta)
             ctx.meta = (True, float(eps), int(act), bool(training), bias is not None)
@@ -3004,21 +2976,7 @@ class _DecoderConv(torch.autograd.Function):
         dev = g.device
         ggamma = gbeta = None
         if has_bn:
-            s1 = torch.empty(Cout, device=dev, dtype=torch.float32)
-            s2 = torch.empty_like(s1)
-            ws = torch.empty(_q("ts_bn_workspace_bytes", B, Cout, N), device=dev, dtype=torch.uint8)
-            dy = torch.empty_like(y)
-            if training:
-                _lib.check(L.ts_bn_train_bwd(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                             _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy), _lib.ptr(ws), B, Cout, N, y.stride(0), y.stride(1),
-                                             g.stride(0), g.stride(1), eps, act, float(B * N), st), "ts_bn_train_bwd")
-            else:
-                _lib.check(L.ts_bn_act_bwd_reduce(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                                  _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(ws), B, Cout, N, y.stride(0), y.stride(1), g.stride(0),
-                                                  g.stride(1), eps, act, st), "ts_bn_act_bwd_reduce")
-                _lib.check(L.ts_bn_act_bwd_apply(_lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
-                                                 _lib.ptr(s1), _lib.ptr(s2), _lib.ptr(dy), B, Cout, N, y.stride(0), y.stride(1), g.stride(0),
-                                                 g.stride(1), eps, act, 0, float(B * N), st), "ts_bn_act_bwd_apply")
+            dy, s2, s1 = _bn_act_backward(y, g, mean, var, gamma, beta, eps, act, training, None, float(B * N), False)
             ggamma, gbeta = (s2 if need[4] else None), (s1 if need[5] else None)
         else:
             dy = g
@@ -3028,7 +2986,7 @@ class _DecoderConv(torch.autograd.Function):
         gup = gskip = dw = gbias = None
         if (need[0] and Cu) or need[1]:
             dcat = torch.empty((B, Cin, H, W), device=dev, dtype=torch.float32)
-            w_b = _layout(weight, 0, 1, flip=True)                   # [co][t][ci], taps flipped
+            w_b = _bwd_data_layout(weight, 1, False)
             _lib.check(L.ts_conv3d_hw_bwd_data(_lib.ptr(dy), _lib.ptr(w_b), _lib.ptr(dcat), B, Cin, Cout, 1, H, W, 1, 1, 0, Cout * N, N,
                                                Cin * N, N, st), "ts_conv3d_hw_bwd_data")
             if need[1]:

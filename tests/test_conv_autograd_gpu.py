@@ -110,6 +110,58 @@ def test_layers_use_the_hip_convolutions_on_gpu():
     assert odd(torch.zeros(1, 4, 3, 5, 5, device=dev)).shape == (1, 4, 3, 5, 5)
 
 
+def _graph_nodes(y):
+    """Names of the autograd nodes behind y, one per node, without the leaves' AccumulateGrad."""
+    names, seen, todo = [], set(), [y.grad_fn]
+    while todo:
+        fn = todo.pop()
+        if fn is not None and fn not in seen:
+            seen.add(fn)
+            names.append(type(fn).__name__)
+            todo += [f for f, _ in fn.next_functions]
+    return sorted(n for n in names if n != "AccumulateGrad")
+
+
+@pytest.mark.parametrize("family", ["hw", "d", "dc", "hw3"])
+def test_each_family_is_one_autograd_node(family):
+    """The raw public function of each family puts exactly ONE node of ours into the graph (functional._ConvRaw), the fused wrapper
+    exactly _ConvBNAct.  conv3d / conv_transpose3d of the (1,3,3) family and conv_transpose3d of the (k,1,1) family add their bias with
+    the framework's add behind the node (a view of the bias and the add: nothing else); the others carry it in the kernel's epilogue."""
+    import temporalstereo_amd.functional as TF
+    dev = _dev()
+    ours = "_ConvRawBackward"
+    outside = sorted([ours, "AddBackward0", "ViewBackward0"])
+    leaf = lambda seed, shape, scale=1.0: t(synth.normal(seed, "v", shape, scale), dev).requires_grad_(True)
+    if family == "hw":
+        x, w, wt, b = leaf(1, (1, 40, 2, 9, 15)), leaf(2, (64, 40, 1, 3, 3), 0.1), leaf(3, (40, 64, 1, 3, 3), 0.1), leaf(4, (64,))
+        s, p, d, tr = (1, 1, 1), (0, 1, 1), (1, 1, 1), ((1, 2, 2), (0, 1, 1), (0, 1, 1))
+        raw = [(TF.conv3d(x, w, None, s, p, d), [ours]), (TF.conv3d(x, w, b, s, p, d), outside),
+               (TF.conv_transpose3d(x, wt, None, *tr), [ours]), (TF.conv_transpose3d(x, wt, b, *tr), outside)]
+        geom = (1, 1, False)
+    elif family == "d":
+        x, w, wt, b = leaf(1, (2, 16, 5, 11, 23)), leaf(2, (32, 16, 3, 1, 1), 0.2), leaf(3, (16, 32, 3, 1, 1), 0.2), leaf(4, (32,))
+        s, p, d, tr = (1, 1, 1), (1, 0, 0), (1, 1, 1), ((2, 1, 1), (1, 0, 0), (1, 0, 0))
+        raw = [(TF.conv3d(x, w, None, s, p, d), [ours]), (TF.conv3d(x, w, b, s, p, d), [ours]),          # bias in the epilogue
+               (TF.conv_transpose3d(x, wt, None, *tr), [ours]), (TF.conv_transpose3d(x, wt, b, *tr), outside)]
+        geom = (1, 1, 1, False)
+    elif family == "dc":
+        x, w, b = leaf(1, (2, 8, 5, 7)), leaf(2, (8, 16, 4, 4), 0.1), leaf(4, (16,))
+        raw = [(TF.conv_transpose2d_k4s2(x, w), [ours]), (TF.conv_transpose2d_k4s2(x, w, b), [ours])]
+        geom = None
+    else:
+        x, w, b = leaf(1, (2, 8, 1, 5, 7)), leaf(2, (8, 8, 3, 3, 3), 0.1), leaf(4, (8,))
+        raw = [(TF.conv3d_k333(x, w), [ours])]
+        geom = (1, 1, False)
+    for y, want in raw:
+        assert _graph_nodes(y) == want
+    cout = b.numel()
+    bn = (torch.nn.BatchNorm2d(cout) if family == "dc" else torch.nn.BatchNorm3d(cout)).to(dev).train()
+    y = TF.conv_bn_act(x, w, b, bn, "SiLU", family, geom)
+    assert _graph_nodes(y) == ["_ConvBNActBackward"]
+    y.sum().backward()
+    assert all(v.grad is not None for v in (x, w, b, bn.weight, bn.bias))
+
+
 # ------------------------------------------------------------------------------- element stages
 def test_resize_add_silu_autograd():
     import temporalstereo_amd.functional as TF

@@ -424,6 +424,35 @@ def test_train_forward_updates_the_running_statistics():
             check("decoder_%s after two train forwards %s" % (tag, k), got[k], s64[k], stage_bar(dev, float(s64[k].abs().max())))
 
 
+def test_batchnorm_two_launch_form_equals_the_three_launch_form(monkeypatch):
+    """decoder_conv shares conv_bn_act's BatchNorm tail, so TS_BN_FUSED=0 reaches it too: the single-rank two-launch form
+    (ts_bn_train_{fwd,bwd}) and the three-launch form (statistics / apply, reduce / apply) take the same partials in the same fixed
+    order -- output, five gradients, running statistics and counter identical to the bit (the decoder's counterpart of the test of
+    this name in test_conv_autograd_gpu.py)."""
+    res = {}
+    old = _lib.lib().ts_bn_set_small_elems(0)           # (the layer is small enough for the one-launch form otherwise)
+    try:
+        for fused in (True, False):
+            monkeypatch.setattr(TF, "_BN_FUSED", fused)
+            bn = nn.BatchNorm2d(16)
+            with torch.no_grad():
+                bn.weight.copy_(torch.from_numpy(synth.uniform(7301, "gamma", (16,), 0.5, 1.5)))
+                bn.bias.copy_(torch.from_numpy(synth.normal(7301, "beta", (16,), 0.1)))
+            bn = bn.to(_dev()).train()
+            up = gpu(torch.from_numpy(synth.normal(7301, "up", (2, 8, 5, 7)))).requires_grad_(True)
+            skip = gpu(torch.from_numpy(synth.normal(7301, "skip", (2, 8, 9, 13)))).requires_grad_(True)
+            weight = gpu(torch.from_numpy(synth.normal(7301, "w", (16, 16, 3, 3), 0.1))).requires_grad_(True)
+            out = TF.decoder_conv(up, skip, weight, None, bn, "SiLU")
+            out.backward(gpu(torch.from_numpy(synth.normal(7301, "g", (2, 16, 9, 13)))))
+            res[fused] = [out.detach(), up.grad, skip.grad, weight.grad, bn.weight.grad, bn.bias.grad, bn.running_mean.clone(),
+                          bn.running_var.clone(), bn.num_batches_tracked.clone()]
+    finally:
+        _lib.lib().ts_bn_set_small_elems(old)
+    for a, b in zip(res[True], res[False]):
+        assert a is not None and torch.equal(a, b)
+    assert int(res[True][-1]) == 1
+
+
 def test_sync_batchnorm_routing(monkeypatch):
     """A SyncBatchNorm takes the kernels in eval mode and on a single rank; in train mode on more than one rank (a patched
     torch.distributed is enough) the module goes to _reference_forward and functional.decoder_conv refuses."""

@@ -68,3 +68,35 @@ def test_layers_constructor_contract():
         get_norm("nope", 4)
     y = c(torch.randn(2, 4, 3, 5, 5))
     assert y.shape == (2, 8, 3, 5, 5)
+
+
+def test_every_supported_convolution_has_a_family_entry():
+    """functional.conv3d_supported names the family that runs a layer and functional._FAMILIES holds what runs it: every name the
+    first can return is a key of the second, over the hyper-parameters the function branches on; every entry is complete; and an
+    entry's cout reads the weight's output-channel dimension (dimension 1 of a transposed weight, dimension 0 otherwise)."""
+    import itertools
+    from temporalstereo_amd import functional as TF
+    fam = TF._FAMILIES
+    assert set(fam) == {"hw", "d", "dc", "hw3"}
+    seen = set()
+    kernels = [(1, 3, 3), (1, 1, 1), (3, 1, 1), (5, 1, 1), (7, 1, 1), (3, 3, 3), (1, 3, 1)]
+    strides = [(1, 1, 1), (1, 2, 2), (2, 1, 1), (1, 2, 1), (2, 2, 2), (1, 3, 3)]
+    paddings = [(0, 0, 0), (0, 1, 1), (0, 2, 2), (1, 0, 0), (2, 0, 0), (1, 1, 1), (0, 1, 2)]
+    dilations = [(1, 1, 1), (1, 2, 2), (2, 1, 1), (1, 2, 1), (1, 3, 3)]
+    channels = [(8, 16), (64, 64), (65, 8), (8, 65)]
+    out_pads = [(0, 0, 0), (0, 1, 1), (1, 0, 0)]
+    for k, s, p, d, (c0, c1), groups in itertools.product(kernels, strides, paddings, dilations, channels, (1, 2)):
+        for transposed, op in [(False, (0, 0, 0))] + [(True, o) for o in out_pads]:
+            kind = TF.conv3d_supported((c0, c1) + k, s, p, d, groups, transposed, op)
+            assert kind is None or kind in fam, kind
+            seen.add(kind)
+    assert TF.conv3d_supported((8, 16, 3, 3), (1, 1), (1, 1), (1, 1), 1) is None           # not a 5-D weight
+    assert seen == {None, "hw", "d"}            # every branch of the function was reached ("dc" and "hw3" are chosen by their callers)
+    for name, f in fam.items():
+        assert callable(f.forward) and callable(f.backward) and callable(f.cout), name
+        assert f.takes_addend == (name == "hw"), name
+    w = torch.empty(5, 7, 1, 1, 1)
+    assert fam["dc"].cout(torch.empty(5, 7, 4, 4), None) == 7
+    assert fam["hw3"].cout(torch.empty(5, 7, 3, 3, 3), (1, 1, False)) == 5
+    assert fam["hw"].cout(w, (1, 1, False)) == 5 and fam["hw"].cout(w, (2, 1, True)) == 7
+    assert fam["d"].cout(w, (1, 1, 0, False)) == 5 and fam["d"].cout(w, (2, 1, 1, True)) == 7

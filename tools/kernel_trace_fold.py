@@ -5,7 +5,9 @@ the same kernels and grids become one group whose `times` is the number of group
   rocprofv3 --kernel-trace --output-format csv -d DIR1 -- python -m pytest tests/test_conv_gru_gpu.py::test_bits_do_not_depend_on_the_batch_grouping
   rocprofv3 --kernel-trace --output-format csv -d DIR2 -- python -m pytest tests/test_decoder_gpu.py::test_bits_do_not_depend_on_the_batch_grouping
   python tools/kernel_trace_fold.py --out profiles/hw3_grouping_kernel_trace.txt "<first test id>" DIR1 "<second test id>" DIR2
-Usage: python tools/kernel_trace_fold.py [--out FILE] [--keep NAME ...] [--group-at NAME] TITLE DIR [TITLE DIR ...]"""
+Usage: python tools/kernel_trace_fold.py [--out FILE] [--keep NAME ...] [--group-at NAME] [--counts] TITLE DIR [TITLE DIR ...]
+--counts: no launch order; one row per (kernel, workgroups, threads) with the number of its launches, sorted by name -- what two
+traces of the same work must agree in (profiles/conv_nodes_kernel_trace.txt; --keep "" keeps every kernel)."""
 import argparse
 import csv
 import glob
@@ -46,17 +48,22 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--keep", nargs="+", default=["gru_conv_kernel", "decoder_conv_kernel", "hw3::"])
     ap.add_argument("--group-at", default="weight_layout_kernel")
+    ap.add_argument("--counts", action="store_true")
     ap.add_argument("pairs", nargs="+", help="TITLE DIR [TITLE DIR ...]")
     args = ap.parse_args()
     lines = ["Kernel launches from `rocprofv3 --kernel-trace --output-format csv`, each trace collected in a run of its own, folded by",
              "tools/kernel_trace_fold.py: rows are in launch order; a launch of %s starts a group (one call), and consecutive" % args.group_at,
              "groups with the same kernels and grids are one group whose `times` is their number.  Kept: kernels named %s." % ", ".join(args.keep), ""]
+    if args.counts:
+        lines[1:3] = ["tools/kernel_trace_fold.py --counts: one row per (kernel, workgroups, threads); `times` is the number of its launches.  Kept: "
+                      "%s." % ("kernels named " + ", ".join(args.keep) if all(args.keep) else "every kernel")]
     for title, d in zip(args.pairs[0::2], args.pairs[1::2]):
         rows = launches(d)
         kept = [r for r in rows if any(k in r[0] for k in args.keep)]
         lines.append("%s: %d kernel launches in the trace, %d kept" % (title, len(rows), len(kept)))
         lines.append("  %5s  %-72s %12s %10s" % ("times", "kernel", "workgroups", "threads"))
-        for g, n in folded(kept, args.group_at):
+        groups = [([r], kept.count(r)) for r in sorted(set(kept))] if args.counts else folded(kept, args.group_at)
+        for g, n in groups:
             for name, wgs, wg in g:
                 lines.append("  %5d  %-72s %12d %10d" % (n, name, wgs, wg))
         lines.append("")
