@@ -693,6 +693,53 @@ int ts_decoder_conv_fwd(const float* up, const float* skip, const float* w_l, co
 int ts_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int h, int w, int H, int W, long long dy_bstride,
                            long long dy_cstride, long long dx_bstride, long long dx_cstride, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MemoryInvertedResidual: the encoder's inverted-residual block with the feature memory spliced into its input,
+ * backbone/TemporalStereo.py:165-218, fp32 throughout, no atomics (ABI 22).  Eval form, four launches:
+ *   e = silu(conv1x1(cat([memory, input[:, mc:]], 1)) * scale + shift)            ts_mbconv_expand_fwd
+ *   d = silu(depthwise3x3(e) * scale + shift), plane_sum = sum over the plane of d  ts_depthwise3x3_fwd
+ *   gate = sigmoid(w_expand . silu(w_reduce . (plane_sum * inv_hw) + b_reduce) + b_expand)      ts_se_gate_fwd
+ *   y = conv1x1(d * gate) * scale + shift + residual                              ts_mbconv_project_fwd
+ * Both 1x1 convolutions run on the f32-input MFMA with blocked sums (chains of 256 products, then a chain of blocks); an output's
+ * bits do not depend on the batch or the launch geometry.
+ * ts_mbconv_weight_layout     w [Cout][Cin] (the framework's 1x1 weight, contiguous) -> w_l, ts_mbconv_weight_bytes(Cin, Cout) bytes
+ *                             (0 outside 1..2048 each), 16-byte aligned: the transpose, zero padded; one launch.
+ * ts_mbconv_expand_fwd        input channels [0, mc) are read from memory [B,mc,H,W], channels [mc, C) from input [B,C,H,W] (its first mc
+ *                             channels are not read), each in place; the concatenation is not written.  memory NULL: input alone (the
+ *                             first frame; mc and the memory strides are ignored).  y [B,Cmid,H,W] OVERWRITTEN.
+ * ts_mbconv_project_fwd       x [B,Cmid,H,W] times gate [B][Cmid] (dense) per channel while it is read; the gated map is not written.
+ *                             residual and y [B,C,H,W]; y OVERWRITTEN (y may not alias residual unless they are the same elements).
+ * ts_depthwise3x3_fwd         x, y [B,C,H,W], w [C][9], stride 1, padding 1; act 0 none | 1 SiLU; flip 1 reverses the nine taps (with
+ *                             no epilogue: the input gradient of dy).  plane_sum [B][C] may be NULL; a plane's sum is taken in an order
+ *                             fixed by (H, W): the same bits whatever B and C are.  One workgroup per (b, c) plane.
+ * ts_depthwise3x3_bwd_weight  dw [C][9] OVERWRITTEN: dw[c][t] = sum over b, y, x of dy[b,c,y,x] x[b,c,y+t/3-1,x+t%3-1], fixed order.
+ * ts_se_gate_fwd              plane_sum, gate [B][Cmid]; w_reduce [Cr][Cmid], b_reduce [Cr], w_expand [Cmid][Cr], b_expand [Cmid], all
+ *                             dense; one launch of B x ceil(Cmid / 256) workgroups, each of which repeats the reduce step for its
+ *                             batch element and then computes 256 gate channels.  A reduce row is read in 16-byte pieces when
+ *                             Cmid % 4 == 0 and w_reduce is 16-byte aligned, an expand row when Cr % 4 == 0 and w_expand is: the
+ *                             summation order of a row depends on those three facts (not on B), and so do its bits.
+ * scale / shift (per output channel) may be NULL (1 / 0).  Tensors with strides have batch / channel strides in elements and dense
+ * planes.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, mc outside [0, C], an unknown activation or flip, overlapping
+ * strides), then C > 512, Cmid > 2048, Cr > 512, an axis >= 2^20, a plane >= 2^31 pixels, a grid that does not fit
+ * (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL), then the alignment of w_l (TS_ERR_ALIGN).
+ * ---------------------------------------------------------------------------------------- */
+size_t ts_mbconv_weight_bytes(int Cin, int Cout);
+int ts_mbconv_weight_layout(const float* w, float* w_l, int Cin, int Cout, void* stream);
+int ts_mbconv_expand_fwd(const float* memory, const float* input, const float* w_l, const float* scale, const float* shift, float* y,
+                         int B, int C, int mc, int Cmid, int H, int W, long long mem_bstride, long long mem_cstride,
+                         long long in_bstride, long long in_cstride, long long y_bstride, long long y_cstride, void* stream);
+int ts_mbconv_project_fwd(const float* x, const float* gate, const float* w_l, const float* scale, const float* shift,
+                          const float* residual, float* y, int B, int Cmid, int C, int H, int W, long long x_bstride,
+                          long long x_cstride, long long r_bstride, long long r_cstride, long long y_bstride, long long y_cstride,
+                          void* stream);
+int ts_depthwise3x3_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y, float* plane_sum, int B,
+                        int C, int H, int W, int act, int flip, long long x_bstride, long long x_cstride, long long y_bstride,
+                        long long y_cstride, void* stream);
+int ts_depthwise3x3_bwd_weight(const float* x, const float* dy, float* dw, int B, int C, int H, int W, long long x_bstride,
+                               long long x_cstride, long long dy_bstride, long long dy_cstride, void* stream);
+int ts_se_gate_fwd(const float* plane_sum, const float* w_reduce, const float* b_reduce, const float* w_expand, const float* b_expand,
+                   float* gate, int B, int Cmid, int Cr, float inv_hw, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

@@ -16,6 +16,22 @@ activations, wider layers -- takes `_reference_forward`, the reference's op sequ
 (norm='SyncBN', dist.sync_batchnorm, a converted backbone) in train mode on more than one rank: the kernel path computes per-rank
 statistics, the wrappers' conv_bn_act exchanges them; in eval mode and on a single rank a SyncBatchNorm takes the kernels.  The module
 takes one path for a given configuration whatever the plane size.
+
+MemoryInvertedResidual: the inverted-residual block of the encoder's last stages with the per-frame feature memory spliced into its
+input -- the reference's `_inverted_residual_forward` (architecture/modeling/backbone/TemporalStereo.py:183-218) -- and `block_forward`,
+its `_block_forward` (:165-180).
+
+    mc = int(C * memory_percent);  x = cat([memory if given else input[:, :mc], input[:, mc:]], 1)
+    x = act1(bn1(conv_pw(x)));  x = act2(bn2(conv_dw(x)));  x = se(x);  x = bn3(conv_pwl(x))
+    return input + x, input[:, :mc]
+
+Routing, one path per configuration whatever the plane size: fp32 GPU tensors under the 'hip' backend, a recognised block inside the
+kernels' envelope (functional.mbconv_supported), eval mode and nothing that needs a gradient -> functional.mbconv_eval, four launches
+(csrc/mbconv.hip).  The same tensors in train mode or with a gradient needed -> `_train_forward`: the reference's op sequence with the
+splice on temporal.exchange_feature_memory and the depthwise convolution on functional.depthwise_conv3x3; the 1x1 convolutions, the
+BatchNorms and the squeeze-excite step stay framework ops there.  Everything else -- CPU tensors, other dtypes,
+set_conv_backend('torch'), drop_path_rate > 0 in train mode, a block `from_block` did not recognise -- takes `_reference_forward`, the
+reference's statements on the block's own submodules.
 """
 import torch
 import torch.nn as nn
@@ -139,3 +155,208 @@ class FeatureDecoder(nn.Module):
             up = self._layer(seq[1], None, self._layer(seq[0], up, skip))
             outs.append(up)
         return outs[::-1]
+
+
+# ------------------------------------------------------------------------------------------------------- the encoder's memory MBConv block
+def _make_divisible(v, divisor=8):
+    """The EfficientNet family's channel rounding: the nearest multiple of `divisor`, at least `divisor`, never more than 10 % below v."""
+    new = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return new + divisor if new < 0.9 * v else new
+
+
+def _drop_path(x, rate, training):
+    """Stochastic depth per sample: in train mode a sample's branch is dropped with probability `rate`, the kept ones scaled by 1 / (1 - rate)."""
+    if rate == 0.0 or not training:
+        return x
+    keep = 1.0 - rate
+    mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+    return x.div(keep) * mask
+
+
+class SqueezeExcite(nn.Module):
+    """x * gate(conv_expand(act1(conv_reduce(mean_hw(x))))), both convolutions 1x1 with bias."""
+
+    def __init__(self, chs, se_chs):
+        super().__init__()
+        self.conv_reduce = nn.Conv2d(chs, se_chs, 1, bias=True)
+        self.act1 = nn.SiLU(inplace=True)
+        self.conv_expand = nn.Conv2d(se_chs, chs, 1, bias=True)
+        self.gate = nn.Sigmoid()
+
+    def forward(self, x):
+        x_se = x.mean((2, 3), keepdim=True)
+        x_se = self.conv_expand(self.act1(self.conv_reduce(x_se)))
+        return x * self.gate(x_se)
+
+
+_MBCONV_PARTS = ("conv_pw", "bn1", "act1", "conv_dw", "bn2", "act2", "se", "conv_pwl", "bn3")
+
+
+class MemoryInvertedResidual(nn.Module):
+    """The inverted-residual (MBConv) block with a residual -- stride 1, equal input and output width -- whose first
+    mc = int(in_chs * memory_percent) input channels are replaced by the previous frame's (`memory`), and whose own first mc input
+    channels are returned as the next frame's memory.
+
+    Attributes and state-dict keys are those of the block the reference takes from its pinned timm 0.4.12 (`InvertedResidual` of
+    efficientnetv2_rw_s): conv_pw.weight, bn1.*, conv_dw.weight, bn2.*, se.conv_reduce.{weight,bias}, se.conv_expand.{weight,bias},
+    conv_pwl.weight, bn3.*; has_residual, drop_path_rate.  timm is not a dependency of this package and was not at hand when this was
+    written: the list is taken as given from the reference's use of the block (backbone/TemporalStereo.py:199-216 names every
+    attribute but the squeeze-excite step's own)."""
+
+    def __init__(self, in_chs, exp_ratio=4.0, se_ratio=0.25, memory_percent=0.25, mid_chs=None, se_chs=None, drop_path_rate=0.0):
+        super().__init__()
+        mid_chs = int(mid_chs) if mid_chs else _make_divisible(in_chs * exp_ratio)
+        se_chs = int(se_chs) if se_chs else _make_divisible(in_chs * se_ratio, 1)
+        self.conv_pw = nn.Conv2d(in_chs, mid_chs, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(mid_chs)
+        self.act1 = nn.SiLU(inplace=True)
+        self.conv_dw = nn.Conv2d(mid_chs, mid_chs, 3, 1, 1, groups=mid_chs, bias=False)
+        self.bn2 = nn.BatchNorm2d(mid_chs)
+        self.act2 = nn.SiLU(inplace=True)
+        self.se = SqueezeExcite(mid_chs, se_chs)
+        self.conv_pwl = nn.Conv2d(mid_chs, in_chs, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(in_chs)
+        self.has_residual = True
+        self.drop_path_rate = float(drop_path_rate)
+        self.memory_percent = float(memory_percent)
+        self._recognised = True
+
+    @classmethod
+    def from_block(cls, block, memory_percent):
+        """Adopts an existing inverted-residual block by its attributes: the SAME submodule objects (so the same Parameters and buffers;
+        nothing is copied), `has_residual` required.  The kernels are taken only when the block is recognised (`_recognise`); any other
+        block keeps running its own submodules in the reference's order.  In the reference:
+        `MemoryInvertedResidual.from_block(b, self.memory_percent)` over the residual members of block1..block4."""
+        for name in _MBCONV_PARTS:
+            if not hasattr(block, name):
+                raise ValueError("MemoryInvertedResidual.from_block: the block has no '%s'" % name)
+        if not getattr(block, "has_residual", False):
+            raise ValueError("MemoryInvertedResidual.from_block: a block with a residual (stride 1, equal widths) expected")
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        for name in _MBCONV_PARTS:
+            setattr(self, name, getattr(block, name))
+        self.has_residual = True
+        self.drop_path_rate = float(getattr(block, "drop_path_rate", 0.0))
+        self.memory_percent = float(memory_percent)
+        self._recognised = self._recognise()
+        self.train(block.training)
+        return self
+
+    def _recognise(self):
+        """True when the submodules are exactly what csrc/mbconv.hip computes."""
+        def conv(m, cin, cout, k, groups, bias):
+            return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.in_channels == cin and m.out_channels == cout and \
+                m.kernel_size == (k, k) and m.stride == (1, 1) and m.padding == (k // 2, k // 2) and m.dilation == (1, 1) and \
+                m.groups == groups and (m.bias is not None) == bias and m.padding_mode == "zeros"
+
+        def norm(m, c):
+            return type(m) in (nn.BatchNorm2d, nn.SyncBatchNorm) and m.num_features == c and m.affine and m.track_running_stats
+
+        pw, se = self.conv_pw, self.se
+        if not isinstance(pw, nn.Conv2d):
+            return False
+        C, Cmid = pw.in_channels, pw.out_channels
+        if not (conv(pw, C, Cmid, 1, 1, False) and conv(self.conv_dw, Cmid, Cmid, 3, Cmid, False) and conv(self.conv_pwl, Cmid, C, 1, 1, False)):
+            return False
+        if not (norm(self.bn1, Cmid) and norm(self.bn2, Cmid) and norm(self.bn3, C)):
+            return False
+        if not (isinstance(self.act1, nn.SiLU) and isinstance(self.act2, nn.SiLU)):
+            return False
+        if not all(hasattr(se, n) for n in ("conv_reduce", "act1", "conv_expand", "gate")) or not isinstance(se.conv_reduce, nn.Conv2d):
+            return False
+        Cr = se.conv_reduce.out_channels
+        gate = se.gate
+        return conv(se.conv_reduce, Cmid, Cr, 1, 1, True) and conv(se.conv_expand, Cr, Cmid, 1, 1, True) and isinstance(se.act1, nn.SiLU) and \
+            (isinstance(gate, nn.Sigmoid) or getattr(gate, "__name__", None) == "sigmoid")
+
+    def _route(self, input, memory):
+        """'kernels' | 'train' | 'reference' (the module's docstring)."""
+        from . import functional as TF
+        if not self._recognised or input.dim() != 4 or not layers._hip_conv(input) or (memory is not None and not layers._hip_conv(memory)):
+            return "reference"
+        norms = (self.bn1, self.bn2, self.bn3)
+        training = self.training or any(bn.training for bn in norms)
+        if training and self.drop_path_rate > 0:
+            return "reference"
+        params = [p for p in self.parameters()]
+        if any(not (p.is_cuda and p.dtype == torch.float32) for p in params) or any(TF.bn_exchanges(bn) for bn in norms):
+            return "reference"
+        if not TF.mbconv_supported(self.conv_pw.in_channels, self.conv_pw.out_channels, self.se.conv_reduce.out_channels):
+            return "reference"
+        if training or (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [input, memory] + params)):
+            return "train"
+        return "kernels"
+
+    def _reference_forward(self, input, memory, mc):
+        input1, input2 = input[:, :mc], input[:, mc:]
+        x = torch.cat([input1 if memory is None else memory, input2], dim=1)
+        x = self.act1(self.bn1(self.conv_pw(x)))
+        x = self.act2(self.bn2(self.conv_dw(x)))
+        x = self.se(x)
+        x = self.bn3(self.conv_pwl(x))
+        if self.drop_path_rate > 0:
+            x = _drop_path(x, self.drop_path_rate, self.training)
+        return input + x, input1
+
+    def _train_forward(self, input, memory, memory_percent):
+        from . import functional as TF
+        from . import temporal
+        x, new_memory = temporal.exchange_feature_memory(input, memory, memory_percent)
+        x = self.act1(self.bn1(self.conv_pw(x)))
+        x = self.act2(self.bn2(TF.depthwise_conv3x3(x, self.conv_dw.weight, self.conv_dw.bias)))
+        x = self.se(x)
+        x = self.bn3(self.conv_pwl(x))
+        return input + x, new_memory
+
+    def _kernel_forward(self, input, memory, mc, return_stages=False):
+        from . import functional as TF
+        se = self.se
+        res = TF.mbconv_eval(input, memory, self.conv_pw.weight, TF._bn_eval_fold(self.bn1), self.conv_dw.weight, TF._bn_eval_fold(self.bn2),
+                             se.conv_reduce.weight, se.conv_reduce.bias, se.conv_expand.weight, se.conv_expand.bias, self.conv_pwl.weight,
+                             TF._bn_eval_fold(self.bn3), return_stages=return_stages)
+        if return_stages:
+            return res[0], input[:, :mc], dict(act1=res[1], act2=res[2], gate=res[3])
+        return res, input[:, :mc]
+
+    def _forward(self, input, memory, memory_percent):
+        ic = input.shape[1]
+        mc = int(ic * memory_percent)
+        if memory is not None and memory.shape[1] != mc:
+            raise AssertionError("input shape: {}; memory shape: {}!".format(input.shape, memory.shape))
+        if memory is not None and (memory.dim() != input.dim() or memory.shape[0] != input.shape[0] or memory.shape[2:] != input.shape[2:]):
+            # the reference's torch.cat refuses these; the kernels take batch and plane from the input alone
+            raise RuntimeError("MemoryInvertedResidual: memory {} does not match the batch and plane of input {}".format(
+                tuple(memory.shape), tuple(input.shape)))
+        if mc == 0:
+            memory = None                   # an empty memory: the block sees its own input
+        route = self._route(input, memory)
+        if route == "kernels":
+            return self._kernel_forward(input, memory, mc)
+        if route == "train":
+            return self._train_forward(input, memory, memory_percent)
+        return self._reference_forward(input, memory, mc)
+
+    def forward(self, input, memory=None):
+        """-> (output, new_memory): new_memory is the view input[:, :mc]."""
+        return self._forward(input, memory, self.memory_percent)
+
+
+def block_forward(block, input, memory_percent=0.0, memories=None, memory_idx=0):
+    """The reference's `_block_forward` (backbone/TemporalStereo.py:165-180): the walk over a stage -- a sequential of sequentials.  Every
+    MemoryInvertedResidual goes through the memory path with memories[memory_idx] (None on the first frame) and appends its new memory;
+    every other member is called.  -> (x, out_memories, memory_idx)."""
+    out_memories = []
+    for sequential in block:
+        for member in sequential:
+            if isinstance(member, MemoryInvertedResidual) and member.has_residual:
+                if memory_percent > 0:
+                    m = memories[memory_idx] if memories is not None and len(memories) > 0 else None
+                    input, m = member._forward(input, m, memory_percent)
+                    out_memories.append(m)
+                    memory_idx += 1
+                else:
+                    input = member._forward(input, None, 0.0)[0]
+            else:
+                input = member(input)
+    return input, out_memories, memory_idx

@@ -117,6 +117,8 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_conv_gru_weight_layout),  TS_PLAN_OP(ts_conv_gru_gates_fwd),      TS_PLAN_OP(ts_conv_gru_out_fwd),
     TS_PLAN_OP(ts_conv_gru_gate_bwd_a),     TS_PLAN_OP(ts_conv_gru_gate_bwd_b),     TS_PLAN_OP(ts_conv_gru_grad_sum),
     TS_PLAN_OP(ts_decoder_weight_layout),   TS_PLAN_OP(ts_decoder_conv_fwd),        TS_PLAN_OP(ts_resize_bilinear_bwd),
+    TS_PLAN_OP(ts_mbconv_weight_layout),    TS_PLAN_OP(ts_mbconv_expand_fwd),       TS_PLAN_OP(ts_mbconv_project_fwd),
+    TS_PLAN_OP(ts_depthwise3x3_fwd),        TS_PLAN_OP(ts_depthwise3x3_bwd_weight), TS_PLAN_OP(ts_se_gate_fwd),
 };
 
 struct Call {

@@ -3051,3 +3051,167 @@ def decoder_conv(up, skip, weight, bias=None, bn=None, activation=None):
     if not grad:
         tensors = tuple(t.detach() if t is not None else None for t in tensors)
     return _DecoderConv.apply(*tensors, rmean, rvar, eps, momentum, act, training, counter, not grad, bn is not None)
+
+
+# ---- MemoryInvertedResidual (reference: backbone/TemporalStereo.py:165-218) ------------------------------------------------------------
+MBCONV_MAX_CHANNELS = 512         # the kernel path's envelope (csrc/mbconv.hip): the block's width C and the squeeze width Cr ...
+MBCONV_MAX_MID = 2048             # ... and the expanded width Cmid
+
+
+def mbconv_supported(C, Cmid, Cr):
+    return 1 <= C <= MBCONV_MAX_CHANNELS and 1 <= Cmid <= MBCONV_MAX_MID and 1 <= Cr <= MBCONV_MAX_CHANNELS
+
+
+def _mbconv_weight_make(weight, out=None):
+    Cout, Cin = weight.shape[0], weight.shape[1]
+    if out is None:
+        nbytes = _q("ts_mbconv_weight_bytes", Cin, Cout)
+        if not nbytes:
+            raise RuntimeError("mbconv: a 1x1 weight of %d input / %d output channels is outside the kernel path (1..%d each)"
+                               % (Cin, Cout, MBCONV_MAX_MID))
+        out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
+    _lib.check(_lib.lib().ts_mbconv_weight_layout(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, _stream()), "ts_mbconv_weight_layout")
+    return out
+
+
+def _mbconv_weight(weight):
+    """The pointwise kernels' order of a [Cout, Cin, 1, 1] weight (ts_mbconv_weight_layout); inside a `WeightLayouts` context a leaf is
+    laid out once per step and refreshed with the others, as `_decoder_weight`."""
+    if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
+        return _LAYOUTS.get_custom(weight, "mbconv", _mbconv_weight_make)
+    return _mbconv_weight_make(_lib.contiguous(weight.detach()))
+
+
+def _bn_eval_fold(bn, bias=None):
+    """(scale, shift) of an eval-mode BatchNorm behind a convolution: `_decoder_fold`'s entry (a `BNFolds` context's when one is open)."""
+    return _decoder_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bias, bn.eps, bn.num_features)
+
+
+def _depthwise_launch(x, w9, scale, shift, y, plane_sum, act, flip):
+    B, C, H, W = x.shape
+    rc = _lib.lib().ts_depthwise3x3_fwd(_lib.ptr(x), _lib.ptr(w9), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), _lib.ptr(plane_sum), B, C, H,
+                                        W, int(act), int(flip), x.stride(0), x.stride(1), y.stride(0), y.stride(1), _stream())
+    _lib.check(rc, "ts_depthwise3x3_fwd")
+
+
+def _mbconv_check(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_expand, b_expand, w_pwl, fold3, out):
+    """Shapes of everything mbconv_eval hands to the kernels, before any launch: they take B, H and W from `inp` alone."""
+    if inp.dim() != 4 or min(inp.shape) < 1:
+        raise ValueError("mbconv_eval: input must be a non-empty [B,C,H,W], got %s" % (tuple(inp.shape),))
+    B, C, H, W = inp.shape
+    if w_pw.dim() != 4 or tuple(w_pw.shape[1:]) != (C, 1, 1):
+        raise ValueError("mbconv_eval: conv_pw weight must be [Cmid, %d, 1, 1], got %s" % (C, tuple(w_pw.shape)))
+    Cmid = w_pw.shape[0]
+    if w_reduce.dim() != 4 or tuple(w_reduce.shape[1:]) != (Cmid, 1, 1):
+        raise ValueError("mbconv_eval: conv_reduce weight must be [Cr, %d, 1, 1], got %s" % (Cmid, tuple(w_reduce.shape)))
+    Cr = w_reduce.shape[0]
+    for name, t, shape in (("conv_dw weight", w_dw, (Cmid, 1, 3, 3)), ("conv_reduce bias", b_reduce, (Cr,)),
+                           ("conv_expand weight", w_expand, (Cmid, Cr, 1, 1)), ("conv_expand bias", b_expand, (Cmid,)),
+                           ("conv_pwl weight", w_pwl, (C, Cmid, 1, 1))):
+        if t is None or tuple(t.shape) != shape:
+            raise ValueError("mbconv_eval: %s must be %s, got %s" % (name, list(shape), None if t is None else tuple(t.shape)))
+    for name, fold, n in (("bn1", fold1, Cmid), ("bn2", fold2, Cmid), ("bn3", fold3, C)):
+        if len(fold) != 2 or any(v is None or v.dim() != 1 or v.numel() < n or not v.is_contiguous() for v in fold):
+            raise ValueError("mbconv_eval: the %s fold must be a (scale, shift) pair of dense vectors of at least %d values" % (name, n))
+    if not mbconv_supported(C, Cmid, Cr):
+        raise RuntimeError("mbconv_eval: C = %d, Cmid = %d, Cr = %d are outside the kernel path (C, Cr <= %d, Cmid <= %d)"
+                           % (C, Cmid, Cr, MBCONV_MAX_CHANNELS, MBCONV_MAX_MID))
+    if memory is not None:
+        if memory.dim() != 4 or memory.shape[0] != B or tuple(memory.shape[2:]) != (H, W) or not 1 <= memory.shape[1] <= C:
+            raise ValueError("mbconv_eval: memory must be [%d, mc <= %d, %d, %d] as the input is %s, got %s"
+                             % (B, C, H, W, tuple(inp.shape), tuple(memory.shape)))
+    if out is not None:
+        if tuple(out.shape) != (B, C, H, W) or out.stride(3) != 1 or out.stride(2) != W or out.stride(1) < H * W or \
+                (B > 1 and out.stride(0) < out.stride(1) * (C - 1) + H * W):
+            raise ValueError("mbconv_eval: out must be [%d, %d, %d, %d] with dense planes and strides that do not overlap, got %s strides %s"
+                             % (B, C, H, W, tuple(out.shape), tuple(out.stride())))
+
+
+def mbconv_eval(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_expand, b_expand, w_pwl, fold3, out=None,
+                return_stages=False):
+    """The eval form of one MemoryInvertedResidual block as FOUR launches (csrc/mbconv.hip): expand (reads [memory | inp[:, mc:]] in
+    place), depthwise (+ the plane sums), gate, project (reads the gated map, adds `inp`).  fold1..3: (scale, shift) of the three
+    BatchNorms (`_bn_eval_fold`); the weights as the framework holds them; memory [B,mc,H,W] or None.  Nothing here asks for a
+    gradient: the caller has checked.  Outside `WeightLayouts` / `BNFolds` contexts the two weight layouts and three folds are launches
+    of their own.  -> the block's output [B,C,H,W] (written into `out` when given); with return_stages also (after act1, after act2,
+    gate)."""
+    _mbconv_check(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_expand, b_expand, w_pwl, fold3, out)
+    _require_gpu(inp, memory, w_pw, w_dw, w_reduce, b_reduce, w_expand, b_expand, w_pwl, out, *fold1, *fold2, *fold3)
+    inp = _plane_view(inp)
+    B, C, H, W = inp.shape
+    Cmid, Cr = w_pw.shape[0], w_reduce.shape[0]
+    mc = 0
+    mb = mcs = 0
+    if memory is not None:
+        memory = _plane_view(memory)
+        mc = memory.shape[1]
+        mb, mcs = memory.stride(0), memory.stride(1)
+    dev = inp.device
+    L, st = _lib.lib(), _stream()
+    e = torch.empty((B, Cmid, H, W), device=dev, dtype=torch.float32)
+    rc = L.ts_mbconv_expand_fwd(_lib.ptr(memory), _lib.ptr(inp), _lib.ptr(_mbconv_weight(w_pw)), _lib.ptr(fold1[0]), _lib.ptr(fold1[1]),
+                                _lib.ptr(e), B, C, mc, Cmid, H, W, mb, mcs, inp.stride(0), inp.stride(1), Cmid * H * W, H * W, st)
+    _lib.check(rc, "ts_mbconv_expand_fwd")
+    d = torch.empty_like(e)
+    sums = torch.empty((B, Cmid), device=dev, dtype=torch.float32)
+    _depthwise_launch(e, _lib.contiguous(w_dw.detach()), fold2[0], fold2[1], d, sums, 1, 0)
+    gate = torch.empty((B, Cmid), device=dev, dtype=torch.float32)
+    rc = L.ts_se_gate_fwd(_lib.ptr(sums), _lib.ptr(_lib.contiguous(w_reduce.detach())), _lib.ptr(b_reduce.detach()),
+                          _lib.ptr(_lib.contiguous(w_expand.detach())), _lib.ptr(b_expand.detach()), _lib.ptr(gate), B, Cmid, Cr,
+                          1.0 / float(H * W), st)
+    _lib.check(rc, "ts_se_gate_fwd")
+    y = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if out is None else out
+    rc = L.ts_mbconv_project_fwd(_lib.ptr(d), _lib.ptr(gate), _lib.ptr(_mbconv_weight(w_pwl)), _lib.ptr(fold3[0]), _lib.ptr(fold3[1]),
+                                 _lib.ptr(inp), _lib.ptr(y), B, Cmid, C, H, W, Cmid * H * W, H * W, inp.stride(0), inp.stride(1), y.stride(0),
+                                 y.stride(1), st)
+    _lib.check(rc, "ts_mbconv_project_fwd")
+    return (y, e, d, gate) if return_stages else y
+
+
+class _Depthwise3x3(torch.autograd.Function):
+    """conv2d(x, weight [C,1,3,3], bias, stride 1, padding 1, groups C) on csrc/mbconv.hip: ts_depthwise3x3_fwd (the bias is its
+    epilogue's shift); backward: the same entry with the taps flipped over dy (input gradient), ts_depthwise3x3_bwd_weight, and
+    ts_channel_sum_fwd for the bias.  No atomics."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        _require_gpu(x, weight, bias)
+        if x.dim() != 4 or weight.dim() != 4 or tuple(weight.shape) != (x.shape[1], 1, 3, 3):
+            raise ValueError("depthwise_conv3x3: x [B,C,H,W] and weight [C,1,3,3] expected, got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+        if bias is not None and tuple(bias.shape) != (x.shape[1],):
+            raise ValueError("depthwise_conv3x3: bias must be [%d], got %s" % (x.shape[1], tuple(bias.shape)))
+        if min(x.shape) < 1:
+            raise ValueError("depthwise_conv3x3: empty input")
+        x = _plane_view(x)
+        w9 = _lib.contiguous(weight.detach())
+        y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        _depthwise_launch(x, w9, None, _lib.contiguous(bias.detach()) if bias is not None else None, y, None, 0, 0)
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = _plane_view(g)
+        B, C, H, W = g.shape
+        gx = gw = gb = None
+        if need[0]:
+            gx = torch.empty((B, C, H, W), device=g.device, dtype=torch.float32)
+            _depthwise_launch(g, _lib.contiguous(weight.detach()), None, None, gx, None, 0, 1)
+        if need[1]:
+            gw = torch.empty(weight.shape, device=g.device, dtype=torch.float32)
+            rc = _lib.lib().ts_depthwise3x3_bwd_weight(_lib.ptr(x), _lib.ptr(g), _lib.ptr(gw), B, C, H, W, x.stride(0), x.stride(1),
+                                                       g.stride(0), g.stride(1), _stream())
+            _lib.check(rc, "ts_depthwise3x3_bwd_weight")
+        if ctx.has_bias and need[2]:
+            gb = _channel_sum(g)
+        return gx, gw, gb
+
+
+def depthwise_conv3x3(x, weight, bias=None):
+    """F.conv2d(x, weight, bias, stride=1, padding=1, groups=C) for a [C,1,3,3] weight on the HIP kernels (fp32 GPU tensors; any plane),
+    with gradients for x, weight and bias."""
+    return _Depthwise3x3.apply(x, weight, bias)

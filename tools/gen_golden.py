@@ -2062,6 +2062,135 @@ def decoder_cases(M):
     print("\n".join(lines))
 
 
+def reference_mbconv(block_class):
+    """The reference's OWN `_inverted_residual_forward` and `_block_forward` (architecture/modeling/backbone/TemporalStereo.py:165-218),
+    compiled from its file's syntax tree -- the module imports timm at the top, which this image does not have.  The name
+    `InvertedResidual` (the isinstance test of `_block_forward`) is bound to `block_class`, `drop_path` to a function that must not be
+    called (the stand-in's drop_path_rate is 0)."""
+    import ast
+    path = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "modeling", "backbone", "TemporalStereo.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    names = ("_block_forward", "_inverted_residual_forward")
+    funcs = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in names]
+    assert sorted(f.name for f in funcs) == sorted(names)
+
+    def drop_path(*a, **k):
+        raise AssertionError("drop_path must not be reached: the stand-in's drop_path_rate is 0")
+    ns = {"torch": torch, "InvertedResidual": block_class, "drop_path": drop_path}
+    exec(compile(ast.fix_missing_locations(ast.Module(body=funcs, type_ignores=[])), path, "exec"), ns)
+    return ns["_inverted_residual_forward"], ns["_block_forward"]
+
+
+def mbconv_cases(M):
+    """tests/golden/mbconv_*.npz: the reference's own memory-block function and stage walk on tests/mbconv_ref.py's stand-in block, on
+    the CPU, in fp32 and fp64, train mode and eval mode; dev_* = how far its fp32 run lies from its fp64 run."""
+    import mbconv_ref as R
+    block_fwd, stage_fwd = reference_mbconv(R.StandInBlock)
+    lines = ["mbconv_*.npz: tools/gen_golden.py --only-mbconv, numpy %s, torch %s CPU -- the reference's own _inverted_residual_forward and" % (np.__version__, torch.__version__),
+             "_block_forward (architecture/modeling/backbone/TemporalStereo.py:165-218, compiled from the file's syntax tree with the name",
+             "InvertedResidual bound to tests/mbconv_ref.py's StandInBlock -- timm, where the reference's block comes from, is not part of its",
+             "checkout -- and drop_path to a function that raises) on seeded inputs in float32 and in float64, in train mode and in eval mode,",
+             "with the backward of seeded cotangents of every frame's output.  A case is a stage nn.Sequential(nn.Sequential(block, ...)) walked",
+             "by _block_forward once per frame, memory_percent 1/4; a single-block, single-frame case is ALSO run through",
+             "_inverted_residual_forward directly and the two runs are asserted identical.",
+             "Inputs, all kept as their seed (tests/mbconv_ref.py fixture_state / fixture_inputs / fixture_memory / fixture_cotangents draw them",
+             "again): convolution weights N(0,1) * 2 / sqrt(fan-in), convolution biases N(0, 0.1), BatchNorm weight U(0.5, 1.5) and bias N(0, 0.1),",
+             "running mean N(0, 0.1), running variance U(0.5, 1.5), inputs and memory N(0,1), cotangents k / 8 with k an integer in [-8, 8].",
+             "Stored: seed, keys and key_shapes (the stage's state-dict keys in order, shapes padded with -1), and per mode m in (train, eval) the",
+             "deviations of EVERY output, stage and gradient over the WHOLE arrays: dev_<m>_f<frame>_out, dev_<m>_f<frame>_b<block>_<act1|act2|gate>",
+             "= max |fp32 run - fp64 run|, max_<m>_<...> = max |.| of the fp64 run, rel_grad_<m>_<in_f<frame>|memory|parameter key> = relative L2",
+             "of the fp32 run's gradient against the fp64 run's.  Arrays (fp32 run; one of more than %d elements at %d seeded flat positions," % (R.SAMPLE, R.SAMPLE),
+             "mbconv_ref.sample): those mbconv_ref.stored names -- train mode the outputs and the gradients of inputs, memory and the three",
+             "convolution weights; eval mode the outputs, act2 and the gate.  The rest would take the four files past 1 MB; the tests compare",
+             "everything against the fp64 restatement, which the generator asserts equal to the reference's fp64 run to 1e-10."]
+    total = 0
+    for tag in R.TAGS:
+        c = R.CASES[tag]
+        seed = synth.SEED0 + 15000 + 1000 * ord(tag)
+
+        def run(dt, training):
+            net = R.stand_in_stage(tag)
+            keys = list(net.state_dict().keys())
+            shapes = [tuple(v.shape) for v in net.state_dict().values()]
+            res = net.load_state_dict(R.fixture_state(seed, tag), strict=True)
+            assert not res.missing_keys and not res.unexpected_keys
+            net = net.to(dt).train(training)
+            ins = R.fixture_inputs(seed, tag, dt)
+            memory = R.fixture_memory(seed, tag, dt)
+            for t in ins + ([memory] if memory is not None else []):
+                t.requires_grad_(True)
+            got, hooks = {}, []
+            at = {"f": 0}
+            for i, blk in enumerate(net[0]):
+                for name, mod in (("act1", blk.act1), ("act2", blk.act2), ("gate", blk.se.gate)):
+                    hooks.append(mod.register_forward_hook(
+                        lambda m, a, o, i=i, name=name: got.__setitem__("f%d_b%d_%s" % (at["f"], i, name), o.detach().clone().flatten(1) if name == "gate" else o.detach().clone())))
+            memories = [memory] if memory is not None else None
+            outs = []
+            for f, x in enumerate(ins):
+                at["f"] = f
+                out, memories, idx = stage_fwd(net, x, R.MEMORY_PERCENT, memories, 0)
+                assert idx == c["blocks"] and len(memories) == c["blocks"]
+                for m in memories:
+                    assert m.shape[1] == int(c["C"] * R.MEMORY_PERCENT)
+                outs.append(out)
+                got["f%d_out" % f] = out.detach()
+            if c["blocks"] == 1 and c["frames"] == 1:            # the function itself, without the walk
+                import copy
+                twin = copy.deepcopy(net[0][0])                  # (its running statistics have moved once already in train mode:
+                with torch.no_grad():                            #  batch statistics are what a train-mode output is made of)
+                    direct, m1 = block_fwd(twin, ins[0], memory, R.MEMORY_PERCENT)
+                assert torch.equal(direct, outs[0].detach()) and torch.equal(m1, ins[0][:, :m1.shape[1]])
+            for h in hooks:
+                h.remove()
+            torch.autograd.backward(outs, R.fixture_cotangents(seed, tag, dt))
+            for f, x in enumerate(ins):
+                got["grad_in_f%d" % f] = x.grad.detach()
+            if memory is not None:
+                got["grad_memory"] = memory.grad.detach()
+            for k, p in net.named_parameters():
+                got["grad_" + k] = p.grad.detach()
+            return got, keys, shapes
+
+        arrs = dict(seed=seed)
+        note = []
+        for mode in R.MODES:
+            training = mode == "train"
+            r32, keys, shapes = run(torch.float32, training)
+            r64, _, _ = run(torch.float64, training)
+            assert keys == [k for k, _ in R.key_shapes(tag)] and shapes == [s for _, s in R.key_shapes(tag)]
+            own = R.run(seed, tag, torch.float64, training)            # the restatement stands where the reference stands
+            assert set(own) == set(r64), set(own) ^ set(r64)
+            for k in r64:
+                assert float((own[k] - r64[k]).abs().max()) <= 1e-10 * max(1.0, float(r64[k].abs().max())), (tag, mode, k)
+            devs, rels = [], []
+            for k in r32:
+                if k.startswith("grad_"):
+                    name = "grad_%s_%s" % (mode, k[5:])
+                    arrs["rel_" + name] = float((r32[k].double() - r64[k]).norm() / r64[k].norm())
+                    rels.append(arrs["rel_" + name])
+                else:
+                    name = "%s_%s" % (mode, k)
+                    arrs["dev_" + name] = float((r32[k].double() - r64[k]).abs().max())
+                    arrs["max_" + name] = float(r64[k].abs().max())
+                    devs.append(arrs["dev_" + name])
+                if R.stored(name):
+                    arrs[name] = R.sample(r32[k], seed)
+            note.append("%s: dev %.3g .. %.3g, rel_grad %.3g .. %.3g" % (mode, min(devs), max(devs), min(rels), max(rels)))
+        arrs["keys"] = np.array(keys)
+        arrs["key_shapes"] = np.array([list(s) + [-1] * (4 - len(s)) for s in shapes], dtype=np.int64)
+        size = save_fixed("mbconv_" + tag, **arrs)
+        total += size
+        lines.append("mbconv_%s  B=%d C=%d Cmid=%d Cr=%d plane %dx%d, %d block(s), %d frame(s), first-frame memory %s  seed %d; %s; %.0f KB"
+                     % (tag, c["B"], c["C"], c["Cmid"], c["Cr"], c["plane"][0], c["plane"][1], c["blocks"], c["frames"], c["memory"], seed,
+                        "; ".join(note), size / 1024))
+    lines.append("total %.0f KB" % (total / 1024))
+    assert total < 1000 * 1000, total
+    with open(os.path.join(OUT, "PROVENANCE_mbconv.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def save_fixed(name, **arrs):
     """`save` with the archive's time stamps pinned, so that a fixture regenerates byte for byte."""
     import zipfile
@@ -2448,6 +2577,9 @@ def main():
         return
     if "--only-decoder" in sys.argv:
         decoder_cases(M)
+        return
+    if "--only-mbconv" in sys.argv:
+        mbconv_cases(M)
         return
     if "--only-flow-frame" in sys.argv:
         flow_frame_cases(M)

@@ -4,6 +4,8 @@
     python tools/kernel_resources.py temporalstereo_amd/csrc/render.hip          (the rendering kernels: no scratch)
     python tools/kernel_resources.py temporalstereo_amd/csrc/preprocess.hip      (the frame-preparation kernels: no scratch)
     python tools/kernel_resources.py temporalstereo_amd/csrc/augment.hip         (the augmentation kernels: no scratch)
+    python tools/kernel_resources.py temporalstereo_amd/csrc/mbconv.hip          (the memory MBConv block's kernels: no scratch;
+                                                                                  profiles/mbconv_kernel_resources.txt)
 """
 import re
 import subprocess
