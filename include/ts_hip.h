@@ -740,6 +740,40 @@ int ts_depthwise3x3_bwd_weight(const float* x, const float* dy, float* dw, int B
 int ts_se_gate_fwd(const float* plane_sum, const float* w_reduce, const float* b_reduce, const float* w_expand, const float* b_expand,
                    float* gate, int B, int Cmid, int Cr, float inv_hw, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The encoder's large planes: the stem, block0's ConvBnAct members and the fused-MBConv (EdgeResidual) members of block1 / block2,
+ * backbone/TemporalStereo.py:62-70,105-113, fp32 throughout, no atomics (ABI 23).  Eval forms:
+ *   y = act(conv3x3(x, stride s, padding 1) * scale + shift) (+ residual)        ts_conv3x3_s_fwd        a ConvBnAct, the stem, a
+ *                                                                                                        fused block's expansion
+ *   y = conv1x1(x) * scale + shift (+ residual)                                  ts_fused_project_fwd    a fused block's projection
+ * Both run on the f32-input MFMA through the cores of the decoder (3x3, blocked sums of 288 products) and of the memory block (1x1,
+ * blocked sums of 256 products); an output's bits do not depend on the batch or the launch geometry.
+ * ts_conv3x3_s_weight_layout  w [Cout][Cin][3][3] (contiguous) -> w_l, ts_conv3x3_s_weight_bytes(Cin, Cout, stride) bytes (0 outside the
+ *                             envelope), 16-byte aligned; one launch.  stride 2: the image of the phase form -- a stride-1 3x3 over
+ *                             the 4 Cin phase channels x[c, 2y + py, 2x + px] whose taps at offsets {-1, 0} carry the weights, zeros
+ *                             elsewhere.  An image serves the stride it was made for only.
+ * ts_conv3x3_s_fwd            x [B,Cin,H,W]; y and residual [B,Cout,ceil(H/s),ceil(W/s)]; s 1 | 2; act 0 none | 1 SiLU.  The residual is
+ *                             added AFTER the activation and is accepted at s = 1 only (TS_ERR_SHAPE otherwise).  y OVERWRITTEN.
+ * ts_fused_project_fwd        x [B,Cmid,H,W]; y and residual [B,Cout,H,W]; w_l is ts_mbconv_weight_layout's image of [Cout][Cmid].
+ *                             y OVERWRITTEN.
+ * Aliasing (both entries, TS_ERR_SHAPE): y may not overlap x, and y is either the residual's own elements (the same pointer and
+ * strides) or apart from it.  "Overlap" is judged on the operands' bounding extents [p, p + (B - 1) bstride + (C - 1) cstride + plane):
+ * two interleaved channel slices of one wider buffer are refused although they share no element.
+ * scale / shift (per output channel) and residual may each be NULL (1 / 0 / nothing added).  Tensors have batch / channel strides in
+ * elements and dense planes.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, another stride or activation, a residual
+ * at stride 2, overlapping strides), then Cin (s = 1) or 4 Cin (s = 2) > 512, Cout > 512, Cmid > 2048, an axis >= 2^20, a grid that
+ * does not fit (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL), then the alignment of w_l (TS_ERR_ALIGN), then the aliasing rule
+ * (TS_ERR_SHAPE).
+ * ---------------------------------------------------------------------------------------- */
+size_t ts_conv3x3_s_weight_bytes(int Cin, int Cout, int stride);
+int ts_conv3x3_s_weight_layout(const float* w, float* w_l, int Cin, int Cout, int stride, void* stream);
+int ts_conv3x3_s_fwd(const float* x, const float* w_l, const float* scale, const float* shift, const float* residual, float* y, int B,
+                     int Cin, int Cout, int H, int W, int stride, int act, long long x_bstride, long long x_cstride,
+                     long long r_bstride, long long r_cstride, long long y_bstride, long long y_cstride, void* stream);
+int ts_fused_project_fwd(const float* x, const float* w_l, const float* scale, const float* shift, const float* residual, float* y,
+                         int B, int Cmid, int Cout, int H, int W, long long x_bstride, long long x_cstride, long long r_bstride,
+                         long long r_cstride, long long y_bstride, long long y_cstride, void* stream);
+
 /* K2c  the temporal state update of one frame, fused: update_map's closures update_local_map and
  * update_past_cost, projects/TemporalStereo/TemporalStereo.py:340-384 / :386-426, three launches.
  *   prev_disp  full-resolution disparity of the previous frame, [B,1,full_h,full_w] (disp_bstride elements

@@ -199,6 +199,10 @@ SIGNATURES = {
     "ts_depthwise3x3_fwd": (c_int, [c_f32p] * 6 + [c_int] * 6 + [ctypes.c_longlong] * 4 + [c_ptr]),
     "ts_depthwise3x3_bwd_weight": (c_int, [c_f32p] * 3 + [c_int] * 4 + [ctypes.c_longlong] * 4 + [c_ptr]),
     "ts_se_gate_fwd": (c_int, [c_f32p] * 6 + [c_int] * 3 + [c_float, c_ptr]),
+    "ts_conv3x3_s_weight_bytes": (c_size, [c_int] * 3),
+    "ts_conv3x3_s_weight_layout": (c_int, [c_f32p] * 2 + [c_int] * 3 + [c_ptr]),
+    "ts_conv3x3_s_fwd": (c_int, [c_f32p] * 6 + [c_int] * 7 + [ctypes.c_longlong] * 6 + [c_ptr]),
+    "ts_fused_project_fwd": (c_int, [c_f32p] * 6 + [c_int] * 5 + [ctypes.c_longlong] * 6 + [c_ptr]),
     "ts_reproject_memory_workspace_bytes": (c_size, [c_int] * 5),
     "ts_reproject_memory_fwd": (c_int, [c_f32p, ctypes.c_longlong, c_int, c_int, c_f32p, c_f32p, c_int, c_f32p, c_int, c_int,
                                         c_f32p, c_int, c_f32p, c_f32p, c_f32p, c_float, c_float, c_f32p, c_f32p, c_f32p,

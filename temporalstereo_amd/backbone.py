@@ -32,6 +32,13 @@ splice on temporal.exchange_feature_memory and the depthwise convolution on func
 BatchNorms and the squeeze-excite step stay framework ops there.  Everything else -- CPU tensors, other dtypes,
 set_conv_backend('torch'), drop_path_rate > 0 in train mode, a block `from_block` did not recognise -- takes `_reference_forward`, the
 reference's statements on the block's own submodules.
+
+StemConv, ConvBnAct, FusedInvertedResidual: the encoder's large planes -- the stem, the members of block0 and the fused-MBConv
+(edge-residual) members of block1 / block2 (backbone/TemporalStereo.py:62-70,105-113) -- routed the same way: one launch (stem, ConvBnAct)
+or two (a fused block) in eval mode without a gradient (csrc/fused_mbconv.hip), the stride-1 3x3 on functional.decoder_conv's node in
+train mode, the block's own submodules otherwise.  InvertedResidual: the MBConv block without a residual, framework ops.
+TemporalStereoBackbone: the reference's backbone module over all of these, with its forward(l_img, r_img, prev_info), its state-dict
+keys, `from_backbone` adopting an existing one and a constructor from a table of widths.
 """
 import torch
 import torch.nn as nn
@@ -61,7 +68,7 @@ class FeatureDecoder(nn.Module):
         self.deconv8_4 = pair(out_channels[2] + channels[1], out_channels[1])
 
     @classmethod
-    def from_backbone(cls, module):
+    def from_backbone(cls, module, set_mode=True):
         """Adopts `conv32`, `deconv32_16`, `deconv16_8` and `deconv8_4` of an existing reference backbone: the decoder's wrappers hold
         the SAME Parameter and buffer objects (nothing is copied), so the backbone's optimizer, checkpoints and .to() keep working.
         In the reference: `self.decoder = FeatureDecoder.from_backbone(self)` and `return self.decoder(x4, x8, x16, x32), out_memories`
@@ -95,7 +102,10 @@ class FeatureDecoder(nn.Module):
             if len(seq) != 2:
                 raise ValueError("FeatureDecoder.from_backbone: '%s' must hold two convolutions" % name)
             setattr(self, name, nn.Sequential(adopt(seq[0]), adopt(seq[1])))
-        self.train(module.training)
+        if set_mode:
+            self.train(module.training)
+        else:                               # (the submodules keep the modes they have: TemporalStereoBackbone adopts at every call)
+            self.training = module.training
         return self
 
     @staticmethod
@@ -360,3 +370,464 @@ def block_forward(block, input, memory_percent=0.0, memories=None, memory_idx=0)
             else:
                 input = member(input)
     return input, out_memories, memory_idx
+
+
+# ------------------------------------------------------------------------------------------------------- the encoder's large planes
+def _conv3x3(m):
+    """A plain 3x3 convolution csrc/fused_mbconv.hip computes: stride 1 or 2, padding 1, no bias."""
+    return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.kernel_size == (3, 3) and m.stride in ((1, 1), (2, 2)) and \
+        m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1 and m.bias is None and m.padding_mode == "zeros"
+
+
+def _conv1x1(m, cin):
+    return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.in_channels == cin and m.kernel_size == (1, 1) and \
+        m.stride == (1, 1) and m.padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1 and m.bias is None
+
+
+def _batchnorm(m, c):
+    return type(m) in (nn.BatchNorm2d, nn.SyncBatchNorm) and m.num_features == c and m.affine and m.track_running_stats and m.momentum is not None
+
+
+class _LargePlaneBlock(nn.Module):
+    """What StemConv, ConvBnAct and FusedInvertedResidual share: the routing decision and the 3x3 + BatchNorm + SiLU step of the three
+    routes.  A subclass names its 3x3 convolution and its BatchNorms (`_conv3`, `_norms`) and its envelope (`_supported`)."""
+    has_residual = False
+    drop_path_rate = 0.0
+
+    def _route(self, x):
+        """'kernels' | 'train' | 'reference' (the module's docstring)."""
+        from . import functional as TF
+        if not self._recognised or x.dim() != 4 or not layers._hip_conv(x):
+            return "reference"
+        norms = self._norms()
+        training = self.training or any(bn.training for bn in norms)
+        if training and self.drop_path_rate > 0:
+            return "reference"
+        params = [p for p in self.parameters()]
+        if any(not (p.is_cuda and p.dtype == torch.float32) for p in params) or any(TF.bn_exchanges(bn) for bn in norms):
+            return "reference"
+        if not self._supported():
+            return "reference"
+        if training or (torch.is_grad_enabled() and any(t.requires_grad for t in [x] + params)):
+            return "train"
+        return "kernels"
+
+    @staticmethod
+    def _conv3_train(conv, bn, act, x):
+        """silu(bn(conv3x3(x))) with a gradient or batch statistics: stride 1 on functional.decoder_conv's node, stride 2 framework ops."""
+        from . import functional as TF
+        if conv.stride == (1, 1):
+            return TF.decoder_conv(None, x, conv.weight, None, bn, "SiLU")
+        return act(bn(conv(x)))
+
+    def forward(self, x):
+        route = self._route(x)
+        if route == "kernels":
+            return self._kernel_forward(x)
+        if route == "train":
+            return self._train_forward(x)
+        return self._reference_forward(x)
+
+
+class StemConv(_LargePlaneBlock):
+    """The encoder's stem, `act1(bn1(conv_stem(x)))`: a 3x3 convolution of stride 2 (or 1), padding 1, without bias, BatchNorm, SiLU --
+    attributes and state-dict keys as the reference's backbone holds them (backbone/TemporalStereo.py:62-64, 105).  Eval mode without a
+    gradient: ONE launch, the stride-2 form in the phase order (csrc/fused_mbconv.hip)."""
+
+    def __init__(self, in_chs=3, out_chs=24, stride=2):
+        super().__init__()
+        self.conv_stem = nn.Conv2d(in_chs, out_chs, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(out_chs)
+        self.act1 = nn.SiLU(inplace=True)
+        self._recognised = True
+
+    @classmethod
+    def from_modules(cls, conv_stem, bn1, act1):
+        """Adopts the three submodule objects themselves (the same Parameters and buffers; nothing is copied)."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.conv_stem, self.bn1, self.act1 = conv_stem, bn1, act1
+        self._recognised = self._recognise()
+        self.training = bn1.training            # (the three keep the modes they have)
+        return self
+
+    def _recognise(self):
+        c = self.conv_stem
+        return _conv3x3(c) and _batchnorm(self.bn1, c.out_channels) and isinstance(self.act1, nn.SiLU)
+
+    def _norms(self):
+        return (self.bn1,)
+
+    def _supported(self):
+        from . import functional as TF
+        c = self.conv_stem
+        return TF.conv3x3_s_supported(c.in_channels, c.out_channels, c.stride[0])
+
+    def _reference_forward(self, x):
+        return self.act1(self.bn1(self.conv_stem(x)))
+
+    def _train_forward(self, x):
+        return self._conv3_train(self.conv_stem, self.bn1, self.act1, x)
+
+    def _kernel_forward(self, x):
+        from . import functional as TF
+        return TF.conv3x3_bn_act(x, self.conv_stem.weight, TF._bn_eval_fold(self.bn1), self.conv_stem.stride[0], "SiLU")
+
+
+class ConvBnAct(_LargePlaneBlock):
+    """A member of the encoder's first stage: `act1(bn1(conv(x)))` plus the input where `has_residual` (stride 1, equal widths, `skip`).
+    Attributes and state-dict keys follow timm 0.4.12's `ConvBnAct` as efficientnetv2_rw_s builds it -- conv.weight, bn1.*; act1,
+    has_residual, drop_path_rate.  timm is not a dependency of this package and was not at hand when this was written: the list rests
+    on the record (the reference's backbone takes `net.blocks[0]` as it is, backbone/TemporalStereo.py:68).  Eval mode without a gradient:
+    ONE launch with the residual added after the activation (csrc/fused_mbconv.hip)."""
+
+    def __init__(self, in_chs, out_chs, stride=1, skip=False, drop_path_rate=0.0):
+        super().__init__()
+        self.conv = nn.Conv2d(in_chs, out_chs, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(out_chs)
+        self.act1 = nn.SiLU(inplace=True)
+        self.has_residual = bool(skip) and stride == 1 and in_chs == out_chs
+        self.drop_path_rate = float(drop_path_rate)
+        self._recognised = True
+
+    @classmethod
+    def from_block(cls, block):
+        """Adopts an existing block by its attributes: the SAME submodule objects.  A block `_recognise` does not accept keeps running its
+        own submodules in the reference's order."""
+        for name in ("conv", "bn1", "act1"):
+            if not hasattr(block, name):
+                raise ValueError("ConvBnAct.from_block: the block has no '%s'" % name)
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.conv, self.bn1, self.act1 = block.conv, block.bn1, block.act1
+        self.has_residual = bool(getattr(block, "has_residual", False))
+        self.drop_path_rate = float(getattr(block, "drop_path_rate", 0.0))
+        self._recognised = self._recognise()
+        self.train(block.training)
+        return self
+
+    def _recognise(self):
+        c = self.conv
+        if not (_conv3x3(c) and _batchnorm(self.bn1, c.out_channels) and isinstance(self.act1, nn.SiLU)):
+            return False
+        return not self.has_residual or (c.stride == (1, 1) and c.in_channels == c.out_channels)
+
+    def _norms(self):
+        return (self.bn1,)
+
+    def _supported(self):
+        from . import functional as TF
+        return TF.conv3x3_s_supported(self.conv.in_channels, self.conv.out_channels, self.conv.stride[0])
+
+    def _reference_forward(self, x):
+        shortcut = x
+        x = self.conv(x)
+        x = self.bn1(x)
+        x = self.act1(x)
+        if self.has_residual:
+            if self.drop_path_rate > 0:
+                x = _drop_path(x, self.drop_path_rate, self.training)
+            x += shortcut
+        return x
+
+    def _train_forward(self, x):
+        y = self._conv3_train(self.conv, self.bn1, self.act1, x)
+        return y + x if self.has_residual else y
+
+    def _kernel_forward(self, x):
+        from . import functional as TF
+        return TF.conv3x3_bn_act(x, self.conv.weight, TF._bn_eval_fold(self.bn1), self.conv.stride[0], "SiLU",
+                                 residual=x if self.has_residual else None)
+
+
+_FUSED_PARTS = ("conv_exp", "bn1", "act1", "conv_pwl", "bn2")
+
+
+class FusedInvertedResidual(_LargePlaneBlock):
+    """The fused-MBConv (edge-residual) block of the encoder's second and third stages:
+
+        x = act1(bn1(conv_exp(input)));  x = se(x);  x = bn2(conv_pwl(x));  return x + input if has_residual else x
+
+    conv_exp a 3x3 of stride 1 or 2 and padding 1, conv_pwl a 1x1, neither with a bias.  Attributes and state-dict keys follow timm
+    0.4.12's `EdgeResidual` as efficientnetv2_rw_s builds it -- conv_exp.weight, bn1.*, conv_pwl.weight, bn2.*; act1, se (None or
+    nn.Identity there: no squeeze-excite in these stages), has_residual, drop_path_rate.  timm is not a dependency of this package and
+    was not at hand when this was written: the list rests on the record (the reference takes `net.blocks[1:3]` as they are,
+    backbone/TemporalStereo.py:69-70; its `_block_forward` calls every member that is not an InvertedResidual).
+
+    Routing, one path per configuration whatever the plane size: fp32 GPU tensors under the 'hip' backend, a recognised block inside
+    the envelope (functional.fused_mbconv_supported), eval mode and nothing that needs a gradient -> functional.fused_mbconv_eval, TWO
+    launches (csrc/fused_mbconv.hip).  The same in train mode or with a gradient needed -> `_train_forward`: the stride-1 expansion with
+    its BatchNorm and SiLU on functional.decoder_conv's node; the 1x1, its BatchNorm, the residual and a stride-2 expansion stay
+    framework ops.  Everything else -- CPU tensors, other dtypes, set_conv_backend('torch'), a train-mode SyncBatchNorm over several
+    ranks, drop_path_rate > 0 in train mode, a block `from_block` did not recognise (a real squeeze-excite, a stride on conv_pwl,
+    another activation or norm) -- takes `_reference_forward`, the statements above on the block's own submodules."""
+
+    def __init__(self, in_chs, out_chs, exp_ratio=4.0, stride=1, mid_chs=None, noskip=False, drop_path_rate=0.0):
+        super().__init__()
+        mid_chs = int(mid_chs) if mid_chs else _make_divisible(in_chs * exp_ratio)
+        self.conv_exp = nn.Conv2d(in_chs, mid_chs, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(mid_chs)
+        self.act1 = nn.SiLU(inplace=True)
+        self.se = nn.Identity()
+        self.conv_pwl = nn.Conv2d(mid_chs, out_chs, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(out_chs)
+        self.has_residual = in_chs == out_chs and stride == 1 and not noskip
+        self.drop_path_rate = float(drop_path_rate)
+        self._recognised = True
+
+    @classmethod
+    def from_block(cls, block):
+        """Adopts an existing edge-residual block by its attributes: the SAME submodule objects (so the same Parameters and buffers;
+        nothing is copied).  The kernels are taken only when the block is recognised (`_recognise`)."""
+        for name in _FUSED_PARTS:
+            if not hasattr(block, name):
+                raise ValueError("FusedInvertedResidual.from_block: the block has no '%s'" % name)
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        for name in _FUSED_PARTS:
+            setattr(self, name, getattr(block, name))
+        self.se = getattr(block, "se", None)
+        self.has_residual = bool(getattr(block, "has_residual", False))
+        self.drop_path_rate = float(getattr(block, "drop_path_rate", 0.0))
+        self._recognised = self._recognise()
+        self.train(block.training)
+        return self
+
+    def _recognise(self):
+        """True when the submodules are exactly what csrc/fused_mbconv.hip computes."""
+        e, p = self.conv_exp, self.conv_pwl
+        if not _conv3x3(e) or not _conv1x1(p, e.out_channels):
+            return False
+        if not (_batchnorm(self.bn1, e.out_channels) and _batchnorm(self.bn2, p.out_channels) and isinstance(self.act1, nn.SiLU)):
+            return False
+        if not (self.se is None or type(self.se) is nn.Identity):
+            return False
+        return not self.has_residual or (e.stride == (1, 1) and e.in_channels == p.out_channels)
+
+    def _norms(self):
+        return (self.bn1, self.bn2)
+
+    def _supported(self):
+        from . import functional as TF
+        e = self.conv_exp
+        return TF.fused_mbconv_supported(e.in_channels, e.out_channels, self.conv_pwl.out_channels, e.stride[0])
+
+    def _reference_forward(self, x):
+        shortcut = x
+        x = self.conv_exp(x)
+        x = self.bn1(x)
+        x = self.act1(x)
+        if self.se is not None:
+            x = self.se(x)
+        x = self.conv_pwl(x)
+        x = self.bn2(x)
+        if self.has_residual:
+            if self.drop_path_rate > 0:
+                x = _drop_path(x, self.drop_path_rate, self.training)
+            x += shortcut
+        return x
+
+    def _train_forward(self, x):
+        y = self._conv3_train(self.conv_exp, self.bn1, self.act1, x)
+        y = self.bn2(self.conv_pwl(y))
+        return y + x if self.has_residual else y
+
+    def _kernel_forward(self, x, return_stages=False):
+        from . import functional as TF
+        res = TF.fused_mbconv_eval(x, self.conv_exp.weight, TF._bn_eval_fold(self.bn1), self.conv_exp.stride[0], self.conv_pwl.weight,
+                                   TF._bn_eval_fold(self.bn2), x if self.has_residual else None, return_stages=return_stages)
+        if return_stages:
+            return res[0], dict(mid=res[1])
+        return res
+
+
+class InvertedResidual(nn.Module):
+    """The MBConv block WITHOUT a residual -- the first member of a stage, which changes the stride or the width -- on framework ops in
+    the reference's op order (the one `_inverted_residual_forward` spells out, minus the memory and the residual).  It exists so that a
+    backbone can be constructed without timm; it has no kernel path (a stride-2 depthwise kernel is not part of this package)."""
+
+    def __init__(self, in_chs, out_chs, stride=1, exp_ratio=4.0, se_ratio=0.25, mid_chs=None, se_chs=None):
+        super().__init__()
+        if in_chs == out_chs and stride == 1:
+            raise ValueError("InvertedResidual: a block of stride 1 and equal widths has a residual: MemoryInvertedResidual")
+        mid_chs = int(mid_chs) if mid_chs else _make_divisible(in_chs * exp_ratio)
+        se_chs = int(se_chs) if se_chs else _make_divisible(in_chs * se_ratio, 1)
+        self.conv_pw = nn.Conv2d(in_chs, mid_chs, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(mid_chs)
+        self.act1 = nn.SiLU(inplace=True)
+        self.conv_dw = nn.Conv2d(mid_chs, mid_chs, 3, stride, 1, groups=mid_chs, bias=False)
+        self.bn2 = nn.BatchNorm2d(mid_chs)
+        self.act2 = nn.SiLU(inplace=True)
+        self.se = SqueezeExcite(mid_chs, se_chs)
+        self.conv_pwl = nn.Conv2d(mid_chs, out_chs, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(out_chs)
+        self.has_residual = False
+        self.drop_path_rate = 0.0
+
+    def forward(self, x):
+        x = self.act1(self.bn1(self.conv_pw(x)))
+        x = self.act2(self.bn2(self.conv_dw(x)))
+        x = self.se(x)
+        return self.bn3(self.conv_pwl(x))
+
+
+# per stage: runs of (kind, output width, stride of the first member, expansion ratio, members); kinds: 'cn' ConvBnAct with skip,
+# 'er' fused (edge-residual), 'ir' inverted residual with squeeze-excite.  efficientnetv2_rw_s as timm 0.4.12 defines it
+# (cn_r2_k3_s1_e1_c24_skip / er_r4_k3_s2_e4_c48 / er_r4_k3_s2_e4_c64 / ir_r6_k3_s2_e4_c128_se0.25 / ir_r9_k3_s1_e6_c160_se0.25 /
+# ir_r15_k3_s2_e6_c272_se0.25, stem 24), cut into five stages as the reference cuts it (backbone/TemporalStereo.py:66-72).
+ARCHS = {
+    "efficientnetv2_rw_s": dict(
+        stem=24, se_ratio=0.25,
+        stages=((("cn", 24, 1, 1.0, 2),),
+                (("er", 48, 2, 4.0, 4),),
+                (("er", 64, 2, 4.0, 4),),
+                (("ir", 128, 2, 4.0, 6), ("ir", 160, 1, 6.0, 9)),
+                (("ir", 272, 2, 6.0, 15),)),
+        out_channels=(0, 64, 128, 256, 320)),
+}
+_STAGES = ("block0", "block1", "block2", "block3", "block4")
+
+
+class TemporalStereoBackbone(nn.Module):
+    """The reference's backbone `TEMPORALSTEREO` (architecture/modeling/backbone/TemporalStereo.py:19-162): the two eyes concatenated
+    along the batch, the stem, five stages, the three-level decoder, and the per-frame feature memories of the residual MBConv blocks
+    kept in `prev_info['memories']`.  `_forward` and `forward` are the reference's, statement for statement, with `block_forward` for
+    its `_block_forward` and a FeatureDecoder for its decoder lines.  State-dict keys are the reference module's: conv_stem.weight,
+    bn1.*, block0.0.0.conv.weight, ..., block1.0.0.conv_exp.weight, ..., block3.0.1.conv_pw.weight, ..., conv32.*, deconv32_16.*,
+    deconv16_8.*, deconv8_4.*.
+
+    arch: a name in ARCHS or a table of the same form (dict(stem, se_ratio, stages, out_channels)).  The layout is built from the table
+    of widths: there are no pretrained weights and nothing is downloaded (the reference asks timm for `pretrained=True`; load a
+    checkpoint of the reference's backbone with load_state_dict).  `from_backbone(module)` adopts an existing reference backbone.
+
+    Who runs what: the stem is a StemConv, block0's members ConvBnAct, the members of block1 / block2 FusedInvertedResidual, the
+    residual members of block3 / block4 MemoryInvertedResidual, the decoder a FeatureDecoder -- each with its own routing (kernels in
+    eval mode without a gradient).  The non-residual first member of a run in block3 / block4 is an InvertedResidual on framework ops.
+    The StemConv and the FeatureDecoder are made at every call from the submodules registered on this module AT THAT MOMENT (they
+    hold no state of their own), so a replaced child -- nn.SyncBatchNorm.convert_sync_batchnorm(model), `net.bn1 = ...` -- is what runs.
+    In eval mode under no_grad `forward` opens a `WeightLayouts` and a `BNFolds` context for the call when none is open; nothing is
+    kept between calls (a caller that wants layouts and folds kept across frames opens the contexts itself and refreshes them)."""
+
+    def __init__(self, arch="efficientnetv2_rw_s", in_planes=3, memory_percent=1 / 4, norm='BN', activation='SiLU'):
+        super().__init__()
+        table = ARCHS[arch] if isinstance(arch, str) else dict(arch)
+        self.in_planes, self.memory_percent, self.norm, self.activation = in_planes, memory_percent, norm, activation
+        self.conv_stem = nn.Conv2d(in_planes, table["stem"], 3, 2, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(table["stem"])
+        self.act1 = nn.SiLU(inplace=True)
+        width, channels = table["stem"], []
+        if len(table["stages"]) != 5:
+            raise ValueError("TemporalStereoBackbone: the table holds five stages")
+        for name, runs in zip(_STAGES, table["stages"]):
+            seqs = []
+            for kind, out, stride, exp, members in runs:
+                blocks = []
+                for i in range(members):
+                    s = stride if i == 0 else 1
+                    if kind == "cn":
+                        blocks.append(ConvBnAct(width, out, s, skip=True))
+                    elif kind == "er":
+                        blocks.append(FusedInvertedResidual(width, out, exp, s))
+                    elif kind == "ir" and width == out and s == 1:
+                        blocks.append(MemoryInvertedResidual(width, exp, table["se_ratio"], memory_percent))
+                    elif kind == "ir":
+                        blocks.append(InvertedResidual(width, out, s, exp, table["se_ratio"]))
+                    else:
+                        raise ValueError("TemporalStereoBackbone: unknown block kind %r" % (kind,))
+                    width = out
+                seqs.append(nn.Sequential(*blocks))
+            setattr(self, name, nn.Sequential(*seqs))
+            channels.append(width)
+        decoder = FeatureDecoder(channels, table["out_channels"], norm, activation)
+        for name in _NAMES:
+            setattr(self, name, getattr(decoder, name))
+
+    @classmethod
+    def from_backbone(cls, module):
+        """Adopts an existing reference backbone: the stem's three submodules, every member of block0 .. block4 (ConvBnAct,
+        FusedInvertedResidual and MemoryInvertedResidual `from_block` by the members' attributes; a member none of them takes -- the
+        non-residual MBConv blocks -- is kept as it is) and the decoder's four.  Parameters and buffers are the SAME objects, nothing is
+        copied: the module's state dict, optimizer and .to() keep working.  `model.backbone = TemporalStereoBackbone.from_backbone(
+        model.backbone)` replaces the per-submodule recipe."""
+        for name in ("conv_stem", "bn1", "act1") + _STAGES + _NAMES:
+            if not hasattr(module, name):
+                raise ValueError("TemporalStereoBackbone.from_backbone: the module has no '%s'" % name)
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.in_planes = getattr(module, "in_planes", module.conv_stem.in_channels)
+        self.memory_percent = getattr(module, "memory_percent", 1 / 4)
+        self.norm, self.activation = getattr(module, "norm", None), getattr(module, "activation", None)
+        self.conv_stem, self.bn1, self.act1 = module.conv_stem, module.bn1, module.act1
+
+        def adopt(m):
+            if isinstance(m, (ConvBnAct, FusedInvertedResidual, MemoryInvertedResidual)):
+                return m
+            if all(hasattr(m, n) for n in _FUSED_PARTS):
+                return FusedInvertedResidual.from_block(m)
+            if all(hasattr(m, n) for n in _MBCONV_PARTS):
+                return MemoryInvertedResidual.from_block(m, self.memory_percent) if getattr(m, "has_residual", False) else m
+            if all(hasattr(m, n) for n in ("conv", "bn1", "act1")):
+                return ConvBnAct.from_block(m)
+            return m
+        for name in _STAGES:
+            setattr(self, name, nn.Sequential(*[nn.Sequential(*[adopt(m) for m in seq]) for seq in getattr(module, name)]))
+        decoder = FeatureDecoder.from_backbone(module, set_mode=False)
+        for name in _NAMES:                     # (a plain nn.Conv2d is wrapped once: the wrapper shares its Parameters and is what is registered)
+            setattr(self, name, getattr(decoder, name))
+        self.training = module.training         # (every adopted submodule keeps the mode it has)
+        return self
+
+    @property
+    def _parts(self):
+        """(StemConv, FeatureDecoder) over the submodules registered on this module NOW.  Both are views without parameters of their
+        own, kept out of the module registry so that the state-dict keys stay conv_stem.*, bn1.*, conv32.*, deconv*; they are made per
+        call so that a child replaced after construction (a SyncBatchNorm conversion, an assignment) is the one that runs."""
+        stem = StemConv.from_modules(self.conv_stem, self.bn1, self.act1)
+        stem.training = self.training
+        return stem, FeatureDecoder.from_backbone(self, set_mode=False)
+
+    def _forward(self, x, memories):
+        stem, decoder = self._parts
+        memory_idx = 0
+        out_memories = []
+        x = stem(x)
+        x = self.block0(x)
+        x, out, memory_idx = block_forward(self.block1, x, self.memory_percent, memories, memory_idx)
+        x4 = x
+        out_memories.extend(out)
+        x, out, memory_idx = block_forward(self.block2, x, self.memory_percent, memories, memory_idx)
+        x8 = x
+        out_memories.extend(out)
+        x, out, memory_idx = block_forward(self.block3, x, self.memory_percent, memories, memory_idx)
+        x16 = x
+        out_memories.extend(out)
+        x, out, memory_idx = block_forward(self.block4, x, self.memory_percent, memories, memory_idx)
+        x32 = x
+        out_memories.extend(out)
+        return decoder(x4, x8, x16, x32), out_memories
+
+    def forward(self, *input):
+        if len(input) != 3:
+            raise ValueError('expected input length 3 (got {} length input)'.format(len(input)))
+        from . import functional as TF
+        l_img, r_img, prev_info = input
+        mem = prev_info.get('memories', [])
+        B, _, _, _ = l_img.shape
+
+        lr_img = torch.cat([l_img, r_img], dim=0)
+
+        if not self.training and not torch.is_grad_enabled() and TF._LAYOUTS is None and TF._FOLDS is None and layers._hip_conv(lr_img):
+            with TF.WeightLayouts(), TF.BNFolds():
+                lr_fms, mem = self._forward(lr_img, mem)
+        else:
+            lr_fms, mem = self._forward(lr_img, mem)
+
+        l_fms = [fms[:B] for fms in lr_fms]
+        r_fms = [fms[B:] for fms in lr_fms]
+
+        if self.memory_percent > 0:
+            prev_info['memories'] = mem
+        else:
+            prev_info['memories'] = []
+
+        return l_fms, r_fms, prev_info

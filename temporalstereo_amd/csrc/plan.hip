@@ -119,6 +119,7 @@ const Entry kTable[] = {
     TS_PLAN_OP(ts_decoder_weight_layout),   TS_PLAN_OP(ts_decoder_conv_fwd),        TS_PLAN_OP(ts_resize_bilinear_bwd),
     TS_PLAN_OP(ts_mbconv_weight_layout),    TS_PLAN_OP(ts_mbconv_expand_fwd),       TS_PLAN_OP(ts_mbconv_project_fwd),
     TS_PLAN_OP(ts_depthwise3x3_fwd),        TS_PLAN_OP(ts_depthwise3x3_bwd_weight), TS_PLAN_OP(ts_se_gate_fwd),
+    TS_PLAN_OP(ts_conv3x3_s_weight_layout), TS_PLAN_OP(ts_conv3x3_s_fwd),           TS_PLAN_OP(ts_fused_project_fwd),
 };
 
 struct Call {

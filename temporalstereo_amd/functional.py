@@ -3215,3 +3215,142 @@ def depthwise_conv3x3(x, weight, bias=None):
     """F.conv2d(x, weight, bias, stride=1, padding=1, groups=C) for a [C,1,3,3] weight on the HIP kernels (fp32 GPU tensors; any plane),
     with gradients for x, weight and bias."""
     return _Depthwise3x3.apply(x, weight, bias)
+
+
+# ---- the encoder's large planes: stem, ConvBnAct, fused MBConv (reference: backbone/TemporalStereo.py:62-70,105-113) --------------------
+CONV3X3_S_MAX_CHANNELS = 512      # the kernel path's envelope (csrc/fused_mbconv.hip): the 3x3's core channels -- Cin at stride 1, 4 Cin at
+#                                   stride 2 (the phase form) -- and its Cout; the projection takes Cmid <= 2048 and Cout <= 512
+
+
+def conv3x3_s_supported(Cin, Cout, stride):
+    return stride in (1, 2) and 1 <= Cin and Cin * (4 if stride == 2 else 1) <= CONV3X3_S_MAX_CHANNELS and 1 <= Cout <= CONV3X3_S_MAX_CHANNELS
+
+
+def fused_mbconv_supported(Cin, Cmid, Cout, stride):
+    """Whether a fused (edge-residual) block Cin -> Cmid (3x3, stride 1 | 2) -> Cout (1x1) is inside the kernels' envelope."""
+    return conv3x3_s_supported(Cin, Cmid, stride) and 1 <= Cmid <= MBCONV_MAX_MID and 1 <= Cout <= MBCONV_MAX_CHANNELS
+
+
+def _conv3x3_s_weight_make(stride):
+    def make(weight, out=None):
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        if out is None:
+            nbytes = _q("ts_conv3x3_s_weight_bytes", Cin, Cout, stride)
+            if not nbytes:
+                raise RuntimeError("conv3x3_bn_act: %d input / %d output channels at stride %d are outside the kernel path (%s)"
+                                   % (Cin, Cout, stride, "4 Cin <= %d at stride 2, Cin and Cout <= %d" % ((CONV3X3_S_MAX_CHANNELS,) * 2)))
+            out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
+        _lib.check(_lib.lib().ts_conv3x3_s_weight_layout(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, stride, _stream()),
+                   "ts_conv3x3_s_weight_layout")
+        return out
+    return make
+
+
+_CONV3X3_S_MAKE = {1: _conv3x3_s_weight_make(1), 2: _conv3x3_s_weight_make(2)}
+
+
+def _conv3x3_s_weight(weight, stride):
+    """The 3x3 core's chunked order of a [Cout, Cin, 3, 3] weight for one stride (ts_conv3x3_s_weight_layout: at stride 2 the phase
+    order); inside a `WeightLayouts` context a leaf is laid out once per step and refreshed with the others, as `_decoder_weight`."""
+    if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
+        return _LAYOUTS.get_custom(weight, "conv3x3_s%d" % stride, _CONV3X3_S_MAKE[stride])
+    return _CONV3X3_S_MAKE[stride](_lib.contiguous(weight.detach()))
+
+
+def _fold_check(what, name, fold, n):
+    if fold is None:
+        return None, None
+    if len(fold) != 2 or any(v is None or v.dim() != 1 or v.numel() < n or not v.is_contiguous() for v in fold):
+        raise ValueError("%s: the %s fold must be a (scale, shift) pair of dense vectors of at least %d values" % (what, name, n))
+    return fold
+
+
+def _out_check(what, name, t, shape):
+    """A [B,C,H,W] operand the kernels write (or read as the residual) in place: dense planes, strides that do not overlap."""
+    B, C, H, W = shape
+    if tuple(t.shape) != tuple(shape) or t.stride(3) != 1 or t.stride(2) != W or t.stride(1) < H * W or \
+            (B > 1 and t.stride(0) < t.stride(1) * (C - 1) + H * W):
+        raise ValueError("%s: %s must be %s with dense planes and strides that do not overlap, got %s strides %s"
+                         % (what, name, list(shape), tuple(t.shape), tuple(t.stride())))
+
+
+def conv3x3_bn_act(x, weight, fold, stride, activation, residual=None, out=None):
+    """The eval form of a 3x3 convolution (padding 1, stride 1 | 2, no bias) with its BatchNorm folded, its activation and -- at stride 1 --
+    a residual added AFTER the activation, as ONE launch (csrc/fused_mbconv.hip, ts_conv3x3_s_fwd): the reference encoder's stem, a
+    ConvBnAct of block0, the expansion of a fused block.  x [B,Cin,H,W] is read in place through its strides; weight [Cout,Cin,3,3] as the
+    framework holds it; fold: (scale, shift) of the BatchNorm (`_bn_eval_fold`) or None; activation None | 'SiLU'; residual
+    [B,Cout,H,W] or None.  -> [B,Cout,ceil(H/s),ceil(W/s)] (written into `out` when given).  Nothing here asks for a gradient: the caller
+    has checked.  Outside a `WeightLayouts` context the weight layout is a launch of its own."""
+    what = "conv3x3_bn_act"
+    if activation not in (None, "SiLU"):
+        raise ValueError("%s: activation must be None or 'SiLU'" % what)
+    if stride not in (1, 2):
+        raise ValueError("%s: stride must be 1 or 2, got %r" % (what, stride))
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError("%s: x must be a non-empty [B,C,H,W], got %s" % (what, tuple(x.shape)))
+    B, Cin, H, W = x.shape
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (Cin, 3, 3):
+        raise ValueError("%s: weight must be [Cout, %d, 3, 3], got %s" % (what, Cin, tuple(weight.shape)))
+    Cout = weight.shape[0]
+    scale, shift = _fold_check(what, "BatchNorm", fold, Cout)
+    if not conv3x3_s_supported(Cin, Cout, stride):
+        raise RuntimeError("%s: %d input / %d output channels at stride %d are outside the kernel path" % (what, Cin, Cout, stride))
+    Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+    if residual is not None:
+        if stride != 1:
+            raise ValueError("%s: a residual is taken at stride 1 only" % what)
+        if tuple(residual.shape) != (B, Cout, Ho, Wo):
+            raise ValueError("%s: residual must be %s, got %s" % (what, [B, Cout, Ho, Wo], tuple(residual.shape)))
+    if out is not None:
+        _out_check(what, "out", out, (B, Cout, Ho, Wo))
+    _require_gpu(x, weight, scale, shift, residual, out)
+    x = _plane_view(x)
+    rb = rc = 0
+    if residual is not None:
+        residual = _plane_view(residual)
+        rb, rc = residual.stride(0), residual.stride(1)
+    y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=torch.float32) if out is None else out
+    code = _lib.lib().ts_conv3x3_s_fwd(_lib.ptr(x), _lib.ptr(_conv3x3_s_weight(weight, stride)), _lib.ptr(scale), _lib.ptr(shift),
+                                       _lib.ptr(residual), _lib.ptr(y), B, Cin, Cout, H, W, int(stride), BN_ACT[activation], x.stride(0),
+                                       x.stride(1), rb, rc, y.stride(0), y.stride(1), _stream())
+    _lib.check(code, "ts_conv3x3_s_fwd")
+    return y
+
+
+def fused_mbconv_eval(x, w_exp, fold1, stride, w_pwl, fold2, residual, out=None, return_stages=False):
+    """The eval form of one fused (edge-residual) block as TWO launches (csrc/fused_mbconv.hip): the 3x3 expansion with bn1 and SiLU
+    (`conv3x3_bn_act`; it writes the mid map [B,Cmid,ceil(H/s),ceil(W/s)]) and the 1x1 projection that folds bn2 and adds the residual
+    (ts_fused_project_fwd).  fold1 / fold2: (scale, shift) of the two BatchNorms (`_bn_eval_fold`); the weights as the framework holds
+    them; residual: the tensor added to the projection ([B,Cout,.,.], for a residual block the input itself) or None.  Nothing here asks
+    for a gradient: the caller has checked.  Outside `WeightLayouts` / `BNFolds` contexts the two weight layouts and two folds are
+    launches of their own.  -> the block's output (written into `out` when given); with return_stages also the mid map."""
+    what = "fused_mbconv_eval"
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError("%s: x must be a non-empty [B,C,H,W], got %s" % (what, tuple(x.shape)))
+    if w_exp.dim() != 4 or w_pwl.dim() != 4 or tuple(w_pwl.shape[1:]) != (w_exp.shape[0], 1, 1):
+        raise ValueError("%s: conv_exp weight [Cmid,Cin,3,3] and conv_pwl weight [Cout,Cmid,1,1] expected, got %s and %s"
+                         % (what, tuple(w_exp.shape), tuple(w_pwl.shape)))
+    B, Cin, H, W = x.shape
+    Cmid, Cout = w_exp.shape[0], w_pwl.shape[0]
+    if fold1 is None or fold2 is None:
+        raise ValueError("%s: both BatchNorm folds are required" % what)
+    scale2, shift2 = _fold_check(what, "bn2", fold2, Cout)
+    if stride not in (1, 2) or not fused_mbconv_supported(Cin, Cmid, Cout, stride):
+        raise RuntimeError("%s: Cin = %d, Cmid = %d, Cout = %d at stride %r are outside the kernel path" % (what, Cin, Cmid, Cout, stride))
+    Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+    if residual is not None and tuple(residual.shape) != (B, Cout, Ho, Wo):
+        raise ValueError("%s: residual must be %s, got %s" % (what, [B, Cout, Ho, Wo], tuple(residual.shape)))
+    if out is not None:
+        _out_check(what, "out", out, (B, Cout, Ho, Wo))
+    _require_gpu(w_pwl, scale2, shift2, residual, out)
+    mid = conv3x3_bn_act(x, w_exp, fold1, stride, "SiLU")
+    rb = rc = 0
+    if residual is not None:
+        residual = _plane_view(residual)
+        rb, rc = residual.stride(0), residual.stride(1)
+    y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=torch.float32) if out is None else out
+    code = _lib.lib().ts_fused_project_fwd(_lib.ptr(mid), _lib.ptr(_mbconv_weight(w_pwl)), _lib.ptr(scale2), _lib.ptr(shift2),
+                                           _lib.ptr(residual), _lib.ptr(y), B, Cmid, Cout, Ho, Wo, mid.stride(0), mid.stride(1), rb, rc,
+                                           y.stride(0), y.stride(1), _stream())
+    _lib.check(code, "ts_fused_project_fwd")
+    return (y, mid) if return_stages else y

@@ -2191,6 +2191,152 @@ def mbconv_cases(M):
     print("\n".join(lines))
 
 
+def reference_encoder(mb_class):
+    """The reference's OWN `_block_forward`, `_inverted_residual_forward`, `TEMPORALSTEREO._forward` and `TEMPORALSTEREO.forward`
+    (architecture/modeling/backbone/TemporalStereo.py:101-218), compiled from its file's syntax tree -- the module imports timm at the
+    top, which this image does not have.  `InvertedResidual` is bound to `mb_class`, `drop_path` to a function that raises.
+    -> (_block_forward, _forward(self, x, memories), forward(self, l_img, r_img, prev_info))"""
+    import ast
+    import typing
+    import torch.nn.functional as F
+    path = os.path.join(ref_import.REFERENCE_ROOT, "architecture", "modeling", "backbone", "TemporalStereo.py")
+    tree = ast.parse(open(path).read(), filename=path)
+    names = ("_block_forward", "_inverted_residual_forward")
+    funcs = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in names]
+    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "TEMPORALSTEREO")
+    funcs += [n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name in ("_forward", "forward")]
+    assert sorted(f.name for f in funcs) == sorted(names + ("_forward", "forward"))
+
+    def drop_path(*a, **k):
+        raise AssertionError("drop_path must not be reached: the stand-ins' drop_path_rate is 0")
+    ns = {"torch": torch, "F": F, "InvertedResidual": mb_class, "drop_path": drop_path, "Union": typing.Union, "List": typing.List,
+          "Tuple": typing.Tuple}
+    exec(compile(ast.fix_missing_locations(ast.Module(body=funcs, type_ignores=[])), path, "exec"), ns)
+    return ns["_block_forward"], ns["_forward"], ns["forward"]
+
+
+def encoder_cases(M):
+    """tests/golden/encoder_*.npz: tests/encoder_ref.py's stand-in blocks called as the reference calls them -- as modules, through its
+    own `_block_forward`, and (case d) through its own backbone `forward` -- on the CPU, in fp32 and fp64, train mode and eval mode;
+    dev_* = how far the fp32 run lies from the fp64 run."""
+    import types
+    import encoder_ref as R
+    from architecture.modeling.layers import Conv2d
+    stage_fwd, ref__forward, ref_forward = reference_encoder(R.StandInMB)
+    lines = ["encoder_*.npz: tools/gen_golden.py --only-encoder, numpy %s, torch %s CPU -- tests/encoder_ref.py's stand-ins for timm 0.4.12's" % (np.__version__, torch.__version__),
+             "ConvBnAct, EdgeResidual and InvertedResidual (timm, where the reference's blocks come from, is not part of its checkout) run by the",
+             "reference's own code: _block_forward, _inverted_residual_forward, TEMPORALSTEREO._forward and TEMPORALSTEREO.forward",
+             "(architecture/modeling/backbone/TemporalStereo.py:101-218, compiled from the file's syntax tree with the name InvertedResidual bound to",
+             "encoder_ref.StandInMB and drop_path to a function that raises), the decoder's submodules built by the reference's own Conv2d;",
+             "on seeded inputs in float32 and in float64, in train mode and in eval mode, with the backward of seeded cotangents.",
+             "a, b: one fused block called as a module.  c: a stage of two fused blocks through _block_forward with memory_percent 1/4 (asserted:",
+             "out_memories empty, memory_idx unchanged).  d: a miniature backbone (encoder_ref.MINI: stem 3 -> 8, a ConvBnAct with skip, two",
+             "fused stages of a stride-2 and a residual block, two MBConv stages of a non-residual stride-2 and a residual block, the",
+             "decoder) through forward(l_img, r_img, prev_info) on two frames of 2 x 3 x 64 x 96, the second reading the first's memories.",
+             "Inputs, all kept as their seed (encoder_ref fixture_state / fixture_inputs / fixture_cotangents draw them again): convolution weights",
+             "N(0,1) * 2 / sqrt(fan-in) (case d, some twenty layers deep: 1 / sqrt(fan-in)), convolution biases N(0, 0.1), BatchNorm weight U(0.5, 1.5) and bias N(0, 0.1), running mean N(0, 0.1),",
+             "running variance U(0.5, 1.5), inputs N(0,1), cotangents k / 8 with k an integer in [-8, 8].",
+             "Stored: seed, keys and key_shapes (the state-dict keys in order, shapes padded with -1), and per mode m in (train, eval) the",
+             "deviations of EVERY output, stage and gradient over the WHOLE arrays: dev_<m>_<key> = max |fp32 run - fp64 run|, max_<m>_<key> =",
+             "max |.| of the fp64 run, rel_grad_<m>_<input|parameter key> = relative L2 of the fp32 run's gradient against the fp64 run's.",
+             "Arrays (fp32 run; one of more than %d elements at %d seeded flat positions, encoder_ref.sample): those encoder_ref.stored names." % (R.SAMPLE, R.SAMPLE),
+             "The tests compare everything against the fp64 restatement, which the generator asserts equal to the reference's fp64 run to 1e-10."]
+    total = 0
+    for tag in R.TAGS:
+        c = R.CASES[tag]
+        seed = synth.SEED0 + 17000 + 1000 * ord(tag)
+
+        def run(dt, training):
+            net = R.stand_in(tag, Conv2d)
+            keys = list(net.state_dict().keys())
+            shapes = [tuple(v.shape) for v in net.state_dict().values()]
+            res = net.load_state_dict(R.fixture_state(seed, tag), strict=True)
+            assert not res.missing_keys and not res.unexpected_keys
+            net = net.to(dt).train(training)
+            ins = R.fixture_inputs(seed, tag, dt)
+            for t in ins:
+                t.requires_grad_(True)
+            got, hooks, at = {}, [], {"f": 0}
+
+            def keep(name, pick=lambda o: o):
+                return lambda m, a, o=None: got.__setitem__("f%d_%s" % (at["f"], name), pick(a[0] if o is None else o).detach().clone())
+            outs = []
+            if c["kind"] == "backbone":
+                net._forward = types.MethodType(ref__forward, net)
+                o4 = R.MINI["out_channels"][4]
+                hooks += [net.act1.register_forward_hook(keep("stem")), net.block0.register_forward_hook(keep("block0")),
+                          net.block1[0][-1].register_forward_hook(keep("block1")), net.block2[0][-1].register_forward_hook(keep("block2")),
+                          net.deconv32_16.register_forward_pre_hook(keep("block3", lambda t: t[:, o4:])),
+                          net.conv32.register_forward_pre_hook(keep("block4"))]
+                info = {}
+                for f in range(c["frames"]):
+                    at["f"] = f
+                    before = list(info.get("memories", []))
+                    l_fms, r_fms, info = ref_forward(net, ins[2 * f], ins[2 * f + 1], info)
+                    assert len(info["memories"]) == 2 and (f == 0) == (before == [])
+                    assert [m.shape[1] for m in info["memories"]] == [6, 8]
+                    for k, l, r in zip(R.OUTS, l_fms, r_fms):
+                        whole = torch.cat([l, r], 0)
+                        outs.append(whole)
+                        got["f%d_%s" % (f, k)] = whole.detach()
+            else:
+                for i, blk in enumerate(net[0]):
+                    hooks += [blk.act1.register_forward_hook(keep("b%d_mid" % i)), blk.register_forward_hook(keep("b%d_out" % i))]
+                if c["kind"] == "stage":
+                    out, memories, idx = stage_fwd(net, ins[0], R.MEMORY_PERCENT, None, 0)
+                    assert memories == [] and idx == 0           # no member is an InvertedResidual: nothing takes or leaves a memory
+                else:
+                    out = net[0][0](ins[0])
+                outs.append(out)
+                got["f0_out"] = out.detach()
+            for h in hooks:
+                h.remove()
+            torch.autograd.backward(outs, R.fixture_cotangents(seed, tag, dt))
+            for name, x in zip(R.input_names(tag), ins):
+                got["grad_" + name] = x.grad.detach()
+            for k, p in net.named_parameters():
+                got["grad_" + k] = p.grad.detach()
+            return got, keys, shapes
+
+        arrs = dict(seed=seed)
+        note = []
+        for mode in R.MODES:
+            training = mode == "train"
+            r32, keys, shapes = run(torch.float32, training)
+            r64, _, _ = run(torch.float64, training)
+            assert keys == [k for k, _ in R.key_shapes(tag)] and shapes == [s for _, s in R.key_shapes(tag)]
+            own = R.run(seed, tag, torch.float64, training)            # the restatement stands where the reference stands
+            assert set(own) == set(r64), set(own) ^ set(r64)
+            for k in r64:
+                assert float((own[k] - r64[k]).abs().max()) <= 1e-10 * max(1.0, float(r64[k].abs().max())), (tag, mode, k)
+            devs, rels = [], []
+            for k in r32:
+                if k.startswith("grad_"):
+                    name = "grad_%s_%s" % (mode, k[5:])
+                    arrs["rel_" + name] = float((r32[k].double() - r64[k]).norm() / r64[k].norm())
+                    rels.append(arrs["rel_" + name])
+                else:
+                    name = "%s_%s" % (mode, k)
+                    arrs["dev_" + name] = float((r32[k].double() - r64[k]).abs().max())
+                    arrs["max_" + name] = float(r64[k].abs().max())
+                    devs.append(arrs["dev_" + name])
+                if R.stored(name):
+                    arrs[name] = R.sample(r32[k], seed)
+            note.append("%s: dev %.3g .. %.3g, rel_grad %.3g .. %.3g" % (mode, min(devs), max(devs), min(rels), max(rels)))
+        arrs["keys"] = np.array(keys)
+        arrs["key_shapes"] = np.array([list(s) + [-1] * (4 - len(s)) for s in shapes], dtype=np.int64)
+        size = save_fixed("encoder_" + tag, **arrs)
+        total += size
+        lines.append("encoder_%s  %s, B=%d, plane %dx%d, %d frame(s)  seed %d; %s; %.0f KB"
+                     % (tag, c["kind"] + (" " + repr(c["members"]) if "members" in c else ""), c["B"], c["plane"][0], c["plane"][1], c["frames"],
+                        seed, "; ".join(note), size / 1024))
+    lines.append("total %.0f KB" % (total / 1024))
+    assert total < 1000 * 1000, total
+    with open(os.path.join(OUT, "PROVENANCE_encoder.txt"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def save_fixed(name, **arrs):
     """`save` with the archive's time stamps pinned, so that a fixture regenerates byte for byte."""
     import zipfile
@@ -2580,6 +2726,9 @@ def main():
         return
     if "--only-mbconv" in sys.argv:
         mbconv_cases(M)
+        return
+    if "--only-encoder" in sys.argv:
+        encoder_cases(M)
         return
     if "--only-flow-frame" in sys.argv:
         flow_frame_cases(M)

@@ -6,6 +6,9 @@
     python tools/kernel_resources.py temporalstereo_amd/csrc/augment.hip         (the augmentation kernels: no scratch)
     python tools/kernel_resources.py temporalstereo_amd/csrc/mbconv.hip          (the memory MBConv block's kernels: no scratch;
                                                                                   profiles/mbconv_kernel_resources.txt)
+    python tools/kernel_resources.py temporalstereo_amd/csrc/fused_mbconv.hip    (the encoder's 3x3 of either stride and the fused
+                                                                                  projection: no scratch;
+                                                                                  profiles/encoder_kernel_resources.txt)
 """
 import re
 import subprocess
