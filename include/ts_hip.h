@@ -683,7 +683,9 @@ int ts_conv_gru_grad_sum(const float* dcat_g, const float* dcat_q, float* dh, fl
  * The other gradients run on ts_conv3d_hw_bwd_data (D = 1, over the concatenation's channels), ts_conv3d_hw_bwd_weight (per source and
  * per slice of <= 64 output channels), ts_bn_* and ts_channel_sum_fwd.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive,
  * an unknown activation, overlapping strides), then Cu + Cs > 512, Cout > 512, an axis >= 2^20, a grid that does not fit
- * (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL; scale, shift, and up when Cu = 0 may be NULL).
+ * (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL; scale, shift, and up when Cu = 0 may be NULL), then the alignment of w_l
+ * (TS_ERR_ALIGN), then the aliasing rule of ts_decoder_conv_fwd (ABI 24, TS_ERR_SHAPE): y lies apart from up and from skip, judged on
+ * the operands' bounding extents as for ts_conv3x3_s_fwd below (other workgroups read the neighbours of what a workgroup writes).
  * ---------------------------------------------------------------------------------------- */
 size_t ts_decoder_weight_bytes(int Cin, int Cout);
 int ts_decoder_weight_layout(const float* w, float* w_l, int Cin, int Cout, void* stream);
@@ -708,7 +710,7 @@ int ts_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int h, int 
  *                             channels are not read), each in place; the concatenation is not written.  memory NULL: input alone (the
  *                             first frame; mc and the memory strides are ignored).  y [B,Cmid,H,W] OVERWRITTEN.
  * ts_mbconv_project_fwd       x [B,Cmid,H,W] times gate [B][Cmid] (dense) per channel while it is read; the gated map is not written.
- *                             residual and y [B,C,H,W]; y OVERWRITTEN (y may not alias residual unless they are the same elements).
+ *                             residual and y [B,C,H,W]; y OVERWRITTEN.
  * ts_depthwise3x3_fwd         x, y [B,C,H,W], w [C][9], stride 1, padding 1; act 0 none | 1 SiLU; flip 1 reverses the nine taps (with
  *                             no epilogue: the input gradient of dy).  plane_sum [B][C] may be NULL; a plane's sum is taken in an order
  *                             fixed by (H, W): the same bits whatever B and C are.  One workgroup per (b, c) plane.
@@ -721,7 +723,12 @@ int ts_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int h, int 
  * scale / shift (per output channel) may be NULL (1 / 0).  Tensors with strides have batch / channel strides in elements and dense
  * planes.  Checks, before any launch: sizes (TS_ERR_SHAPE: non-positive, mc outside [0, C], an unknown activation or flip, overlapping
  * strides), then C > 512, Cmid > 2048, Cr > 512, an axis >= 2^20, a plane >= 2^31 pixels, a grid that does not fit
- * (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL), then the alignment of w_l (TS_ERR_ALIGN).
+ * (TS_ERR_UNSUPPORTED), then pointers (TS_ERR_NULL), then the alignment of w_l (TS_ERR_ALIGN), then the aliasing rules (ABI 24,
+ * TS_ERR_SHAPE; "overlap" is judged on the operands' bounding extents, as for ts_conv3x3_s_fwd below):
+ *   ts_mbconv_expand_fwd    y lies apart from memory and from input;
+ *   ts_mbconv_project_fwd   y lies apart from x; y is either the residual's own elements (the same pointer and strides: the in-place
+ *                           residual) or apart from it;
+ *   ts_depthwise3x3_fwd     y lies apart from x.
  * ---------------------------------------------------------------------------------------- */
 size_t ts_mbconv_weight_bytes(int Cin, int Cout);
 int ts_mbconv_weight_layout(const float* w, float* w_l, int Cin, int Cout, void* stream);

@@ -199,6 +199,42 @@ class SqueezeExcite(nn.Module):
         return x * self.gate(x_se)
 
 
+def _conv(m, k, strides=(1,), cin=None, cout=None, groups=1, bias=False, zeros=True):
+    """A k x k nn.Conv2d as the kernels compute it: a stride out of `strides`, padding k // 2, no dilation, `groups` groups, with or
+    without a bias; cin / cout: the widths it must have (None: any); zeros: padding_mode must be 'zeros' (the fused block's 1x1, which
+    pads nothing, never asked)."""
+    return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.kernel_size == (k, k) and \
+        m.stride in [(s, s) for s in strides] and m.padding == (k // 2, k // 2) and m.dilation == (1, 1) and m.groups == groups and \
+        (m.bias is not None) == bias and (not zeros or m.padding_mode == "zeros") and cin in (None, m.in_channels) and cout in (None, m.out_channels)
+
+
+def _batchnorm(m, c, momentum=True):
+    """A BatchNorm over c channels with affine parameters and running statistics; momentum: a momentum is required (momentum=None, the
+    cumulative average, is outside functional.decoder_conv's node, which the large-plane blocks train on)."""
+    return type(m) in (nn.BatchNorm2d, nn.SyncBatchNorm) and m.num_features == c and m.affine and m.track_running_stats and \
+        (not momentum or m.momentum is not None)
+
+
+def _route(block, norms, supported, *tensors):
+    """'kernels' | 'train' | 'reference' for a block of the encoder (the blocks' docstrings): `tensors` are what the block would hand to
+    the kernels (the input first; None: absent), `norms` its BatchNorms, `supported()` its envelope."""
+    from . import functional as TF
+    tensors = [t for t in tensors if t is not None]
+    if not block._recognised or tensors[0].dim() != 4 or not all(layers._hip_conv(t) for t in tensors):
+        return "reference"
+    training = block.training or any(bn.training for bn in norms)
+    if training and block.drop_path_rate > 0:
+        return "reference"
+    params = [p for p in block.parameters()]
+    if any(not (p.is_cuda and p.dtype == torch.float32) for p in params) or any(TF.bn_exchanges(bn) for bn in norms):
+        return "reference"
+    if not supported():
+        return "reference"
+    if training or (torch.is_grad_enabled() and any(t.requires_grad for t in tensors + params)):
+        return "train"
+    return "kernels"
+
+
 _MBCONV_PARTS = ("conv_pw", "bn1", "act1", "conv_dw", "bn2", "act2", "se", "conv_pwl", "bn3")
 
 
@@ -255,21 +291,13 @@ class MemoryInvertedResidual(nn.Module):
 
     def _recognise(self):
         """True when the submodules are exactly what csrc/mbconv.hip computes."""
-        def conv(m, cin, cout, k, groups, bias):
-            return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.in_channels == cin and m.out_channels == cout and \
-                m.kernel_size == (k, k) and m.stride == (1, 1) and m.padding == (k // 2, k // 2) and m.dilation == (1, 1) and \
-                m.groups == groups and (m.bias is not None) == bias and m.padding_mode == "zeros"
-
-        def norm(m, c):
-            return type(m) in (nn.BatchNorm2d, nn.SyncBatchNorm) and m.num_features == c and m.affine and m.track_running_stats
-
         pw, se = self.conv_pw, self.se
         if not isinstance(pw, nn.Conv2d):
             return False
         C, Cmid = pw.in_channels, pw.out_channels
-        if not (conv(pw, C, Cmid, 1, 1, False) and conv(self.conv_dw, Cmid, Cmid, 3, Cmid, False) and conv(self.conv_pwl, Cmid, C, 1, 1, False)):
+        if not (_conv(pw, 1) and _conv(self.conv_dw, 3, cin=Cmid, cout=Cmid, groups=Cmid) and _conv(self.conv_pwl, 1, cin=Cmid, cout=C)):
             return False
-        if not (norm(self.bn1, Cmid) and norm(self.bn2, Cmid) and norm(self.bn3, C)):
+        if not all(_batchnorm(bn, c, momentum=False) for bn, c in ((self.bn1, Cmid), (self.bn2, Cmid), (self.bn3, C))):
             return False
         if not (isinstance(self.act1, nn.SiLU) and isinstance(self.act2, nn.SiLU)):
             return False
@@ -277,26 +305,14 @@ class MemoryInvertedResidual(nn.Module):
             return False
         Cr = se.conv_reduce.out_channels
         gate = se.gate
-        return conv(se.conv_reduce, Cmid, Cr, 1, 1, True) and conv(se.conv_expand, Cr, Cmid, 1, 1, True) and isinstance(se.act1, nn.SiLU) and \
+        return _conv(se.conv_reduce, 1, cin=Cmid, bias=True) and _conv(se.conv_expand, 1, cin=Cr, cout=Cmid, bias=True) and isinstance(se.act1, nn.SiLU) and \
             (isinstance(gate, nn.Sigmoid) or getattr(gate, "__name__", None) == "sigmoid")
 
     def _route(self, input, memory):
         """'kernels' | 'train' | 'reference' (the module's docstring)."""
         from . import functional as TF
-        if not self._recognised or input.dim() != 4 or not layers._hip_conv(input) or (memory is not None and not layers._hip_conv(memory)):
-            return "reference"
-        norms = (self.bn1, self.bn2, self.bn3)
-        training = self.training or any(bn.training for bn in norms)
-        if training and self.drop_path_rate > 0:
-            return "reference"
-        params = [p for p in self.parameters()]
-        if any(not (p.is_cuda and p.dtype == torch.float32) for p in params) or any(TF.bn_exchanges(bn) for bn in norms):
-            return "reference"
-        if not TF.mbconv_supported(self.conv_pw.in_channels, self.conv_pw.out_channels, self.se.conv_reduce.out_channels):
-            return "reference"
-        if training or (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in [input, memory] + params)):
-            return "train"
-        return "kernels"
+        return _route(self, (self.bn1, self.bn2, self.bn3),
+                      lambda: TF.mbconv_supported(self.conv_pw.in_channels, self.conv_pw.out_channels, self.se.conv_reduce.out_channels), input, memory)
 
     def _reference_forward(self, input, memory, mc):
         input1, input2 = input[:, :mc], input[:, mc:]
@@ -375,17 +391,7 @@ def block_forward(block, input, memory_percent=0.0, memories=None, memory_idx=0)
 # ------------------------------------------------------------------------------------------------------- the encoder's large planes
 def _conv3x3(m):
     """A plain 3x3 convolution csrc/fused_mbconv.hip computes: stride 1 or 2, padding 1, no bias."""
-    return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.kernel_size == (3, 3) and m.stride in ((1, 1), (2, 2)) and \
-        m.padding == (1, 1) and m.dilation == (1, 1) and m.groups == 1 and m.bias is None and m.padding_mode == "zeros"
-
-
-def _conv1x1(m, cin):
-    return isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.in_channels == cin and m.kernel_size == (1, 1) and \
-        m.stride == (1, 1) and m.padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1 and m.bias is None
-
-
-def _batchnorm(m, c):
-    return type(m) in (nn.BatchNorm2d, nn.SyncBatchNorm) and m.num_features == c and m.affine and m.track_running_stats and m.momentum is not None
+    return _conv(m, 3, strides=(1, 2))
 
 
 class _LargePlaneBlock(nn.Module):
@@ -396,21 +402,7 @@ class _LargePlaneBlock(nn.Module):
 
     def _route(self, x):
         """'kernels' | 'train' | 'reference' (the module's docstring)."""
-        from . import functional as TF
-        if not self._recognised or x.dim() != 4 or not layers._hip_conv(x):
-            return "reference"
-        norms = self._norms()
-        training = self.training or any(bn.training for bn in norms)
-        if training and self.drop_path_rate > 0:
-            return "reference"
-        params = [p for p in self.parameters()]
-        if any(not (p.is_cuda and p.dtype == torch.float32) for p in params) or any(TF.bn_exchanges(bn) for bn in norms):
-            return "reference"
-        if not self._supported():
-            return "reference"
-        if training or (torch.is_grad_enabled() and any(t.requires_grad for t in [x] + params)):
-            return "train"
-        return "kernels"
+        return _route(self, self._norms(), self._supported, x)
 
     @staticmethod
     def _conv3_train(conv, bn, act, x):
@@ -596,7 +588,7 @@ class FusedInvertedResidual(_LargePlaneBlock):
     def _recognise(self):
         """True when the submodules are exactly what csrc/fused_mbconv.hip computes."""
         e, p = self.conv_exp, self.conv_pwl
-        if not _conv3x3(e) or not _conv1x1(p, e.out_channels):
+        if not _conv3x3(e) or not _conv(p, 1, cin=e.out_channels, zeros=False):
             return False
         if not (_batchnorm(self.bn1, e.out_channels) and _batchnorm(self.bn2, p.out_channels) and isinstance(self.act1, nn.SiLU)):
             return False

@@ -12,16 +12,14 @@
 //
 // Backward: the convolutions' gradients run on ts_conv3d_hw_bwd_data / ts_conv3d_hw_bwd_weight (D = 1); the three element kernels
 // here carry the gates' derivatives and the sums into dh / dx.  No atomics anywhere: bit-reproducible.
-#include "act_fast.hpp"
 #include "conv_hw3.hpp"
 
 namespace {
 
 constexpr int kMaxC = 64;
-constexpr int kGridCap = 2048;               // blocks of the grid-stride element kernels
+constexpr int kElemGridCap = 2048;           // blocks of the grid-stride element kernels of the backward pass
+using node::pitch_for;                       // (the gates' 2 Ch <= 128 rows: 64 or 128)
 using ts::strides_ok;
-
-inline int pitch_for(int rows) { return (rows + 63) / 64 * 64; }                  // global pitch of a weight row: whole workgroups of any MT
 
 template <bool GATES>
 struct Gru {
@@ -127,35 +125,40 @@ __global__ void __launch_bounds__(256) gru_grad_sum_kernel(const float* __restri
 }
 
 // sizes (TS_ERR_SHAPE), then the envelope (TS_ERR_UNSUPPORTED)
-int check_cell(const char* who, int B, int Ch, int Cx, int H, int W) {
-  TS_REQUIRE(B > 0 && Ch > 0 && Cx > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
-  TS_REQUIRE(Ch <= kMaxC && Cx <= kMaxC, TS_ERR_UNSUPPORTED, "%s: Ch=%d / Cx=%d above %d", who, Ch, Cx, kMaxC);
-  TS_REQUIRE(B < (1 << 20) && H < (1 << 20) && W < (1 << 20), TS_ERR_UNSUPPORTED, "%s: an axis of 2^20 or more", who);
-  const unsigned long long blocks = 8ull * hw3::tiles_x(W) * hw3::tiles_y(H) * B;      // at most 8 row groups
-  TS_REQUIRE(corr::grid_blocks(blocks) != 0, TS_ERR_UNSUPPORTED, "%s: grid too large", who);
-  return TS_OK;
-}
 int check_planes(const char* who, int B, int Ch, long long N) {
   TS_REQUIRE(B > 0 && Ch > 0 && N > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
   TS_REQUIRE(Ch <= kMaxC, TS_ERR_UNSUPPORTED, "%s: Ch=%d above %d", who, Ch, kMaxC);
-  TS_REQUIRE(B < (1 << 20) && N < (1ll << 40), TS_ERR_UNSUPPORTED, "%s: an axis of 2^20 or more", who);
+  TS_REQUIRE(B < node::kMaxAxis && N < (1ll << 40), TS_ERR_UNSUPPORTED, "%s: an axis of 2^20 or more", who);
   return TS_OK;
-}
-
-// the grid is cut along the rows until every compute unit has a workgroup (hw3::launch_rule)
-template <bool GATES>
-int launch_conv(Gru<GATES>& p, int B, hipStream_t st, const char* what) {
-  const hw3::Launch l = hw3::launch_rule(p.g, B, ts::kNumCU);
-  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "%s: grid too large", what);
-  hw3::dispatch_mt(l.mt, [&](auto MT) {
-    if constexpr (GATES || MT() < 8)          // 65 .. 128 rows: the gates alone
-      hipLaunchKernelGGL((gru_conv_kernel<MT(), GATES>), dim3(l.blocks), dim3(256), 0, st, p);
-  });
-  return ts::launched(what);
 }
 
 size_t gates_floats(int Ch, int Cx) { return hw3::image_floats(Ch + Cx, pitch_for(2 * Ch)); }
 size_t cand_floats(int Ch, int Cx) { return hw3::image_floats(Ch + Cx, pitch_for(Ch)); }
+
+// One convolution of the cell, p filled but for its geometry: h and x are the strided operands (the outputs are dense and the cell's own),
+// `dense` the other required pointers.  The grid is cut along the rows until every compute unit has a workgroup (hw3::launch_rule).
+template <bool GATES>
+int launch_conv(const char* who, const char* kernel, Gru<GATES>& p, const float* w_l, std::initializer_list<node::Pointer> dense, int B, int Cx,
+                int H, int W, hipStream_t st) {
+  const int Ch = p.Ch;
+  TS_REQUIRE(B > 0 && Ch > 0 && Cx > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
+  const long long HW = static_cast<long long>(H) * W;
+  auto envelope = [&] {
+    TS_REQUIRE(Ch <= kMaxC && Cx <= kMaxC, TS_ERR_UNSUPPORTED, "%s: Ch=%d / Cx=%d above %d", who, Ch, Cx, kMaxC);
+    return TS_OK;
+  };
+  return node::launch(
+      who, kernel, B, {{"h", p.h, Ch, HW, p.h_bs, p.h_cs, node::IN}, {"x", p.x, Cx, HW, p.x_bs, p.x_cs, node::IN}}, dense, w_l, {B, H, W}, envelope,
+      [&] {          // behind the envelope and the axes; the candidate's image lies behind the gates'
+        const int rows = GATES ? 2 * Ch : Ch;
+        p.g = hw3::geom(GATES ? w_l : w_l + gates_floats(Ch, Cx), Ch + Cx, rows, H, W, pitch_for(rows));
+        return hw3::launch_rule(p.g, B, ts::kNumCU);
+      },
+      [&](auto MT, dim3 grid) {
+        if constexpr (GATES || MT() < 8)          // 65 .. 128 rows: the gates alone
+          hipLaunchKernelGGL((gru_conv_kernel<MT(), GATES>), grid, dim3(256), 0, st, p);
+      });
+}
 
 }  // namespace
 
@@ -172,39 +175,28 @@ extern "C" int ts_conv_gru_weight_layout(const float* wz, const float* wr, const
   hw3::WeightImages im;          // [wz | wr] at the gates' pitch, then wq at the candidate's: one launch
   im.wa = wz; im.ra = Ch; im.wb = wr; im.rb = Ch; im.p0 = pitch_for(2 * Ch);
   im.wc = wq; im.rc = Ch; im.p1 = pitch_for(Ch);
-  return hw3::weight_layout(im, w_l, Ch + Cx, kGridCap, ts::as_stream(stream), "gru_weight_layout_kernel");
+  return hw3::weight_layout(im, w_l, Ch + Cx, node::kGridCap, ts::as_stream(stream), "gru_weight_layout_kernel");
 }
 
 extern "C" int ts_conv_gru_gates_fwd(const float* h, const float* x, const float* w_l, const float* bz, const float* br, float* z,
                                      float* rh, float* r, int B, int Ch, int Cx, int H, int W, long long h_bstride, long long h_cstride,
                                      long long x_bstride, long long x_cstride, void* stream) {
-  if (int rc = check_cell("conv_gru_gates_fwd", B, Ch, Cx, H, W)) return rc;
-  const long long HW = static_cast<long long>(H) * W;
-  TS_REQUIRE(strides_ok(B, Ch, HW, h_bstride, h_cstride), TS_ERR_SHAPE, "conv_gru_gates_fwd: h strides %lld / %lld overlap", h_bstride, h_cstride);
-  TS_REQUIRE(strides_ok(B, Cx, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "conv_gru_gates_fwd: x strides %lld / %lld overlap", x_bstride, x_cstride);
-  TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(bz); TS_REQUIRE_PTR(br); TS_REQUIRE_PTR(z); TS_REQUIRE_PTR(rh);
-  TS_REQUIRE_ALIGNED(w_l);
   Gru<true> p;
-  p.g = hw3::geom(w_l, Ch + Cx, 2 * Ch, H, W, pitch_for(2 * Ch));
   p.a = h; p.x = x; p.b0 = bz; p.b1 = br; p.h = h; p.zin = nullptr; p.o0 = z; p.o1 = rh; p.o2 = r; p.Ch = Ch;
   p.a_bs = h_bstride; p.a_cs = h_cstride; p.x_bs = x_bstride; p.x_cs = x_cstride; p.h_bs = h_bstride; p.h_cs = h_cstride;
-  return launch_conv(p, B, ts::as_stream(stream), "gru_conv_kernel<gates>");
+  return launch_conv("conv_gru_gates_fwd", "gru_conv_kernel<gates>", p, w_l, {{"bz", bz}, {"br", br}, {"z", z}, {"rh", rh}}, B, Cx, H, W,
+                     ts::as_stream(stream));
 }
 
 extern "C" int ts_conv_gru_out_fwd(const float* rh, const float* x, const float* w_l, const float* bq, const float* z, const float* h,
                                    float* out, float* q, int B, int Ch, int Cx, int H, int W, long long h_bstride, long long h_cstride,
                                    long long x_bstride, long long x_cstride, void* stream) {
-  if (int rc = check_cell("conv_gru_out_fwd", B, Ch, Cx, H, W)) return rc;
   const long long HW = static_cast<long long>(H) * W;
-  TS_REQUIRE(strides_ok(B, Ch, HW, h_bstride, h_cstride), TS_ERR_SHAPE, "conv_gru_out_fwd: h strides %lld / %lld overlap", h_bstride, h_cstride);
-  TS_REQUIRE(strides_ok(B, Cx, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "conv_gru_out_fwd: x strides %lld / %lld overlap", x_bstride, x_cstride);
-  TS_REQUIRE_PTR(rh); TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(bq); TS_REQUIRE_PTR(z); TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(out);
-  TS_REQUIRE_ALIGNED(w_l);
   Gru<false> p;
-  p.g = hw3::geom(w_l + gates_floats(Ch, Cx), Ch + Cx, Ch, H, W, pitch_for(Ch));
   p.a = rh; p.x = x; p.b0 = bq; p.b1 = nullptr; p.h = h; p.zin = z; p.o0 = out; p.o1 = q; p.o2 = nullptr; p.Ch = Ch;
   p.a_bs = Ch * HW; p.a_cs = HW; p.x_bs = x_bstride; p.x_cs = x_cstride; p.h_bs = h_bstride; p.h_cs = h_cstride;
-  return launch_conv(p, B, ts::as_stream(stream), "gru_conv_kernel<out>");
+  return launch_conv("conv_gru_out_fwd", "gru_conv_kernel<out>", p, w_l, {{"rh", rh}, {"bq", bq}, {"z", z}, {"out", out}}, B, Cx, H, W,
+                     ts::as_stream(stream));
 }
 
 extern "C" int ts_conv_gru_gate_bwd_a(const float* dout, const float* z, const float* q, const float* h, float* dq_pre, float* dz_pre,
@@ -214,7 +206,7 @@ extern "C" int ts_conv_gru_gate_bwd_a(const float* dout, const float* z, const f
   TS_REQUIRE(strides_ok(B, Ch, N, h_bstride, h_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_a: h strides %lld / %lld overlap", h_bstride, h_cstride);
   TS_REQUIRE(strides_ok(B, Ch, N, dz_bstride, dz_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_a: dz_pre strides %lld / %lld overlap", dz_bstride, dz_cstride);
   TS_REQUIRE_PTR(dout); TS_REQUIRE_PTR(z); TS_REQUIRE_PTR(q); TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(dq_pre); TS_REQUIRE_PTR(dz_pre); TS_REQUIRE_PTR(dh);
-  hipLaunchKernelGGL(gru_gate_bwd_a_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * Ch * N, kGridCap)), dim3(256), 0, ts::as_stream(stream), dout, z,
+  hipLaunchKernelGGL(gru_gate_bwd_a_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * Ch * N, kElemGridCap)), dim3(256), 0, ts::as_stream(stream), dout, z,
                      q, h, dq_pre, dz_pre, dh, B, Ch, N, h_bstride, h_cstride, dz_bstride, dz_cstride);
   return ts::launched("gru_gate_bwd_a_kernel");
 }
@@ -227,7 +219,7 @@ extern "C" int ts_conv_gru_gate_bwd_b(const float* d_rh, const float* r, const f
   TS_REQUIRE(strides_ok(B, Ch, N, h_bstride, h_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_b: h strides %lld / %lld overlap", h_bstride, h_cstride);
   TS_REQUIRE(strides_ok(B, Ch, N, dr_bstride, dr_cstride), TS_ERR_SHAPE, "conv_gru_gate_bwd_b: dr_pre strides %lld / %lld overlap", dr_bstride, dr_cstride);
   TS_REQUIRE_PTR(d_rh); TS_REQUIRE_PTR(r); TS_REQUIRE_PTR(h); TS_REQUIRE_PTR(dr_pre); TS_REQUIRE_PTR(dh);
-  hipLaunchKernelGGL(gru_gate_bwd_b_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * Ch * N, kGridCap)), dim3(256), 0, ts::as_stream(stream), d_rh, r,
+  hipLaunchKernelGGL(gru_gate_bwd_b_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * Ch * N, kElemGridCap)), dim3(256), 0, ts::as_stream(stream), d_rh, r,
                      h, dr_pre, dh, B, Ch, N, drh_bstride, drh_cstride, h_bstride, h_cstride, dr_bstride, dr_cstride);
   return ts::launched("gru_gate_bwd_b_kernel");
 }
@@ -238,7 +230,7 @@ extern "C" int ts_conv_gru_grad_sum(const float* dcat_g, const float* dcat_q, fl
   TS_REQUIRE(Cx > 0, TS_ERR_SHAPE, "conv_gru_grad_sum: non-positive size");
   TS_REQUIRE(Cx <= kMaxC, TS_ERR_UNSUPPORTED, "conv_gru_grad_sum: Cx=%d above %d", Cx, kMaxC);
   TS_REQUIRE_PTR(dcat_g); TS_REQUIRE_PTR(dcat_q); TS_REQUIRE_PTR(dh);
-  hipLaunchKernelGGL(gru_grad_sum_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * (Ch + Cx) * N, kGridCap)), dim3(256), 0, ts::as_stream(stream),
+  hipLaunchKernelGGL(gru_grad_sum_kernel, dim3(ts::blocks_for(static_cast<long long>(B) * (Ch + Cx) * N, kElemGridCap)), dim3(256), 0, ts::as_stream(stream),
                      dcat_g, dcat_q, dh, dx, B, Ch, Cx, N);
   return ts::launched("gru_grad_sum_kernel");
 }

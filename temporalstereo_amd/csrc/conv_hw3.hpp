@@ -31,13 +31,14 @@
 //   source(b)         -> a reader (gc, gy, gx) -> float of batch element b;
 //   sink(b, gy, gx)   -> a writer (row, sum) of output pixel (gy, gx) of batch element b, called for row < g.rows only.
 #pragma once
-#include <type_traits>
-
+#include "conv_node.hpp"
 #include "corr_common.hpp"
 
 namespace hw3 {
 
 using corr::v4f;
+using node::dispatch_mt;
+using node::Launch;
 
 constexpr int kCK = 8;                       // input channels per staged chunk
 constexpr int kKC = kCK * 9;                 // contraction elements per chunk
@@ -198,10 +199,6 @@ int weight_layout(const WeightImages& s, float* out, int Cin, int cap, hipStream
 // The launch rule: MT blocks of 16 output rows per workgroup, `groups` workgroups along the rows.  Start at mt_for(rows) and halve MT
 // while the grid holds fewer than min_blocks workgroups: a grid that leaves compute units idle is cut finer along the rows (the input
 // tile is then staged by more workgroups, from L2).  Sets g.groups; returns MT and the blocks of the 1-D grid (0: they do not fit one).
-struct Launch {
-  int mt;
-  unsigned blocks;
-};
 inline Launch launch_rule(Geom& g, int B, unsigned long long min_blocks) {
   int mt = mt_for(g.rows);
   const unsigned long long tiles = static_cast<unsigned long long>(g.tiles_x) * g.tiles_y * B;
@@ -209,17 +206,6 @@ inline Launch launch_rule(Geom& g, int B, unsigned long long min_blocks) {
   while (mt > 1 && tiles * groups(mt) < min_blocks) mt /= 2;
   g.groups = groups(mt);
   return Launch{mt, corr::grid_blocks(tiles * g.groups)};
-}
-
-// a runtime MT as a compile-time one: dispatch_mt(mt, [&](auto MT) { hipLaunchKernelGGL(kern<MT()>, ...); })
-template <class F>
-inline void dispatch_mt(int mt, F&& f) {
-  switch (mt) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    default: f(std::integral_constant<int, 8>{}); break;
-  }
 }
 
 }  // namespace hw3

@@ -30,13 +30,13 @@ namespace pw1 {
 
 using corr::v4f;
 using hw3::w_pitch;
+using node::pitch_for;
 
 constexpr int kCK = 32;                      // input channels per staged chunk
 constexpr int kTP = 64;                      // pixels per workgroup
 constexpr int kXP = kTP + 16;                // 80 == 16 mod 32
 
 inline int chunks_for(int Cin) { return (Cin + kCK - 1) / kCK; }
-inline int pitch_for(int rows) { return rows <= 64 ? 64 : (rows + 127) / 128 * 128; }      // whole workgroups of any MT
 inline size_t image_floats(int Cin, int rows) { return static_cast<size_t>(chunks_for(Cin)) * kCK * pitch_for(rows); }
 
 struct Geom {
@@ -176,6 +176,31 @@ inline hw3::Launch launch_rule(Geom& g, int B, unsigned long long min_blocks) {
   while (mt > 1 && tiles * groups(mt) < min_blocks) mt /= 2;
   g.groups = groups(mt);
   return hw3::Launch{mt, corr::grid_blocks(tiles * g.groups)};
+}
+
+// The pointwise projection: channel gc of `x` in place through its strides -- GATED: times gate[b, gc] ([B][Cin]) while it is staged,
+// so a gated map is never written -- finished by the affine epilogue.
+template <bool GATED>
+struct Project {
+  Geom g;
+  node::Plane<const float> x;
+  const float* gate;
+  node::Affine<ACT_NONE, GATED ? 1 : node::kRuntime> ep;      // no activation; the gated use always has a residual
+
+  __device__ __forceinline__ auto source(int b) const {
+    return [px = x.at(b, 0), pg = GATED ? gate + static_cast<long long>(b) * g.Cin : nullptr, x_cs = x.cs](int gc, long long p) {
+      (void)pg;
+      if constexpr (GATED) return px[gc * x_cs + p] * pg[gc];
+      else return px[gc * x_cs + p];
+    };
+  }
+  __device__ __forceinline__ auto sink(int b, long long p) const { return ep.writer(b, p); }
+};
+
+// a plane's pixels are one 32-bit count here
+inline int check_plane(const char* who, long long N) {
+  TS_REQUIRE(N <= 0x7fffffffll, TS_ERR_UNSUPPORTED, "%s: a plane of 2^31 pixels or more", who);
+  return TS_OK;
 }
 
 }  // namespace pw1

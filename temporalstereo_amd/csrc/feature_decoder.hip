@@ -15,31 +15,27 @@
 // ascending order, the fine pixels whose two source indices (ts::lin_src again, evaluated per candidate: the forward's own
 // predicate) include it.  No atomics: bit-reproducible.
 #include "bilinear.hpp"
-#include "conv_common.hpp"
 #include "conv_hw3.hpp"
 
 namespace {
 
 constexpr int kMaxC = 512;                   // Cu + Cs and Cout
 constexpr int kFlush = 4;                    // chunks (32 input channels, 288 products) per block of the blocked summation
-constexpr int kMaxAxis = 1 << 20;
-constexpr int kGridCap = 4096;               // blocks of the grid-stride element kernels
+using node::kGridCap;
+using node::kMaxAxis;
+using node::pitch_for;
 using ts::strides_ok;
-
-inline int pitch_for(int rows) { return rows <= 64 ? 64 : (rows + 127) / 128 * 128; }      // whole workgroups of any MT
 
 struct Dec {
   hw3::Geom g;              // rows: Cout
   const float* up;          // source of channels [0, Cu), [B,Cu,h,w], read through the resize
   const float* skip;        // source of channels [Cu, Cu + Cs), [B,Cs,H,W]
-  const float* scale;
-  const float* shift;
-  float* y;
-  int Cu, h, w_in, act;
+  node::Affine<> ep;        // act(sum * scale + shift), no residual
+  int Cu, h, w_in;
   float sh, sw;             // source steps of the resize
-  long long up_bs, up_cs, skip_bs, skip_cs, y_bs, y_cs;
+  long long up_bs, up_cs, skip_bs, skip_cs;
 
-  // the lambdas hold copies of what they use, never `this`: a store through y then cannot be taken to change a field
+  // the lambda holds copies of what it uses, never `this`: a store through y then cannot be taken to change a field
   __device__ __forceinline__ auto source(int b) const {
     return [pu = up + b * up_bs, ps = skip + b * skip_bs, Cu = Cu, up_cs = up_cs, skip_cs = skip_cs, h = h, w_in = w_in, sh = sh, sw = sw,
             W = g.W](int gc, int gy, int gx) {
@@ -47,13 +43,7 @@ struct Dec {
       return ps[(gc - Cu) * skip_cs + hw3::pixel_at(gy, gx, W)];
     };
   }
-  __device__ __forceinline__ auto sink(int b, int gy, int gx) const {
-    return [py = y + b * y_bs + hw3::pixel_at(gy, gx, g.W), y_cs = y_cs, scale = scale, shift = shift, act = act](int row, float v) {
-      if (scale) v *= scale[row];
-      if (shift) v += shift[row];
-      py[row * y_cs] = act == ACT_SILU ? silu_fast(v) : v;
-    };
-  }
+  __device__ __forceinline__ auto sink(int b, int gy, int gx) const { return ep.writer(b, hw3::pixel_at(gy, gx, g.W)); }
 };
 
 template <int MT>
@@ -128,38 +118,32 @@ extern "C" int ts_decoder_conv_fwd(const float* up, const float* skip, const flo
                                    int B, int Cu, int Cs, int Cout, int h, int w, int H, int W, int act, long long up_bstride,
                                    long long up_cstride, long long skip_bstride, long long skip_cstride, long long y_bstride,
                                    long long y_cstride, void* stream) {
-  TS_REQUIRE(B > 0 && Cu >= 0 && Cs > 0 && Cout > 0 && H > 0 && W > 0 && (Cu == 0 || (h > 0 && w > 0)), TS_ERR_SHAPE,
-             "decoder_conv_fwd: non-positive size");
-  TS_REQUIRE(act == ACT_NONE || act == ACT_SILU, TS_ERR_SHAPE, "decoder_conv_fwd: unknown activation %d", act);
+  const char* who = "decoder_conv_fwd";
+  TS_REQUIRE(B > 0 && Cu >= 0 && Cs > 0 && Cout > 0 && H > 0 && W > 0 && (Cu == 0 || (h > 0 && w > 0)), TS_ERR_SHAPE, "%s: non-positive size", who);
+  TS_REQUIRE(act == ACT_NONE || act == ACT_SILU, TS_ERR_SHAPE, "%s: unknown activation %d", who, act);
   const long long HW = static_cast<long long>(H) * W;
-  TS_REQUIRE(strides_ok(B, Cu, static_cast<long long>(h) * w, up_bstride, up_cstride), TS_ERR_SHAPE,
-             "decoder_conv_fwd: up strides %lld / %lld overlap", up_bstride, up_cstride);
-  TS_REQUIRE(strides_ok(B, Cs, HW, skip_bstride, skip_cstride), TS_ERR_SHAPE, "decoder_conv_fwd: skip strides %lld / %lld overlap",
-             skip_bstride, skip_cstride);
-  TS_REQUIRE(strides_ok(B, Cout, HW, y_bstride, y_cstride), TS_ERR_SHAPE, "decoder_conv_fwd: y strides %lld / %lld overlap", y_bstride,
-             y_cstride);
-  TS_REQUIRE(Cu + Cs <= kMaxC && Cout <= kMaxC, TS_ERR_UNSUPPORTED, "decoder_conv_fwd: Cu + Cs = %d / Cout = %d above %d", Cu + Cs, Cout, kMaxC);
-  TS_REQUIRE(B < kMaxAxis && H < kMaxAxis && W < kMaxAxis && h < kMaxAxis && w < kMaxAxis, TS_ERR_UNSUPPORTED,
-             "decoder_conv_fwd: an axis of 2^20 or more");
+  const node::Operand U{"up", up, Cu, static_cast<long long>(h) * w, up_bstride, up_cstride, node::IN},
+      S{"skip", skip, Cs, HW, skip_bstride, skip_cstride, node::IN}, Y{"y", y, Cout, HW, y_bstride, y_cstride, node::OUT};
   Dec p;
-  p.g = hw3::geom(w_l, Cu + Cs, Cout, H, W, pitch_for(Cout));
+  p.up = up; p.skip = skip;
+  p.Cu = Cu; p.h = Cu ? h : 1; p.w_in = Cu ? w : 1;
+  p.sh = ts::ac_scale(p.h, H); p.sw = ts::ac_scale(p.w_in, W);
+  p.up_bs = up_bstride; p.up_cs = up_cstride; p.skip_bs = skip_bstride; p.skip_cs = skip_cstride;
+  p.ep = {scale, shift, act, {nullptr, 0, 0}, {y, y_bstride, y_cstride}};
+  auto envelope = [&] {
+    TS_REQUIRE(Cu + Cs <= kMaxC && Cout <= kMaxC, TS_ERR_UNSUPPORTED, "%s: Cu + Cs = %d / Cout = %d above %d", who, Cu + Cs, Cout, kMaxC);
+    return TS_OK;
+  };
   // A grid of fewer than two workgroups per compute unit is cut finer along the rows (hw3::launch_rule): a lone workgroup has nothing
   // to hide its staging behind (measured at 1, 2 and 4 per compute unit: batch 2 of the 544 x 960 decoder 1385 / 1218 / 1187 us,
   // batch 8 3194 / 3175 / 3239 us).
-  const hw3::Launch l = hw3::launch_rule(p.g, B, 2ull * ts::kNumCU);
-  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "decoder_conv_fwd: grid too large");
-  if (Cu > 0) TS_REQUIRE_PTR(up);
-  TS_REQUIRE_PTR(skip);
-  TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(y);
-  TS_REQUIRE_ALIGNED(w_l);
-  p.up = up; p.skip = skip; p.scale = scale; p.shift = shift; p.y = y;
-  p.Cu = Cu; p.h = Cu ? h : 1; p.w_in = Cu ? w : 1; p.act = act;
-  p.sh = ts::ac_scale(p.h, H); p.sw = ts::ac_scale(p.w_in, W);
-  p.up_bs = up_bstride; p.up_cs = up_cstride; p.skip_bs = skip_bstride; p.skip_cs = skip_cstride; p.y_bs = y_bstride; p.y_cs = y_cstride;
-  hw3::dispatch_mt(l.mt, [&](auto MT) {
-    hipLaunchKernelGGL((decoder_conv_kernel<MT()>), dim3(l.blocks), dim3(256), 0, ts::as_stream(stream), p);
-  });
-  return ts::launched("decoder_conv_kernel");
+  return node::launch(
+      who, "decoder_conv_kernel", B, {U, S, Y}, {}, w_l, {B, H, W, h, w}, envelope,
+      [&] {          // the geometry behind the envelope and the axes
+        p.g = hw3::geom(w_l, Cu + Cs, Cout, H, W, pitch_for(Cout));
+        return hw3::launch_rule(p.g, B, 2ull * ts::kNumCU);
+      },
+      [&](auto MT, dim3 grid) { hipLaunchKernelGGL((decoder_conv_kernel<MT()>), grid, dim3(256), 0, ts::as_stream(stream), p); });
 }
 
 extern "C" int ts_resize_bilinear_bwd(const float* dy, float* dx, int B, int C, int h, int w, int H, int W, long long dy_bstride,

@@ -28,8 +28,6 @@
 // blocks: 48 and 64 channels at stride 1 are two blocks, 24 and 48 at stride 2 (96 and 192 phase channels) three and six.
 // The projection is conv_pw1.hpp's core with FLUSH = 8 (mbconv.hip's): chains of 256 products, then a chain of blocks; Cmid = 96, 192
 // and 256 are one chain.  An output's chains run over the channels in order whatever MT, `groups` and the batch are.
-#include "act_fast.hpp"
-#include "conv_common.hpp"
 #include "conv_pw1.hpp"
 
 namespace {
@@ -38,27 +36,20 @@ constexpr int kMaxC = 512;                   // the 3x3's core channels (Cin at 
 constexpr int kMaxMid = 2048;                // the projection's Cin
 constexpr int kFlush3 = 4;                   // the 3x3: chunks (32 core channels, 288 products) per block of the blocked summation
 constexpr int kFlush1 = 8;                   // the 1x1: chunks (256 input channels) per block
-constexpr int kMaxAxis = 1 << 20;
-constexpr int kGridCap = 4096;               // blocks of the grid-stride weight layout
-using ts::strides_ok;
+using node::pitch_for;
 
-inline int pitch_for(int rows) { return rows <= 64 ? 64 : (rows + 127) / 128 * 128; }      // whole workgroups of any MT
 inline int core_channels(int Cin, int stride) { return stride == 2 ? 4 * Cin : Cin; }
 
 template <int S>
 struct Conv3 {
   hw3::Geom g;              // Cin: core channels; H, W: the OUTPUT plane; rows: Cout
-  const float* x;           // [B,Cin,Hin,Win]
-  const float* scale;
-  const float* shift;
-  const float* res;         // [B,Cout,H,W] or NULL
-  float* y;
-  int Hin, Win, act;
-  long long x_bs, x_cs, r_bs, r_cs, y_bs, y_cs;
+  node::Plane<const float> x;      // [B,Cin,Hin,Win]
+  node::Affine<> ep;        // act(sum * scale + shift) + residual [B,Cout,H,W]
+  int Hin, Win;
 
-  // the lambdas hold copies of what they use, never `this`: a store through y then cannot be taken to change a field
+  // the lambda holds copies of what it uses, never `this`: a store through y then cannot be taken to change a field
   __device__ __forceinline__ auto source(int b) const {
-    return [px = x + b * x_bs, x_cs = x_cs, Hin = Hin, Win = Win](int gc, int gy, int gx) {
+    return [px = x.at(b, 0), x_cs = x.cs, Hin = Hin, Win = Win](int gc, int gy, int gx) {
       if constexpr (S == 1) {
         (void)Hin;
         return px[gc * x_cs + hw3::pixel_at(gy, gx, Win)];
@@ -68,45 +59,15 @@ struct Conv3 {
       }
     };
   }
-  __device__ __forceinline__ auto sink(int b, int gy, int gx) const {
-    const long long at = hw3::pixel_at(gy, gx, g.W);
-    return [py = y + b * y_bs + at, pr = res ? res + b * r_bs + at : nullptr, y_cs = y_cs, r_cs = r_cs, scale = scale, shift = shift,
-            act = act](int row, float v) {
-      if (scale) v *= scale[row];
-      if (shift) v += shift[row];
-      if (act == ACT_SILU) v = silu_fast(v);
-      if (pr) v += pr[row * r_cs];
-      py[row * y_cs] = v;
-    };
-  }
+  __device__ __forceinline__ auto sink(int b, int gy, int gx) const { return ep.writer(b, hw3::pixel_at(gy, gx, g.W)); }
 };
 
-struct FusedProject {
-  pw1::Geom g;              // Cin: Cmid, rows: Cout
-  const float* x;
-  const float* scale;
-  const float* shift;
-  const float* res;         // or NULL
-  float* y;
-  long long x_bs, x_cs, r_bs, r_cs, y_bs, y_cs;
-
-  __device__ __forceinline__ auto source(int b) const {
-    return [px = x + b * x_bs, x_cs = x_cs](int gc, long long p) { return px[gc * x_cs + p]; };
-  }
-  __device__ __forceinline__ auto sink(int b, long long p) const {
-    return [py = y + b * y_bs + p, pr = res ? res + b * r_bs + p : nullptr, y_cs = y_cs, r_cs = r_cs, scale = scale, shift = shift](int row, float v) {
-      if (scale) v *= scale[row];
-      if (shift) v += shift[row];
-      if (pr) v += pr[row * r_cs];
-      py[row * y_cs] = v;
-    };
-  }
-};
+using Project = pw1::Project<false>;     // Cin: Cmid, rows: Cout
 
 template <int MT, int S>
 __global__ void __launch_bounds__(256) conv3x3_kernel(const Conv3<S> p) { hw3::conv_tile<MT, kFlush3>(p); }
 template <int MT>
-__global__ void __launch_bounds__(256) fused_project_kernel(const FusedProject p) { pw1::conv_tile<MT, kFlush1>(p); }
+__global__ void __launch_bounds__(256) fused_project_kernel(const Project p) { pw1::conv_tile<MT, kFlush1>(p); }
 
 // the weight of tap t (0..2: offsets -1, 0, +1) of a phase along one axis, as an index into the 3 framework weights, or -1: zero
 __device__ __forceinline__ int phase_tap(int phase, int t) { return phase == 0 ? (t == 1 ? 1 : -1) : (t == 0 ? 0 : t == 1 ? 2 : -1); }
@@ -132,15 +93,6 @@ __global__ void __launch_bounds__(256) conv3x3_weight_layout_kernel(const float*
   }
 }
 
-// Whether the bounding extents [p, p + (B - 1) bs + (C - 1) cs + vol) of two strided [B][C][vol] operands are apart.  The test is on
-// extents, not elements: two interleaved channel slices of one wider buffer are refused although no element is shared.
-inline bool disjoint(const float* a, int Ba, int Ca, long long va, long long abs_, long long acs, const float* b, int Bb, int Cb,
-                     long long vb, long long bbs, long long bcs) {
-  const float* ae = a + (Ba - 1) * abs_ + (Ca - 1) * acs + va;
-  const float* be = b + (Bb - 1) * bbs + (Cb - 1) * bcs + vb;
-  return ae <= b || be <= a;
-}
-
 }  // namespace
 
 extern "C" size_t ts_conv3x3_s_weight_bytes(int Cin, int Cout, int stride) {
@@ -157,7 +109,7 @@ extern "C" int ts_conv3x3_s_weight_layout(const float* w, float* w_l, int Cin, i
   TS_REQUIRE_ALIGNED(w_l);
   const int pitch = pitch_for(Cout);
   const size_t total = hw3::image_floats(core_channels(Cin, stride), pitch);           // at most 64 x 72 x 512
-  hipLaunchKernelGGL(conv3x3_weight_layout_kernel, dim3(ts::blocks_for(static_cast<long long>(total), kGridCap)), dim3(256), 0,
+  hipLaunchKernelGGL(conv3x3_weight_layout_kernel, dim3(ts::blocks_for(static_cast<long long>(total), node::kGridCap)), dim3(256), 0,
                      ts::as_stream(stream), w, w_l, Cin, Cout, stride, pitch, static_cast<int>(total));
   return ts::launched("conv3x3_weight_layout_kernel");
 }
@@ -169,68 +121,49 @@ extern "C" int ts_conv3x3_s_fwd(const float* x, const float* w_l, const float* s
   TS_REQUIRE(stride == 1 || stride == 2, TS_ERR_SHAPE, "conv3x3_s_fwd: stride %d is neither 1 nor 2", stride);
   TS_REQUIRE(act == ACT_NONE || act == ACT_SILU, TS_ERR_SHAPE, "conv3x3_s_fwd: unknown activation %d", act);
   TS_REQUIRE(residual == nullptr || stride == 1, TS_ERR_SHAPE, "conv3x3_s_fwd: a residual is taken at stride 1 only");
+  const char* who = "conv3x3_s_fwd";
   const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const long long HW = static_cast<long long>(H) * W, HWo = static_cast<long long>(Ho) * Wo;
-  TS_REQUIRE(strides_ok(B, Cin, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "conv3x3_s_fwd: x strides %lld / %lld overlap", x_bstride, x_cstride);
-  TS_REQUIRE(residual == nullptr || strides_ok(B, Cout, HWo, r_bstride, r_cstride), TS_ERR_SHAPE,
-             "conv3x3_s_fwd: residual strides %lld / %lld overlap", r_bstride, r_cstride);
-  TS_REQUIRE(strides_ok(B, Cout, HWo, y_bstride, y_cstride), TS_ERR_SHAPE, "conv3x3_s_fwd: y strides %lld / %lld overlap", y_bstride, y_cstride);
   const int Cc = core_channels(Cin <= kMaxC ? Cin : kMaxC + 1, stride);
-  TS_REQUIRE(B < kMaxAxis && H < kMaxAxis && W < kMaxAxis, TS_ERR_UNSUPPORTED, "conv3x3_s_fwd: an axis of 2^20 or more");
-  TS_REQUIRE(Cc <= kMaxC && Cout <= kMaxC, TS_ERR_UNSUPPORTED, "conv3x3_s_fwd: %d core channels (Cin = %d, stride %d) / Cout = %d above %d", Cc,
-             Cin, stride, Cout, kMaxC);
-  hw3::Geom g = hw3::geom(w_l, Cc, Cout, Ho, Wo, pitch_for(Cout));
-  const hw3::Launch l = hw3::launch_rule(g, B, 2ull * ts::kNumCU);           // as the decoder: fewer than two workgroups per compute unit are cut finer along the rows
-  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "conv3x3_s_fwd: grid too large");
-  TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(y);
-  TS_REQUIRE_ALIGNED(w_l);
-  TS_REQUIRE(disjoint(x, B, Cin, HW, x_bstride, x_cstride, y, B, Cout, HWo, y_bstride, y_cstride), TS_ERR_SHAPE,
-             "conv3x3_s_fwd: y overlaps x (an output's neighbours are read by other workgroups)");
-  TS_REQUIRE(residual == nullptr || (residual == y && r_bstride == y_bstride && r_cstride == y_cstride) ||
-                 disjoint(residual, B, Cout, HWo, r_bstride, r_cstride, y, B, Cout, HWo, y_bstride, y_cstride),
-             TS_ERR_SHAPE, "conv3x3_s_fwd: y overlaps the residual without being its own elements");
+  const node::Operand X{"x", x, Cin, HW, x_bstride, x_cstride, node::IN},
+      R{"residual", residual, residual ? Cout : 0, HWo, r_bstride, r_cstride, node::RES}, Y{"y", y, Cout, HWo, y_bstride, y_cstride, node::OUT};
+  hw3::Geom g;
+  auto envelope = [&] {
+    TS_REQUIRE(Cc <= kMaxC && Cout <= kMaxC, TS_ERR_UNSUPPORTED, "%s: %d core channels (Cin = %d, stride %d) / Cout = %d above %d", who, Cc, Cin, stride,
+               Cout, kMaxC);
+    return TS_OK;
+  };
+  // as the decoder: fewer than two workgroups per compute unit are cut finer along the rows
+  auto rule = [&] {          // the geometry behind the envelope and the axes
+    g = hw3::geom(w_l, Cc, Cout, Ho, Wo, pitch_for(Cout));
+    return hw3::launch_rule(g, B, 2ull * ts::kNumCU);
+  };
   auto run = [&](auto S) {
-    Conv3<S()> p;
-    p.g = g; p.x = x; p.scale = scale; p.shift = shift; p.res = residual; p.y = y;
-    p.Hin = H; p.Win = W; p.act = act;
-    p.x_bs = x_bstride; p.x_cs = x_cstride; p.r_bs = r_bstride; p.r_cs = r_cstride; p.y_bs = y_bstride; p.y_cs = y_cstride;
-    hw3::dispatch_mt(l.mt, [&](auto MT) {
-      hipLaunchKernelGGL((conv3x3_kernel<MT(), S()>), dim3(l.blocks), dim3(256), 0, ts::as_stream(stream), p);
+    return node::launch(who, "conv3x3_kernel", B, {R, X, Y}, {}, w_l, {B, H, W}, envelope, rule, [&](auto MT, dim3 grid) {
+      const Conv3<S()> p{g, X.plane(), {scale, shift, act, R.plane(), {y, y_bstride, y_cstride}}, H, W};
+      hipLaunchKernelGGL((conv3x3_kernel<MT(), S()>), grid, dim3(256), 0, ts::as_stream(stream), p);
     });
   };
-  if (stride == 1) run(std::integral_constant<int, 1>{});
-  else run(std::integral_constant<int, 2>{});
-  return ts::launched("conv3x3_kernel");
+  return stride == 1 ? run(std::integral_constant<int, 1>{}) : run(std::integral_constant<int, 2>{});
 }
 
 extern "C" int ts_fused_project_fwd(const float* x, const float* w_l, const float* scale, const float* shift, const float* residual,
                                     float* y, int B, int Cmid, int Cout, int H, int W, long long x_bstride, long long x_cstride,
                                     long long r_bstride, long long r_cstride, long long y_bstride, long long y_cstride, void* stream) {
-  TS_REQUIRE(B > 0 && Cmid > 0 && Cout > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "fused_project_fwd: non-positive size");
+  const char* who = "fused_project_fwd";
+  TS_REQUIRE(B > 0 && Cmid > 0 && Cout > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
   const long long HW = static_cast<long long>(H) * W;
-  TS_REQUIRE(strides_ok(B, Cmid, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "fused_project_fwd: x strides %lld / %lld overlap", x_bstride, x_cstride);
-  TS_REQUIRE(residual == nullptr || strides_ok(B, Cout, HW, r_bstride, r_cstride), TS_ERR_SHAPE,
-             "fused_project_fwd: residual strides %lld / %lld overlap", r_bstride, r_cstride);
-  TS_REQUIRE(strides_ok(B, Cout, HW, y_bstride, y_cstride), TS_ERR_SHAPE, "fused_project_fwd: y strides %lld / %lld overlap", y_bstride, y_cstride);
-  TS_REQUIRE(Cout <= kMaxC && Cmid <= kMaxMid, TS_ERR_UNSUPPORTED, "fused_project_fwd: Cout = %d above %d or Cmid = %d above %d", Cout, kMaxC, Cmid,
-             kMaxMid);
-  TS_REQUIRE(B < kMaxAxis && H < kMaxAxis && W < kMaxAxis && HW <= 0x7fffffffll, TS_ERR_UNSUPPORTED,
-             "fused_project_fwd: an axis of 2^20 or more, or a plane of 2^31 pixels or more");
-  FusedProject p;
-  p.g = pw1::geom(w_l, Cmid, Cout, HW);
-  const hw3::Launch l = pw1::launch_rule(p.g, B, 2ull * ts::kNumCU);
-  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "fused_project_fwd: grid too large");
-  TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(y);
-  TS_REQUIRE_ALIGNED(w_l);
-  TS_REQUIRE(disjoint(x, B, Cmid, HW, x_bstride, x_cstride, y, B, Cout, HW, y_bstride, y_cstride), TS_ERR_SHAPE,
-             "fused_project_fwd: y overlaps x (a pixel's channels are read by other workgroups)");
-  TS_REQUIRE(residual == nullptr || (residual == y && r_bstride == y_bstride && r_cstride == y_cstride) ||
-                 disjoint(residual, B, Cout, HW, r_bstride, r_cstride, y, B, Cout, HW, y_bstride, y_cstride),
-             TS_ERR_SHAPE, "fused_project_fwd: y overlaps the residual without being its own elements");
-  p.x = x; p.scale = scale; p.shift = shift; p.res = residual; p.y = y;
-  p.x_bs = x_bstride; p.x_cs = x_cstride; p.r_bs = r_bstride; p.r_cs = r_cstride; p.y_bs = y_bstride; p.y_cs = y_cstride;
-  hw3::dispatch_mt(l.mt, [&](auto MT) {
-    hipLaunchKernelGGL((fused_project_kernel<MT()>), dim3(l.blocks), dim3(256), 0, ts::as_stream(stream), p);
-  });
-  return ts::launched("fused_project_kernel");
+  const node::Operand X{"x", x, Cmid, HW, x_bstride, x_cstride, node::IN},
+      R{"residual", residual, residual ? Cout : 0, HW, r_bstride, r_cstride, node::RES}, Y{"y", y, Cout, HW, y_bstride, y_cstride, node::OUT};
+  Project p;
+  p.x = X.plane(); p.gate = nullptr;
+  p.ep = {scale, shift, ACT_NONE, R.plane(), {y, y_bstride, y_cstride}};
+  auto envelope = [&] {
+    TS_REQUIRE(Cout <= kMaxC && Cmid <= kMaxMid, TS_ERR_UNSUPPORTED, "%s: Cout = %d above %d or Cmid = %d above %d", who, Cout, kMaxC, Cmid, kMaxMid);
+    return pw1::check_plane(who, HW);
+  };
+  return node::launch(
+      who, "fused_project_kernel", B, {R, X, Y}, {}, w_l, {B, H, W}, envelope,
+      [&] { p.g = pw1::geom(w_l, Cmid, Cout, HW); return pw1::launch_rule(p.g, B, 2ull * ts::kNumCU); },
+      [&](auto MT, dim3 grid) { hipLaunchKernelGGL((fused_project_kernel<MT()>), grid, dim3(256), 0, ts::as_stream(stream), p); });
 }

@@ -26,8 +26,6 @@
 // ascending order, then the butterfly -- with 32 loads per lane in flight), then a thread takes one expand row as one ascending chain.
 // The reduce step is repeated by the slices of a batch element (Cmid / 256 times: 444 KB from L2 at the widest) rather than made a
 // launch of its own.
-#include "act_fast.hpp"
-#include "conv_common.hpp"
 #include "conv_pw1.hpp"
 #include "reduce.hpp"
 
@@ -36,10 +34,10 @@ namespace {
 constexpr int kMaxC = 512;                   // the block's width (expand's Cin, project's Cout) and the squeeze width Cr
 constexpr int kMaxMid = 2048;                // the expanded width
 constexpr int kFlush = 8;                    // chunks (256 input channels) per block of the blocked summation
-constexpr int kMaxAxis = 1 << 20;
-constexpr int kGridCap = 4096;               // blocks of the grid-stride element kernels
 constexpr int kDR = 8, kDC = 64;             // depthwise tile
 constexpr int kDP = kDC + 8;                 // LDS row pitch: the interior starts at column 4 (16-byte aligned), halos at 3 and 4 + width
+using node::kGridCap;
+using node::kMaxAxis;
 using ts::strides_ok;
 
 // ---------------------------------------------------------------------------------------------------------------- pointwise
@@ -47,55 +45,31 @@ struct Expand {
   pw1::Geom g;              // Cin: C, rows: Cmid
   const float* mem;         // source of channels [0, mc)
   const float* inp;         // source of channels [mc, C)
-  const float* scale;
-  const float* shift;
-  float* y;
+  node::Affine<ACT_SILU, 0> ep;      // silu(sum * scale + shift), never a residual
   int mc;
-  long long mem_bs, mem_cs, in_bs, in_cs, y_bs, y_cs;
+  long long mem_bs, mem_cs, in_bs, in_cs;
 
-  // the lambdas hold copies of what they use, never `this`: a store through y then cannot be taken to change a field
+  // the lambda holds copies of what it uses, never `this`: a store through y then cannot be taken to change a field
   __device__ __forceinline__ auto source(int b) const {
     return [pm = mem + b * mem_bs, pi = inp + b * in_bs, mc = mc, mem_cs = mem_cs, in_cs = in_cs](int gc, long long p) {
       return gc < mc ? pm[gc * mem_cs + p] : pi[gc * in_cs + p];
     };
   }
-  __device__ __forceinline__ auto sink(int b, long long p) const {
-    return [py = y + b * y_bs + p, y_cs = y_cs, scale = scale, shift = shift](int row, float v) {
-      if (scale) v *= scale[row];
-      if (shift) v += shift[row];
-      py[row * y_cs] = silu_fast(v);
-    };
-  }
+  __device__ __forceinline__ auto sink(int b, long long p) const { return ep.writer(b, p); }
 };
 
-struct Project {
-  pw1::Geom g;              // Cin: Cmid, rows: C
-  const float* x;
-  const float* gate;        // [B][Cmid]
-  const float* scale;
-  const float* shift;
-  const float* res;
-  float* y;
-  long long x_bs, x_cs, r_bs, r_cs, y_bs, y_cs;
-
-  __device__ __forceinline__ auto source(int b) const {
-    return [px = x + b * x_bs, pg = gate + static_cast<long long>(b) * g.Cin, x_cs = x_cs](int gc, long long p) {
-      return px[gc * x_cs + p] * pg[gc];
-    };
-  }
-  __device__ __forceinline__ auto sink(int b, long long p) const {
-    return [py = y + b * y_bs + p, pr = res + b * r_bs + p, y_cs = y_cs, r_cs = r_cs, scale = scale, shift = shift](int row, float v) {
-      if (scale) v *= scale[row];
-      if (shift) v += shift[row];
-      py[row * y_cs] = v + pr[row * r_cs];
-    };
-  }
-};
+using Project = pw1::Project<true>;      // Cin: Cmid, rows: C; the gate is [B][Cmid]
 
 template <int MT>
 __global__ void __launch_bounds__(256) expand_kernel(const Expand p) { pw1::conv_tile<MT, kFlush>(p); }
 template <int MT>
 __global__ void __launch_bounds__(256) project_kernel(const Project p) { pw1::conv_tile<MT, kFlush>(p); }
+
+// the block's envelope, and the pointwise core's plane limit
+int check_block(const char* who, int C, int Cmid, long long HW) {
+  TS_REQUIRE(C <= kMaxC && Cmid <= kMaxMid, TS_ERR_UNSUPPORTED, "%s: C = %d above %d or Cmid = %d above %d", who, C, kMaxC, Cmid, kMaxMid);
+  return pw1::check_plane(who, HW);
+}
 
 // ---------------------------------------------------------------------------------------------------------------- depthwise
 // the sum of a workgroup's 256 values in a fixed order, valid in every thread: butterfly per wave, then the four waves in order
@@ -322,62 +296,39 @@ extern "C" int ts_mbconv_weight_layout(const float* w, float* w_l, int Cin, int 
 extern "C" int ts_mbconv_expand_fwd(const float* memory, const float* input, const float* w_l, const float* scale, const float* shift,
                                     float* y, int B, int C, int mc, int Cmid, int H, int W, long long mem_bstride, long long mem_cstride,
                                     long long in_bstride, long long in_cstride, long long y_bstride, long long y_cstride, void* stream) {
-  TS_REQUIRE(B > 0 && C > 0 && Cmid > 0 && H > 0 && W > 0 && mc >= 0 && mc <= C, TS_ERR_SHAPE, "mbconv_expand_fwd: non-positive size or mc outside [0, C]");
+  const char* who = "mbconv_expand_fwd";
+  TS_REQUIRE(B > 0 && C > 0 && Cmid > 0 && H > 0 && W > 0 && mc >= 0 && mc <= C, TS_ERR_SHAPE, "%s: non-positive size or mc outside [0, C]", who);
   const long long HW = static_cast<long long>(H) * W;
   const int seam = memory ? mc : 0;                              // no memory: the first frame reads `input` alone
-  TS_REQUIRE(strides_ok(B, seam, HW, mem_bstride, mem_cstride), TS_ERR_SHAPE, "mbconv_expand_fwd: memory strides %lld / %lld overlap",
-             mem_bstride, mem_cstride);
-  TS_REQUIRE(strides_ok(B, C, HW, in_bstride, in_cstride), TS_ERR_SHAPE, "mbconv_expand_fwd: input strides %lld / %lld overlap", in_bstride,
-             in_cstride);
-  TS_REQUIRE(strides_ok(B, Cmid, HW, y_bstride, y_cstride), TS_ERR_SHAPE, "mbconv_expand_fwd: y strides %lld / %lld overlap", y_bstride,
-             y_cstride);
-  TS_REQUIRE(C <= kMaxC && Cmid <= kMaxMid, TS_ERR_UNSUPPORTED, "mbconv_expand_fwd: C = %d above %d or Cmid = %d above %d", C, kMaxC, Cmid,
-             kMaxMid);
-  TS_REQUIRE(B < kMaxAxis && H < kMaxAxis && W < kMaxAxis && HW <= 0x7fffffffll, TS_ERR_UNSUPPORTED,
-             "mbconv_expand_fwd: an axis of 2^20 or more, or a plane of 2^31 pixels or more");
+  const node::Operand M{"memory", memory, seam, HW, mem_bstride, mem_cstride, node::IN}, I{"input", input, C, HW, in_bstride, in_cstride, node::IN},
+      Y{"y", y, Cmid, HW, y_bstride, y_cstride, node::OUT};
   Expand p;
-  p.g = pw1::geom(w_l, C, Cmid, HW);
+  p.mem = memory; p.inp = input; p.mc = seam;
+  p.mem_bs = mem_bstride; p.mem_cs = mem_cstride; p.in_bs = in_bstride; p.in_cs = in_cstride;
+  p.ep = {scale, shift, ACT_SILU, {nullptr, 0, 0}, {y, y_bstride, y_cstride}};
   // as the decoder: a grid of fewer than two workgroups per compute unit is cut finer along the rows
-  const hw3::Launch l = pw1::launch_rule(p.g, B, 2ull * ts::kNumCU);
-  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "mbconv_expand_fwd: grid too large");
-  TS_REQUIRE_PTR(input); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(y);
-  TS_REQUIRE_ALIGNED(w_l);
-  p.mem = memory; p.inp = input; p.scale = scale; p.shift = shift; p.y = y; p.mc = seam;
-  p.mem_bs = mem_bstride; p.mem_cs = mem_cstride; p.in_bs = in_bstride; p.in_cs = in_cstride; p.y_bs = y_bstride; p.y_cs = y_cstride;
-  hw3::dispatch_mt(l.mt, [&](auto MT) {
-    hipLaunchKernelGGL((expand_kernel<MT()>), dim3(l.blocks), dim3(256), 0, ts::as_stream(stream), p);
-  });
-  return ts::launched("mbconv_expand_kernel");
+  return node::launch(
+      who, "mbconv_expand_kernel", B, {M, I, Y}, {}, w_l, {B, H, W}, [&] { return check_block(who, C, Cmid, HW); },
+      [&] { p.g = pw1::geom(w_l, C, Cmid, HW); return pw1::launch_rule(p.g, B, 2ull * ts::kNumCU); },      // the geometry behind the envelope and the axes
+      [&](auto MT, dim3 grid) { hipLaunchKernelGGL((expand_kernel<MT()>), grid, dim3(256), 0, ts::as_stream(stream), p); });
 }
 
 extern "C" int ts_mbconv_project_fwd(const float* x, const float* gate, const float* w_l, const float* scale, const float* shift,
                                      const float* residual, float* y, int B, int Cmid, int C, int H, int W, long long x_bstride,
                                      long long x_cstride, long long r_bstride, long long r_cstride, long long y_bstride,
                                      long long y_cstride, void* stream) {
-  TS_REQUIRE(B > 0 && C > 0 && Cmid > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "mbconv_project_fwd: non-positive size");
+  const char* who = "mbconv_project_fwd";
+  TS_REQUIRE(B > 0 && C > 0 && Cmid > 0 && H > 0 && W > 0, TS_ERR_SHAPE, "%s: non-positive size", who);
   const long long HW = static_cast<long long>(H) * W;
-  TS_REQUIRE(strides_ok(B, Cmid, HW, x_bstride, x_cstride), TS_ERR_SHAPE, "mbconv_project_fwd: x strides %lld / %lld overlap", x_bstride,
-             x_cstride);
-  TS_REQUIRE(strides_ok(B, C, HW, r_bstride, r_cstride), TS_ERR_SHAPE, "mbconv_project_fwd: residual strides %lld / %lld overlap", r_bstride,
-             r_cstride);
-  TS_REQUIRE(strides_ok(B, C, HW, y_bstride, y_cstride), TS_ERR_SHAPE, "mbconv_project_fwd: y strides %lld / %lld overlap", y_bstride,
-             y_cstride);
-  TS_REQUIRE(C <= kMaxC && Cmid <= kMaxMid, TS_ERR_UNSUPPORTED, "mbconv_project_fwd: C = %d above %d or Cmid = %d above %d", C, kMaxC, Cmid,
-             kMaxMid);
-  TS_REQUIRE(B < kMaxAxis && H < kMaxAxis && W < kMaxAxis && HW <= 0x7fffffffll, TS_ERR_UNSUPPORTED,
-             "mbconv_project_fwd: an axis of 2^20 or more, or a plane of 2^31 pixels or more");
+  const node::Operand X{"x", x, Cmid, HW, x_bstride, x_cstride, node::IN}, R{"residual", residual, C, HW, r_bstride, r_cstride, node::RES},
+      Y{"y", y, C, HW, y_bstride, y_cstride, node::OUT};
   Project p;
-  p.g = pw1::geom(w_l, Cmid, C, HW);
-  const hw3::Launch l = pw1::launch_rule(p.g, B, 2ull * ts::kNumCU);
-  TS_REQUIRE(l.blocks != 0, TS_ERR_UNSUPPORTED, "mbconv_project_fwd: grid too large");
-  TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(gate); TS_REQUIRE_PTR(w_l); TS_REQUIRE_PTR(residual); TS_REQUIRE_PTR(y);
-  TS_REQUIRE_ALIGNED(w_l);
-  p.x = x; p.gate = gate; p.scale = scale; p.shift = shift; p.res = residual; p.y = y;
-  p.x_bs = x_bstride; p.x_cs = x_cstride; p.r_bs = r_bstride; p.r_cs = r_cstride; p.y_bs = y_bstride; p.y_cs = y_cstride;
-  hw3::dispatch_mt(l.mt, [&](auto MT) {
-    hipLaunchKernelGGL((project_kernel<MT()>), dim3(l.blocks), dim3(256), 0, ts::as_stream(stream), p);
-  });
-  return ts::launched("mbconv_project_kernel");
+  p.x = X.plane(); p.gate = gate;
+  p.ep = {scale, shift, ACT_NONE, R.plane(), {y, y_bstride, y_cstride}};
+  return node::launch(
+      who, "mbconv_project_kernel", B, {R, X, Y}, {{"gate", gate}}, w_l, {B, H, W}, [&] { return check_block(who, C, Cmid, HW); },
+      [&] { p.g = pw1::geom(w_l, Cmid, C, HW); return pw1::launch_rule(p.g, B, 2ull * ts::kNumCU); },
+      [&](auto MT, dim3 grid) { hipLaunchKernelGGL((project_kernel<MT()>), grid, dim3(256), 0, ts::as_stream(stream), p); });
 }
 
 extern "C" int ts_depthwise3x3_fwd(const float* x, const float* w, const float* scale, const float* shift, float* y, float* plane_sum,
@@ -395,6 +346,8 @@ extern "C" int ts_depthwise3x3_fwd(const float* x, const float* w, const float* 
   const unsigned blocks = corr::grid_blocks(static_cast<unsigned long long>(B) * C);
   TS_REQUIRE(blocks != 0, TS_ERR_UNSUPPORTED, "depthwise3x3_fwd: grid too large");
   TS_REQUIRE_PTR(x); TS_REQUIRE_PTR(w); TS_REQUIRE_PTR(y);
+  if (int rc = node::check_overlap("depthwise3x3_fwd", B, {{"x", x, C, HW, x_bstride, x_cstride, node::IN}, {"y", y, C, HW, y_bstride, y_cstride, node::OUT}}))
+    return rc;
   ts::dispatch_bool(rows_aligned(x, W, x_bstride, x_cstride), [&](auto VEC) {
     hipLaunchKernelGGL(depthwise_kernel<VEC()>, dim3(blocks), dim3(256), 0, ts::as_stream(stream), x, w, scale, shift, y, plane_sum, C, H,
                        W, act, flip, x_bstride, x_cstride, y_bstride, y_cstride);

@@ -2693,12 +2693,62 @@ def conv_gru_supported(hidden_planes, in_planes):
     return 1 <= hidden_planes <= CONV_GRU_MAX_PLANES and 1 <= in_planes <= CONV_GRU_MAX_PLANES
 
 
-def _plane_view(t):
-    """A [B,C,H,W] tensor the kernels can read in place (dense planes, batch / channel strides that do not overlap), else a copy."""
+def _dense_planes(t):
+    """Whether the kernels can read or write a [B,C,H,W] tensor in place: dense planes, batch / channel strides that do not overlap."""
     B, C, H, W = t.shape
-    if t.stride(3) == 1 and t.stride(2) == W and t.stride(1) >= H * W and (B == 1 or t.stride(0) >= t.stride(1) * (C - 1) + H * W):
-        return t
-    return _lib.contiguous(t)
+    return t.stride(3) == 1 and t.stride(2) == W and t.stride(1) >= H * W and (B == 1 or t.stride(0) >= t.stride(1) * (C - 1) + H * W)
+
+
+def _plane_view(t):
+    """A [B,C,H,W] tensor the kernels can read in place (`_dense_planes`), else a copy."""
+    return t if _dense_planes(t) else _lib.contiguous(t)
+
+
+def _optional_operand(t):
+    """(tensor, batch stride, channel stride) of an optional strided operand (a residual, the memory) as an entry takes it: read in
+    place where `_plane_view` allows; (None, 0, 0) when absent."""
+    if t is None:
+        return None, 0, 0
+    t = _plane_view(t)
+    return t, t.stride(0), t.stride(1)
+
+
+def _node_weight_layout(tag, entry, refusal, *extra):
+    """-> lay(weight): the kernel image of a [Cout, Cin, ...] weight of one 2-D node family, through `entry`_bytes(Cin, Cout, *extra) and
+    `entry`_layout(w, w_l, Cin, Cout, *extra, stream) (one launch).  Inside a `WeightLayouts` context a leaf is laid out once per step
+    and refreshed with the others under `tag`; the maker is built here, once, so that context can keep and call it.  A weight outside
+    the entry's envelope raises RuntimeError(refusal % (Cin, Cout, *extra))."""
+    def make(weight, out=None):
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        if out is None:
+            nbytes = _q(entry + "_bytes", Cin, Cout, *extra)
+            if not nbytes:
+                raise RuntimeError(refusal % ((Cin, Cout) + extra))
+            out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
+        _lib.check(getattr(_lib.lib(), entry + "_layout")(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, *extra, _stream()), entry + "_layout")
+        return out
+
+    def lay(weight):
+        if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
+            return _LAYOUTS.get_custom(weight, tag, make)
+        return make(_lib.contiguous(weight.detach()))
+    return lay
+
+
+def _fold_check(what, name, fold, n, required=False):
+    """-> (scale, shift) of a BatchNorm fold of at least n channels, (None, None) for no fold"""
+    if fold is None and not required:
+        return None, None
+    if fold is None or len(fold) != 2 or any(v is None or v.dim() != 1 or v.numel() < n or not v.is_contiguous() for v in fold):
+        raise ValueError("%s: the %s fold must be a (scale, shift) pair of dense vectors of at least %d values" % (what, name, n))
+    return fold
+
+
+def _out_check(what, name, t, shape):
+    """A [B,C,H,W] operand the kernels write (or read as the residual) in place: `_dense_planes` of exactly `shape`."""
+    if tuple(t.shape) != tuple(shape) or not _dense_planes(t):
+        raise ValueError("%s: %s must be %s with dense planes and strides that do not overlap, got %s strides %s"
+                         % (what, name, list(shape), tuple(t.shape), tuple(t.stride())))
 
 
 def _gru_bwd_weight_layout(ws, Cin):
@@ -2846,30 +2896,15 @@ def decoder_conv_supported(in_channels, out_channels):
     return 1 <= in_channels <= DECODER_MAX_CHANNELS and 1 <= out_channels <= DECODER_MAX_CHANNELS
 
 
-def _decoder_weight_make(weight, out=None):
-    Cout, Cin = weight.shape[0], weight.shape[1]
-    if out is None:
-        nbytes = _q("ts_decoder_weight_bytes", Cin, Cout)
-        if not nbytes:
-            raise RuntimeError("decoder_conv: %d input / %d output channels are outside the kernel path (1..%d each)"
-                               % (Cin, Cout, DECODER_MAX_CHANNELS))
-        out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
-    _lib.check(_lib.lib().ts_decoder_weight_layout(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, _stream()), "ts_decoder_weight_layout")
-    return out
+# the 3x3 core's chunked order of a [Cout, Cin, 3, 3] weight
+_decoder_weight = _node_weight_layout("decoder", "ts_decoder_weight", "decoder_conv: %d input / %d output channels are outside the kernel path "
+                                      + "(1..%d each)" % DECODER_MAX_CHANNELS)
 
 
-def _decoder_weight(weight):
-    """The kernel's chunked order of a [Cout, Cin, 3, 3] weight (ts_decoder_weight_layout); inside a `WeightLayouts` context a leaf is laid
-    out once per step and refreshed with the others."""
-    if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
-        return _LAYOUTS.get_custom(weight, "decoder", _decoder_weight_make)
-    return _decoder_weight_make(_lib.contiguous(weight.detach()))
+_BN_FOLDS = {}
 
 
-_DECODER_FOLDS = {}
-
-
-def _decoder_fold(gamma, beta, mean, var, bias, eps, cout):
+def _bn_fold(gamma, beta, mean, var, bias, eps, cout):
     """(scale, shift) of an eval-mode BatchNorm folded behind the convolution, from the CURRENT statistics: one ts_bn_fold_many launch
     per call (the one-entry table is uploaded once per layer); inside a `BNFolds` context that context's entry.
     Outside such a context the layer's scale / shift buffers are ONE pair per layer, kept here with its tensors (at most 256 layers, then
@@ -2880,13 +2915,13 @@ def _decoder_fold(gamma, beta, mean, var, bias, eps, cout):
         if fold is not None:
             return fold
     key = tuple(t.data_ptr() if t is not None else 0 for t in (gamma, beta, mean, var, bias)) + (int(cout),)
-    e = _DECODER_FOLDS.get(key)
+    e = _BN_FOLDS.get(key)
     if e is None:
-        if len(_DECODER_FOLDS) >= 256:
-            _DECODER_FOLDS.clear()
+        if len(_BN_FOLDS) >= 256:
+            _BN_FOLDS.clear()
         pad = _cpad(cout)
         entry = [gamma, beta, mean, var, bias, torch.empty(pad, device=mean.device), torch.empty(pad, device=mean.device), int(cout), pad]
-        e = _DECODER_FOLDS[key] = (entry, BNFolds()._upload([entry]))
+        e = _BN_FOLDS[key] = (entry, BNFolds()._upload([entry]))
     _lib.check(_lib.lib().ts_bn_fold_many(_lib.ptr(e[1]), 1, float(eps), _stream()), "ts_bn_fold_many")
     return e[0][5], e[0][6]
 
@@ -2950,7 +2985,7 @@ class _DecoderConv(torch.autograd.Function):
                 ctx.meta = (False, 0.0, 0, False, bias is not None)
             return y
         if may_fold and not training:
-            scale, shift = _decoder_fold(gamma, beta, running_mean, running_var, bias_d, eps, Cout)
+            scale, shift = _bn_fold(gamma, beta, running_mean, running_var, bias_d, eps, Cout)
             _decoder_launch(up, skip, w_l, scale, shift, y, act)
             return y
         _decoder_launch(up, skip, w_l, None, bias_d, y, 0)
@@ -3062,29 +3097,14 @@ def mbconv_supported(C, Cmid, Cr):
     return 1 <= C <= MBCONV_MAX_CHANNELS and 1 <= Cmid <= MBCONV_MAX_MID and 1 <= Cr <= MBCONV_MAX_CHANNELS
 
 
-def _mbconv_weight_make(weight, out=None):
-    Cout, Cin = weight.shape[0], weight.shape[1]
-    if out is None:
-        nbytes = _q("ts_mbconv_weight_bytes", Cin, Cout)
-        if not nbytes:
-            raise RuntimeError("mbconv: a 1x1 weight of %d input / %d output channels is outside the kernel path (1..%d each)"
-                               % (Cin, Cout, MBCONV_MAX_MID))
-        out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
-    _lib.check(_lib.lib().ts_mbconv_weight_layout(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, _stream()), "ts_mbconv_weight_layout")
-    return out
-
-
-def _mbconv_weight(weight):
-    """The pointwise kernels' order of a [Cout, Cin, 1, 1] weight (ts_mbconv_weight_layout); inside a `WeightLayouts` context a leaf is
-    laid out once per step and refreshed with the others, as `_decoder_weight`."""
-    if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
-        return _LAYOUTS.get_custom(weight, "mbconv", _mbconv_weight_make)
-    return _mbconv_weight_make(_lib.contiguous(weight.detach()))
+# the pointwise core's order of a [Cout, Cin, 1, 1] weight
+_mbconv_weight = _node_weight_layout("mbconv", "ts_mbconv_weight", "mbconv: a 1x1 weight of %d input / %d output channels is outside the kernel path "
+                                     + "(1..%d each)" % MBCONV_MAX_MID)
 
 
 def _bn_eval_fold(bn, bias=None):
-    """(scale, shift) of an eval-mode BatchNorm behind a convolution: `_decoder_fold`'s entry (a `BNFolds` context's when one is open)."""
-    return _decoder_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bias, bn.eps, bn.num_features)
+    """(scale, shift) of an eval-mode BatchNorm behind a convolution: `_bn_fold`'s entry (a `BNFolds` context's when one is open)."""
+    return _bn_fold(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bias, bn.eps, bn.num_features)
 
 
 def _depthwise_launch(x, w9, scale, shift, y, plane_sum, act, flip):
@@ -3111,8 +3131,7 @@ def _mbconv_check(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_e
         if t is None or tuple(t.shape) != shape:
             raise ValueError("mbconv_eval: %s must be %s, got %s" % (name, list(shape), None if t is None else tuple(t.shape)))
     for name, fold, n in (("bn1", fold1, Cmid), ("bn2", fold2, Cmid), ("bn3", fold3, C)):
-        if len(fold) != 2 or any(v is None or v.dim() != 1 or v.numel() < n or not v.is_contiguous() for v in fold):
-            raise ValueError("mbconv_eval: the %s fold must be a (scale, shift) pair of dense vectors of at least %d values" % (name, n))
+        _fold_check("mbconv_eval", name, fold, n, required=True)
     if not mbconv_supported(C, Cmid, Cr):
         raise RuntimeError("mbconv_eval: C = %d, Cmid = %d, Cr = %d are outside the kernel path (C, Cr <= %d, Cmid <= %d)"
                            % (C, Cmid, Cr, MBCONV_MAX_CHANNELS, MBCONV_MAX_MID))
@@ -3121,10 +3140,7 @@ def _mbconv_check(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_e
             raise ValueError("mbconv_eval: memory must be [%d, mc <= %d, %d, %d] as the input is %s, got %s"
                              % (B, C, H, W, tuple(inp.shape), tuple(memory.shape)))
     if out is not None:
-        if tuple(out.shape) != (B, C, H, W) or out.stride(3) != 1 or out.stride(2) != W or out.stride(1) < H * W or \
-                (B > 1 and out.stride(0) < out.stride(1) * (C - 1) + H * W):
-            raise ValueError("mbconv_eval: out must be [%d, %d, %d, %d] with dense planes and strides that do not overlap, got %s strides %s"
-                             % (B, C, H, W, tuple(out.shape), tuple(out.stride())))
+        _out_check("mbconv_eval", "out", out, (B, C, H, W))
 
 
 def mbconv_eval(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_expand, b_expand, w_pwl, fold3, out=None,
@@ -3140,12 +3156,8 @@ def mbconv_eval(inp, memory, w_pw, fold1, w_dw, fold2, w_reduce, b_reduce, w_exp
     inp = _plane_view(inp)
     B, C, H, W = inp.shape
     Cmid, Cr = w_pw.shape[0], w_reduce.shape[0]
-    mc = 0
-    mb = mcs = 0
-    if memory is not None:
-        memory = _plane_view(memory)
-        mc = memory.shape[1]
-        mb, mcs = memory.stride(0), memory.stride(1)
+    memory, mb, mcs = _optional_operand(memory)
+    mc = memory.shape[1] if memory is not None else 0
     dev = inp.device
     L, st = _lib.lib(), _stream()
     e = torch.empty((B, Cmid, H, W), device=dev, dtype=torch.float32)
@@ -3231,47 +3243,11 @@ def fused_mbconv_supported(Cin, Cmid, Cout, stride):
     return conv3x3_s_supported(Cin, Cmid, stride) and 1 <= Cmid <= MBCONV_MAX_MID and 1 <= Cout <= MBCONV_MAX_CHANNELS
 
 
-def _conv3x3_s_weight_make(stride):
-    def make(weight, out=None):
-        Cout, Cin = weight.shape[0], weight.shape[1]
-        if out is None:
-            nbytes = _q("ts_conv3x3_s_weight_bytes", Cin, Cout, stride)
-            if not nbytes:
-                raise RuntimeError("conv3x3_bn_act: %d input / %d output channels at stride %d are outside the kernel path (%s)"
-                                   % (Cin, Cout, stride, "4 Cin <= %d at stride 2, Cin and Cout <= %d" % ((CONV3X3_S_MAX_CHANNELS,) * 2)))
-            out = torch.empty(nbytes // 4, device=weight.device, dtype=torch.float32)
-        _lib.check(_lib.lib().ts_conv3x3_s_weight_layout(_lib.ptr(weight.detach()), _lib.ptr(out), Cin, Cout, stride, _stream()),
-                   "ts_conv3x3_s_weight_layout")
-        return out
-    return make
-
-
-_CONV3X3_S_MAKE = {1: _conv3x3_s_weight_make(1), 2: _conv3x3_s_weight_make(2)}
-
-
-def _conv3x3_s_weight(weight, stride):
-    """The 3x3 core's chunked order of a [Cout, Cin, 3, 3] weight for one stride (ts_conv3x3_s_weight_layout: at stride 2 the phase
-    order); inside a `WeightLayouts` context a leaf is laid out once per step and refreshed with the others, as `_decoder_weight`."""
-    if _LAYOUTS is not None and weight.is_contiguous() and weight.is_leaf:
-        return _LAYOUTS.get_custom(weight, "conv3x3_s%d" % stride, _CONV3X3_S_MAKE[stride])
-    return _CONV3X3_S_MAKE[stride](_lib.contiguous(weight.detach()))
-
-
-def _fold_check(what, name, fold, n):
-    if fold is None:
-        return None, None
-    if len(fold) != 2 or any(v is None or v.dim() != 1 or v.numel() < n or not v.is_contiguous() for v in fold):
-        raise ValueError("%s: the %s fold must be a (scale, shift) pair of dense vectors of at least %d values" % (what, name, n))
-    return fold
-
-
-def _out_check(what, name, t, shape):
-    """A [B,C,H,W] operand the kernels write (or read as the residual) in place: dense planes, strides that do not overlap."""
-    B, C, H, W = shape
-    if tuple(t.shape) != tuple(shape) or t.stride(3) != 1 or t.stride(2) != W or t.stride(1) < H * W or \
-            (B > 1 and t.stride(0) < t.stride(1) * (C - 1) + H * W):
-        raise ValueError("%s: %s must be %s with dense planes and strides that do not overlap, got %s strides %s"
-                         % (what, name, list(shape), tuple(t.shape), tuple(t.stride())))
+# the 3x3 core's chunked order of a [Cout, Cin, 3, 3] weight for one stride (at stride 2 the phase order)
+_CONV3X3_S_WEIGHT = {stride: _node_weight_layout("conv3x3_s%d" % stride, "ts_conv3x3_s_weight",
+                                                 "conv3x3_bn_act: %d input / %d output channels at stride %d are outside the kernel path "
+                                                 + "(4 Cin <= %d at stride 2, Cin and Cout <= %d)" % ((CONV3X3_S_MAX_CHANNELS,) * 2), stride)
+                     for stride in (1, 2)}
 
 
 def conv3x3_bn_act(x, weight, fold, stride, activation, residual=None, out=None):
@@ -3305,12 +3281,9 @@ def conv3x3_bn_act(x, weight, fold, stride, activation, residual=None, out=None)
         _out_check(what, "out", out, (B, Cout, Ho, Wo))
     _require_gpu(x, weight, scale, shift, residual, out)
     x = _plane_view(x)
-    rb = rc = 0
-    if residual is not None:
-        residual = _plane_view(residual)
-        rb, rc = residual.stride(0), residual.stride(1)
+    residual, rb, rc = _optional_operand(residual)
     y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=torch.float32) if out is None else out
-    code = _lib.lib().ts_conv3x3_s_fwd(_lib.ptr(x), _lib.ptr(_conv3x3_s_weight(weight, stride)), _lib.ptr(scale), _lib.ptr(shift),
+    code = _lib.lib().ts_conv3x3_s_fwd(_lib.ptr(x), _lib.ptr(_CONV3X3_S_WEIGHT[stride](weight)), _lib.ptr(scale), _lib.ptr(shift),
                                        _lib.ptr(residual), _lib.ptr(y), B, Cin, Cout, H, W, int(stride), BN_ACT[activation], x.stride(0),
                                        x.stride(1), rb, rc, y.stride(0), y.stride(1), _stream())
     _lib.check(code, "ts_conv3x3_s_fwd")
@@ -3344,10 +3317,7 @@ def fused_mbconv_eval(x, w_exp, fold1, stride, w_pwl, fold2, residual, out=None,
         _out_check(what, "out", out, (B, Cout, Ho, Wo))
     _require_gpu(w_pwl, scale2, shift2, residual, out)
     mid = conv3x3_bn_act(x, w_exp, fold1, stride, "SiLU")
-    rb = rc = 0
-    if residual is not None:
-        residual = _plane_view(residual)
-        rb, rc = residual.stride(0), residual.stride(1)
+    residual, rb, rc = _optional_operand(residual)
     y = torch.empty((B, Cout, Ho, Wo), device=x.device, dtype=torch.float32) if out is None else out
     code = _lib.lib().ts_fused_project_fwd(_lib.ptr(mid), _lib.ptr(_mbconv_weight(w_pwl)), _lib.ptr(scale2), _lib.ptr(shift2),
                                            _lib.ptr(residual), _lib.ptr(y), B, Cmid, Cout, Ho, Wo, mid.stride(0), mid.stride(1), rb, rc,

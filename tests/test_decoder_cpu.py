@@ -195,9 +195,10 @@ def _sweep(fn, args, required, what):
 
 def test_abi_version_and_argument_checks():
     L = _lib.lib()
-    assert L.ts_version() >= 21
+    assert L.ts_version() >= 24
     buf = ctypes.create_string_buffer(64)
     one = (ctypes.addressof(buf) + 15) // 16 * 16        # never dereferenced by a call that is refused; 16-byte aligned
+    far, farther = one + (1 << 40), one + (1 << 41)      # operands that overlap neither `one` nor one another
     big = 1 << 20
 
     # ts_decoder_weight_bytes(Cin, Cout) / ts_decoder_weight_layout(w, w_l, Cin, Cout, stream)
@@ -241,6 +242,19 @@ def test_abi_version_and_argument_checks():
     assert fn(*ok(B=1, H=big, W=1)) == -3 and fn(*ok(B=1, H=1, W=big)) == -3 and fn(*ok(B=1, h=big, w=1)) == -3 and fn(*ok(B=1, h=1, w=big)) == -3
     # the order: sizes before the envelope before pointers
     assert fn(*ok(Cout=513, yc=N - 1, skip=None)) == -2 and fn(*ok(Cout=513, skip=None)) == -3
+    # the overlap rules, after pointers and alignment: y (argument 5) apart from up and from skip
+    def at(y, **kw):
+        a = list(ok(**kw))
+        a[5] = y
+        return a
+    assert fn(*at(one, up=far)) == -2 and b"y overlaps skip" in L.ts_last_error_string()              # an output over its own input
+    assert fn(*at(one, skip=far)) == -2 and b"y overlaps up" in L.ts_last_error_string()
+    assert fn(*at(farther + 4 * (2 * 5 * N - 1), up=far, skip=farther)) == -2                         # y begins on skip's last element
+    assert fn(*at(far + 4 * (2 * 12 * n - 1), up=far, skip=farther)) == -2                            # ... on up's
+    assert fn(*at(one, Cu=0, h=0, w=0)) == -2 and b"y overlaps skip" in L.ts_last_error_string()      # Cu = 0: `up` is not looked at
+    a = at(one, up=far)
+    a[2] = one + 4
+    assert fn(*a) == -4                                                                               # after the alignment
 
     # ts_resize_bilinear_bwd(dy, dx, B, C, h, w, H, W, dy_bs, dy_cs, dx_bs, dx_cs, stream)
     fn = L.ts_resize_bilinear_bwd

@@ -343,9 +343,10 @@ def _sweep(fn, args, required, what):
 
 def test_abi_version_and_argument_checks():
     L = _lib.lib()
-    assert L.ts_version() >= 22
+    assert L.ts_version() >= 24
     buf = ctypes.create_string_buffer(64)
     one = (ctypes.addressof(buf) + 15) // 16 * 16        # never dereferenced by a call that is refused; 16-byte aligned
+    far, farther = one + (1 << 40), one + (1 << 41)      # operands that overlap neither `one` nor one another
     big = 1 << 20
     N = 9 * 13
 
@@ -384,6 +385,12 @@ def test_abi_version_and_argument_checks():
     assert fn(*ok(C=512, mc=128, Cmid=2048, inp=None)) == -1                   # the envelope's corner passes the envelope check
     assert fn(*ok(B=1, H=big, W=1)) == -3 and fn(*ok(B=1, H=1, W=big)) == -3 and fn(*ok(B=1, H=60000, W=60000)) == -3
     assert fn(*ok(Cmid=2049, yc=N - 1, inp=None)) == -2 and fn(*ok(Cmid=2049, inp=None)) == -3      # sizes before the envelope before pointers
+    # the overlap rules, after pointers and alignment: y apart from memory and from input
+    assert fn(*ok(memory=far, y=one)) == -2 and b"y overlaps input" in L.ts_last_error_string()        # an output over its own input
+    assert fn(*ok(inp=far, y=one)) == -2 and b"y overlaps memory" in L.ts_last_error_string()
+    assert fn(*ok(memory=far, inp=farther, y=farther + 4 * (2 * 24 * N - 1))) == -2                    # y begins on the input's last element
+    assert fn(*ok(memory=far, inp=farther, y=far + 4 * (2 * 6 * N - 1))) == -2                         # ... on the memory's
+    assert fn(*ok(memory=None, inp=far, y=far, w_l=one + 4)) == -4 and fn(*ok(memory=None, inp=far, y=far)) == -2      # after the alignment
 
     # ts_mbconv_project_fwd(x, gate, w_l, scale, shift, residual, y, B, Cmid, C, H, W, x_bs, x_cs, r_bs, r_cs, y_bs, y_cs, stream)
     fn = L.ts_mbconv_project_fwd
@@ -408,6 +415,14 @@ def test_abi_version_and_argument_checks():
     assert fn(*ok(C=513)) == -3 and fn(*ok(Cmid=2049)) == -3 and fn(*ok(C=512, Cmid=2048, x=None)) == -1
     assert fn(*ok(B=1, H=big, W=1)) == -3 and fn(*ok(B=1, H=1, W=big)) == -3
     assert fn(*ok(C=513, yc=N - 1, x=None)) == -2 and fn(*ok(C=513, x=None)) == -3
+    # the overlap rules: y apart from x; the residual is y's own elements or apart from y
+    assert fn(*ok(res=far, y=one)) == -2 and b"y overlaps x" in L.ts_last_error_string()              # an output over its own input
+    assert fn(*ok(res=far, y=one + 4 * (2 * 96 * N - 1))) == -2 and b"y overlaps x" in L.ts_last_error_string()      # y begins on x's last element
+    assert fn(*ok(res=far + 4, y=far)) == -2 and b"residual" in L.ts_last_error_string()              # a residual shifted against y
+    assert fn(*ok(res=far, rcs=N + 1, y=far)) == -2 and b"residual" in L.ts_last_error_string()       # the same pointer, other strides
+    # residual == y with equal strides is the in-place residual: it gets past the residual's rule, to the rule on x
+    assert fn(*ok(x=far, res=far, y=far)) == -2 and b"y overlaps x" in L.ts_last_error_string()
+    assert fn(*ok(res=far, y=one, w_l=one + 4)) == -4                                                 # after the alignment
 
     # ts_depthwise3x3_fwd(x, w, scale, shift, y, plane_sum, B, C, H, W, act, flip, x_bs, x_cs, y_bs, y_cs, stream)
     fn = L.ts_depthwise3x3_fwd
@@ -426,6 +441,10 @@ def test_abi_version_and_argument_checks():
     assert fn(*ok(xb=12 * N - 1)) == -2 and fn(*ok(yc=N - 1)) == -2 and fn(*ok(yb=12 * N - 1)) == -2
     assert fn(*ok(B=1, H=big, W=1)) == -3 and fn(*ok(B=1, W=big, H=1)) == -3 and fn(*ok(B=1, C=big, H=1, W=1)) == -3 and fn(*ok(B=big, H=1, W=1)) == -3
     assert fn(*ok(B=1, H=big, x=None)) == -3 and fn(*ok(B=1, H=big, yc=1)) == -2
+    # the overlap rule, after the pointers: y apart from x
+    assert fn(*ok(y=one)) == -2 and b"y overlaps x" in L.ts_last_error_string()                       # an output over its own input
+    assert fn(*ok(y=one + 4 * (2 * 12 * N - 1))) == -2 and b"overlaps" in L.ts_last_error_string()    # y begins on x's last element
+    assert fn(*ok(y=one, w=None)) == -1
 
     # ts_depthwise3x3_bwd_weight(x, dy, dw, B, C, H, W, x_bs, x_cs, dy_bs, dy_cs, stream)
     fn = L.ts_depthwise3x3_bwd_weight

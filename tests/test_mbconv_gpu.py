@@ -303,6 +303,31 @@ def test_operands_read_in_place_and_output_written_into_a_slice():
     compare_forward(tag, "eval", dict(f0_out=view))
 
 
+def test_output_over_the_input_in_place_and_shifted():
+    """B = 2, C = 16, Cmid = 64, Cr = 4 on a 5 x 7 plane.  `out` the input itself is the in-place residual -- an element of the input is
+    read by the thread that overwrites it -- and has the bits of the out-of-place call; an `out` that is the input shifted by one
+    channel overlaps the residual without being its own elements and is refused (ts_mbconv_project_fwd, TS_ERR_SHAPE)."""
+    B, C, Cmid, Cr, H, W = 2, 16, 64, 4, 5, 7
+    torch.manual_seed(7480)
+    blk = ts.MemoryInvertedResidual(C, mid_chs=Cmid, se_chs=Cr).to(_dev()).eval()
+    x = gpu(t32(synth.normal(7480, "x", (B, C, H, W))))
+    memory = gpu(t32(synth.normal(7480, "m", (B, int(C * MP), H, W))))
+    args = lambda: (blk.conv_pw.weight, TF._bn_eval_fold(blk.bn1), blk.conv_dw.weight, TF._bn_eval_fold(blk.bn2), blk.se.conv_reduce.weight,
+                    blk.se.conv_reduce.bias, blk.se.conv_expand.weight, blk.se.conv_expand.bias, blk.conv_pwl.weight, TF._bn_eval_fold(blk.bn3))
+    with torch.no_grad():
+        dense = TF.mbconv_eval(x, memory, *args())
+        inplace = x.clone()
+        got = TF.mbconv_eval(inplace, memory, *args(), out=inplace)
+        torch.cuda.synchronize()
+        assert got.data_ptr() == inplace.data_ptr() and same_bits(inplace, dense) and not same_bits(dense, x)
+        wide = torch.zeros((B, C + 1, H, W), device=_dev())
+        wide[:, :C] = x
+        with pytest.raises(RuntimeError, match="overlaps"):
+            TF.mbconv_eval(wide[:, :C], memory, *args(), out=wide[:, 1:])
+        torch.cuda.synchronize()
+    assert same_bits(wide[:, :C], x) and not bool(wide[:, C].any())           # refused before the launch: nothing was written
+
+
 def test_weights_scaled_by_1e3():
     """Every convolution weight times 1e3: the pre-activations reach the far ends of SiLU and of the sigmoid; everything stays finite and
     within the bars of the restatement's own fp32 run."""

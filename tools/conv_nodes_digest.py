@@ -3,8 +3,9 @@
 One line per case: the case's name, then `what=<digest>` for the output, every gradient the case has (x, weight, bias, gamma, beta,
 addend, up, skip) and, where a BatchNorm is involved, its running statistics and num_batches_tracked.  A digest is the first 16 hex
 digits of the SHA-256 of the tensor's bytes (shape and dtype included).  The tool goes through the public functions only (conv3d,
-conv_transpose3d, conv_transpose2d_k4s2, conv3d_k333, conv_bn_act, decoder_conv, the layers wrappers), so two trees that hold the same
-built library can be compared line by line: a refactor of the Python side must leave every line as it was.
+conv_transpose3d, conv_transpose2d_k4s2, conv3d_k333, conv_bn_act, decoder_conv, conv_gru, mbconv_eval, depthwise_conv3x3, conv3x3_bn_act,
+fused_mbconv_eval, the layers wrappers), so two trees can be compared line by line: a refactor must leave every line as it was.  The
+2-D nodes run at the shapes of their batch-grouping tests, which reach every MT instantiation of the two fp32-MFMA cores.
 
     python tools/conv_nodes_digest.py [--out FILE]
 """
@@ -220,11 +221,106 @@ def decoder_cases():
                         ("gamma", bn.weight.grad), ("beta", bn.bias.grad)] + bn_state(bn))
 
 
+# ------------------------------------------------------------------ the 2-D f32-MFMA nodes
+def he(seed, name, shape, fan_in):
+    return (synth.normal(seed, name, shape).astype(np.float64) * (2.0 / np.sqrt(fan_in))).astype(np.float32)
+
+
+def fold(seed, n):
+    return gpu(synth.uniform(seed, "scale", (n,), 0.5, 1.5)), gpu(synth.normal(seed, "shift", (n,), 0.1))
+
+
+def gru_cases():
+    def cell(seed, Ch, Cx, grad):
+        C = Ch + Cx
+        return [gpu(a, grad) for a in (he(seed, "wz", (Ch, C, 3, 3), 9 * C), synth.normal(seed, "bz", (Ch,), 0.1), he(seed, "wr", (Ch, C, 3, 3), 9 * C),
+                                       synth.normal(seed, "br", (Ch,), 0.1), he(seed, "wq", (Ch, C, 3, 3), 9 * C), synth.normal(seed, "bq", (Ch,), 0.1))]
+    # test_conv_gru_gpu.py::test_bits_do_not_depend_on_the_batch_grouping: gru_conv_kernel<8 | 4 | 2 | 1, true> and <4 | 2 | 1, false>
+    B, Ch, Cx, H, W = 8, 64, 5, 31, 63
+    h, x, params = gpu(synth.normal(41, "h", (B, Ch, H, W))), gpu(synth.normal(41, "x", (B, Cx, H, W))), cell(41, Ch, Cx, False)
+    for n in (8, 4, 2, 1):
+        with torch.no_grad():
+            out = TF.conv_gru(h[:n], x[:n], *params, return_gates=True)
+        emit("gru/64-5/31x63/B%d" % n, list(zip(("out", "z", "r", "q"), out)))
+    for B, Ch, Cx, H, W in ((2, 12, 5, 9, 13), (1, 64, 64, 6, 7)):
+        h, x, params = gpu(synth.normal(42, "h", (B, Ch, H, W)), True), gpu(synth.normal(42, "x", (B, Cx, H, W)), True), cell(42, Ch, Cx, True)
+        out = TF.conv_gru(h, x, *params)
+        backward(out, 80)
+        emit("gru/%d-%d/%dx%d/grad" % (Ch, Cx, H, W), [("out", out), ("h", h.grad), ("x", x.grad)] +
+             [(k, p.grad) for k, p in zip(("wz", "bz", "wr", "br", "wq", "bq"), params)])
+
+
+def mbconv_cases():
+    # test_mbconv_gpu.py::test_pointwise_bits_do_not_depend_on_the_batch_grouping, as a block: expand 130 -> 300 rows, project 300 -> 130
+    # rows on a 24 x 24 plane; B = 32 | 20 | 12 | 8 | 4 reach expand_kernel and project_kernel <8 | 4 | 2 | 1>
+    B, C, Cmid, Cr, H, W, mc = 32, 130, 300, 8, 24, 24, 33
+    x, mem = gpu(synth.normal(43, "x", (B, C, H, W))), gpu(synth.normal(43, "m", (B, mc, H, W)))
+    w = [gpu(a) for a in (he(43, "pw", (Cmid, C, 1, 1), C), he(43, "dw", (Cmid, 1, 3, 3), 9), he(43, "red", (Cr, Cmid, 1, 1), Cmid),
+                          synth.normal(43, "bred", (Cr,), 0.1), he(43, "exp", (Cmid, Cr, 1, 1), Cr), synth.normal(43, "bexp", (Cmid,), 0.1),
+                          he(43, "pwl", (C, Cmid, 1, 1), Cmid))]
+    f1, f2, f3 = fold(44, Cmid), fold(45, Cmid), fold(46, C)
+    for n, memory in ((32, True), (20, True), (12, True), (8, True), (4, True), (4, False), (1, False)):
+        with torch.no_grad():
+            y, e, d, gate = TF.mbconv_eval(x[:n], mem[:n] if memory else None, w[0], f1, w[1], f2, w[2], w[3], w[4], w[5], w[6], f3, return_stages=True)
+        emit("mbconv/130-300/24x24/B%d/%s" % (n, "memory" if memory else "first"), [("out", y), ("act1", e), ("act2", d), ("gate", gate)])
+
+
+def depthwise_cases():
+    for shape in ((2, 12, 9, 13), (2, 8, 8, 16), (1, 5, 17, 70)):          # scalar staging; 16-byte staging; more than one tile along both axes
+        for with_bias in (False, True):
+            x, w = gpu(synth.normal(47, "x", shape), True), gpu(he(47, "w", (shape[1], 1, 3, 3), 9), True)
+            b = gpu(synth.normal(47, "b", (shape[1],), 0.3), True) if with_bias else None
+            y = TF.depthwise_conv3x3(x, w, b)
+            backward(y, 81)
+            emit("depthwise/%dx%dx%dx%d/%s" % (shape + ("bias" if with_bias else "nobias",)),
+                 [("out", y), ("x", x.grad), ("weight", w.grad), ("bias", b.grad if b is not None else None)])
+
+
+def conv3x3_cases():
+    # test_decoder_gpu.py::test_bits_do_not_depend_on_the_batch_grouping's plane: 128 rows on 31 x 63, B = 16 | 8 | 4 | 2 reach
+    # conv3x3_kernel<8 | 4 | 2 | 1, S>; stride 2 from an odd 61 x 125 plane
+    Cout = 128
+    sc = fold(48, Cout)
+    for stride, Cin, H, W in ((1, 24, 31, 63), (2, 6, 61, 125)):
+        x, w = gpu(synth.normal(49, "x", (16, Cin, H, W))), gpu(he(49, "w", (Cout, Cin, 3, 3), 9 * Cin))
+        res = gpu(synth.normal(49, "r", (16, Cout, 31, 63)))
+        for n in (16, 8, 4, 2):
+            for residual in ((False, True) if stride == 1 else (False,)):
+                with torch.no_grad():
+                    y = TF.conv3x3_bn_act(x[:n], w, sc, stride, "SiLU", residual=res[:n] if residual else None)
+                emit("conv3x3/s%d/%d-%d/%dx%d/B%d/%s" % (stride, Cin, Cout, H, W, n, "residual" if residual else "plain"), [("out", y)])
+    for stride in (1, 2):                   # a small odd plane, no fold, no activation, 130 rows (a ragged second row group)
+        x, w = gpu(synth.normal(50, "x", (2, 5, 9, 13))), gpu(he(50, "w", (130, 5, 3, 3), 45))
+        with torch.no_grad():
+            y = TF.conv3x3_bn_act(x, w, None, stride, None)
+        emit("conv3x3/s%d/5-130/9x13/B2/raw" % stride, [("out", y)])
+
+
+def fused_mbconv_cases():
+    # the pointwise grouping again: 130 rows on 24 x 24, B = 32 | 20 | 12 | 4 reach fused_project_kernel<8 | 4 | 2 | 1>
+    B, Cin, Cmid, Cout, H, W = 32, 24, 96, 130, 24, 24
+    x, res = gpu(synth.normal(51, "x", (B, Cin, H, W))), gpu(synth.normal(51, "r", (B, Cout, H, W)))
+    w_exp, w_pwl = gpu(he(51, "exp", (Cmid, Cin, 3, 3), 9 * Cin)), gpu(he(51, "pwl", (Cout, Cmid, 1, 1), Cmid))
+    f1, f2 = fold(52, Cmid), fold(53, Cout)
+    for n in (32, 20, 12, 4):
+        with torch.no_grad():
+            y, mid = TF.fused_mbconv_eval(x[:n], w_exp, f1, 1, w_pwl, f2, res[:n], return_stages=True)
+        emit("fused_mbconv/s1/24-96-130/24x24/B%d" % n, [("out", y), ("mid", mid)])
+    xs = gpu(synth.normal(54, "x", (2, Cin, 9, 13)))
+    w_same = gpu(he(54, "pwl", (Cin, Cmid, 1, 1), Cmid))
+    with torch.no_grad():
+        y, mid = TF.fused_mbconv_eval(xs, w_exp, f1, 2, w_pwl, f2, None, return_stages=True)
+        emit("fused_mbconv/s2/24-96-130/9x13/B2", [("out", y), ("mid", mid)])
+        y, mid = TF.fused_mbconv_eval(xs, w_exp, f1, 1, w_same, fold(55, Cin), xs, return_stages=True)      # the block's own input as the residual
+        emit("fused_mbconv/s1/24-96-24/9x13/B2/skip", [("out", y), ("mid", mid)])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", help="also write the lines to this file")
     args = ap.parse_args()
     fused_cases(); raw_cases(); node_cases(); decoder_cases()
+    gru_cases(); mbconv_cases(); depthwise_cases(); conv3x3_cases(); fused_mbconv_cases()
     torch.cuda.synchronize()
     if args.out:
         with open(args.out, "w") as fh:
