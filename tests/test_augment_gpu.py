@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import augment_ref as R
+from compare import dev as _dev, gpu, same_bits
 from temporalstereo_amd import _lib, augment as ag, preprocess as pp
 
 pytestmark = pytest.mark.gpu
@@ -26,16 +27,8 @@ CASES = ("augment_ops", "augment_orders", "augment_chain", "augment_occlusion", 
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def load(name):
     return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
 
 
 def fixture_rects(g, b):
@@ -57,10 +50,6 @@ def fixture_aug(g, seed=99, rects=True, device=None):
                 d["rects"] = fixture_rects(g, b)
             rows[e][b] = d
     return ag.Augmentation.from_values(rows, crop=g["crop"], device=_dev() if device is None else device)
-
-
-def same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 @pytest.mark.parametrize("layout", ("HWC", "CHW"))

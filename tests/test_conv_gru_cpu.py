@@ -11,28 +11,16 @@ of that many terms), its root by half of that, and 1.25 leaves that thirty-fold.
 """
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 import conv_gru_ref as R
+from compare import T, err, null_sweep, rel_l2
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
 
 FIXTURES = ("a", "b", "c", "d")
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def err(a, b):
-    return float((a.double() - b.double()).abs().max())
-
-
-def rel_l2(a, b, ref):
-    return float((a.double() - b.double()).norm() / ref.double().norm())
 
 
 @pytest.mark.parametrize("tag", FIXTURES)
@@ -99,14 +87,6 @@ def test_functional_refuses_cpu_tensors():
     assert not TF.conv_gru_supported(65, 8) and not TF.conv_gru_supported(8, 65) and not TF.conv_gru_supported(0, 8)
 
 
-def _sweep(fn, args, required, what):
-    """NULL in every required pointer position -> -1."""
-    for i in required:
-        a = list(args)
-        a[i] = None
-        assert fn(*a) == -1 and b"NULL" in _lib.lib().ts_last_error_string(), (what, i)
-
-
 def test_abi_version_and_argument_checks():
     L = _lib.lib()
     assert L.ts_version() >= 19
@@ -118,7 +98,7 @@ def test_abi_version_and_argument_checks():
     # ts_conv_gru_weight_bytes / ts_conv_gru_weight_layout(wz, wr, wq, w_l, Ch, Cx, stream)
     assert L.ts_conv_gru_weight_bytes(12, 5) > 0 and L.ts_conv_gru_weight_bytes(64, 64) >= 3 * 64 * 128 * 9 * 4
     assert L.ts_conv_gru_weight_bytes(65, 8) == 0 and L.ts_conv_gru_weight_bytes(8, 65) == 0 and L.ts_conv_gru_weight_bytes(0, 8) == 0
-    _sweep(L.ts_conv_gru_weight_layout, (one, one, one, one, 12, 5, None), (0, 1, 2, 3), "weight_layout")
+    null_sweep(L.ts_conv_gru_weight_layout, (one, one, one, one, 12, 5, None), (0, 1, 2, 3), "weight_layout")
     assert L.ts_conv_gru_weight_layout(one, one, one, one, 0, 5, None) == -2
     assert L.ts_conv_gru_weight_layout(one, one, one, one, 12, -1, None) == -2
     assert L.ts_conv_gru_weight_layout(one, one, one, one, 65, 5, None) == -3
@@ -129,7 +109,7 @@ def test_abi_version_and_argument_checks():
     for fn, what in ((L.ts_conv_gru_gates_fwd, "gates_fwd"), (L.ts_conv_gru_out_fwd, "out_fwd")):
         ok = lambda B=2, Ch=12, Cx=5, H=6, W=7, hb=12 * N, hc=N, xb=5 * N, xc=N: \
             (one,) * 8 + (B, Ch, Cx, H, W, hb, hc, xb, xc, None)
-        _sweep(fn, ok(), (0, 1, 2, 3, 4, 5, 6), what)
+        null_sweep(fn, ok(), (0, 1, 2, 3, 4, 5, 6), what)
         # r / q may be NULL: with it the call gets past the pointer checks, to the alignment check of w_l that follows them
         a = list(ok())
         a[7], a[2] = None, one + 4
@@ -145,7 +125,7 @@ def test_abi_version_and_argument_checks():
     # ts_conv_gru_gate_bwd_a(dout, z, q, h, dq_pre, dz_pre, dh, B, Ch, N, h_bs, h_cs, dz_bs, dz_cs, stream)
     ok = lambda B=2, Ch=12, n=N, hb=12 * N, hc=N, zb=24 * N, zc=N: (one,) * 7 + (B, Ch, n, hb, hc, zb, zc, None)
     fn = L.ts_conv_gru_gate_bwd_a
-    _sweep(fn, ok(), tuple(range(7)), "gate_bwd_a")
+    null_sweep(fn, ok(), tuple(range(7)), "gate_bwd_a")
     assert fn(*ok(B=0)) == -2 and fn(*ok(Ch=0)) == -2 and fn(*ok(n=0)) == -2
     assert fn(*ok(hc=N - 1)) == -2 and fn(*ok(zc=N - 1)) == -2 and fn(*ok(zb=12 * N - 1)) == -2
     assert fn(*ok(Ch=65, hb=65 * N, zb=130 * N)) == -3
@@ -154,7 +134,7 @@ def test_abi_version_and_argument_checks():
     # ts_conv_gru_gate_bwd_b(d_rh, r, h, dr_pre, dh, B, Ch, N, drh_bs, drh_cs, h_bs, h_cs, dr_bs, dr_cs, stream)
     ok = lambda B=2, Ch=12, n=N, gb=17 * N, gc=N, hb=12 * N, hc=N, rb=24 * N, rc=N: (one,) * 5 + (B, Ch, n, gb, gc, hb, hc, rb, rc, None)
     fn = L.ts_conv_gru_gate_bwd_b
-    _sweep(fn, ok(), tuple(range(5)), "gate_bwd_b")
+    null_sweep(fn, ok(), tuple(range(5)), "gate_bwd_b")
     assert fn(*ok(B=0)) == -2 and fn(*ok(Ch=-1)) == -2 and fn(*ok(n=0)) == -2
     assert fn(*ok(gc=N - 1)) == -2 and fn(*ok(hc=N - 1)) == -2 and fn(*ok(rc=N - 1)) == -2 and fn(*ok(gb=12 * N - 1)) == -2
     assert fn(*ok(Ch=65, gb=70 * N, hb=65 * N, rb=130 * N)) == -3
@@ -163,6 +143,6 @@ def test_abi_version_and_argument_checks():
     # ts_conv_gru_grad_sum(dcat_g, dcat_q, dh, dx, B, Ch, Cx, N, stream): dx may be NULL
     ok = lambda B=2, Ch=12, Cx=5, n=N: (one,) * 4 + (B, Ch, Cx, n, None)
     fn = L.ts_conv_gru_grad_sum
-    _sweep(fn, ok(), (0, 1, 2), "grad_sum")              # (dx = NULL is exercised on the device: x without a gradient)
+    null_sweep(fn, ok(), (0, 1, 2), "grad_sum")              # (dx = NULL is exercised on the device: x without a gradient)
     assert fn(*ok(B=0)) == -2 and fn(*ok(Ch=0)) == -2 and fn(*ok(Cx=0)) == -2 and fn(*ok(n=-1)) == -2
     assert fn(*ok(Ch=65)) == -3 and fn(*ok(Cx=65)) == -3 and fn(*ok(B=1, n=1 << 40)) == -3

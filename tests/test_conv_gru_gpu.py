@@ -10,20 +10,21 @@ Bars, none taken from the code under test (the project's convention; the factor 
 Each case prints error / bar; with TS_CONV_GRU_PARITY_FILE set the line is appended to that file (profiles/conv_gru_parity.txt is made so).
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import conv_gru_ref as R
+from compare import Parity, dev as _dev, gpu, same_bits, stage_bar
 import temporalstereo_amd as ts
 from temporalstereo_amd import functional as TF
 from temporalstereo_amd import layers
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
+P = Parity("TS_CONV_GRU_PARITY_FILE", width=52)
+check, check_rel = P.check, P.check_rel
 #        tag  B  Ch  Cx  H   W
 SHAPES = {"a": (2, 12, 5, 9, 37),        # nothing a multiple of a tile; the source seam inside a channel chunk; a batch stride
           "b": (1, 32, 48, 17, 70),      # a row longer than a 64-wide tile; several K chunks
@@ -35,43 +36,6 @@ FIXTURES = ("a", "b", "c", "d")
 TAGS = tuple(SHAPES)
 GRAD_TAGS = ("a", "b", "c", "e", "f")
 GRADS = ("h", "x") + R.KEYS
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_CONV_GRU_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
-
-
-def check(name, got, want, bar):
-    err = float((got.double().cpu() - want.double().cpu()).abs().max())
-    report("%-52s max |err| %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def check_rel(name, got, want, ref, bar):
-    """relative L2 of got - want, in units of |ref|"""
-    err = float((got.double().cpu() - want.double().cpu()).norm() / ref.double().cpu().norm())
-    report("%-52s rel L2    %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def stage_bar(dev, peak):
-    return max(4.0 * dev, 16.0 * U * peak)
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,14 +12,11 @@ import pytest
 import torch
 
 import temporalstereo_amd as ts
+from compare import same_bits
 
 pytestmark = pytest.mark.gpu
 
 B, C, H, W, L, RAD = 2, 5, 4, 6, 2, 1
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def inputs():

@@ -11,30 +11,18 @@ stored; where 8192 seeded positions of a larger array are stored the ratio over 
 """
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
 import decoder_ref as R
+from compare import T, err, null_sweep, rel_l2
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
 from temporalstereo_amd import layers
 
 TAGS = ("a", "b")
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def err(a, b):
-    return float((a.double() - b.double()).abs().max())
-
-
-def rel_l2(a, b, ref):
-    return float((a.double() - b.double()).norm() / ref.double().norm())
 
 
 def test_state_dict_is_the_references():
@@ -185,14 +173,6 @@ def test_functional_refuses_cpu_tensors_and_bad_arguments():
     assert not TF.decoder_conv_supported(513, 8) and not TF.decoder_conv_supported(8, 513) and not TF.decoder_conv_supported(0, 8)
 
 
-def _sweep(fn, args, required, what):
-    """NULL in every required pointer position -> -1."""
-    for i in required:
-        a = list(args)
-        a[i] = None
-        assert fn(*a) == -1 and b"NULL" in _lib.lib().ts_last_error_string(), (what, i)
-
-
 def test_abi_version_and_argument_checks():
     L = _lib.lib()
     assert L.ts_version() >= 24
@@ -206,7 +186,7 @@ def test_abi_version_and_argument_checks():
     assert L.ts_decoder_weight_bytes(480, 256) % 16 == 0
     assert L.ts_decoder_weight_bytes(513, 8) == 0 and L.ts_decoder_weight_bytes(8, 513) == 0 and L.ts_decoder_weight_bytes(0, 8) == 0
     fn = L.ts_decoder_weight_layout
-    _sweep(fn, (one, one, 17, 20, None), (0, 1), "weight_layout")
+    null_sweep(fn, (one, one, 17, 20, None), (0, 1), "weight_layout")
     assert fn(one, one, 0, 20, None) == -2 and fn(one, one, 17, -1, None) == -2
     assert fn(one, one, 513, 20, None) == -3 and fn(one, one, 17, 513, None) == -3
     assert fn(one, one + 4, 17, 20, None) == -4
@@ -224,7 +204,7 @@ def test_abi_version_and_argument_checks():
         sb = Cs * sc if sb is None else sb
         yb = Cout * yc if yb is None else yb
         return (up, skip, one, scale, shift, one, B, Cu, Cs, Cout, h, w, H, W, act, ub, uc, sb, sc, yb, yc, None)
-    _sweep(fn, ok(), (0, 1, 2, 5), "decoder_conv_fwd")
+    null_sweep(fn, ok(), (0, 1, 2, 5), "decoder_conv_fwd")
     # scale / shift may be NULL, and so may up when Cu = 0: such a call gets past the pointer checks, to the
     # alignment check of w_l that follows them
     for kw in (dict(scale=None, shift=None), dict(Cu=0, up=None, h=0, w=0)):
@@ -259,7 +239,7 @@ def test_abi_version_and_argument_checks():
     # ts_resize_bilinear_bwd(dy, dx, B, C, h, w, H, W, dy_bs, dy_cs, dx_bs, dx_cs, stream)
     fn = L.ts_resize_bilinear_bwd
     ok = lambda B=2, C=12, h=4, w=7, H=9, W=13, gb=17 * N, gc=N, xb=12 * n, xc=n: (one, one, B, C, h, w, H, W, gb, gc, xb, xc, None)
-    _sweep(fn, ok(), (0, 1), "resize_bilinear_bwd")
+    null_sweep(fn, ok(), (0, 1), "resize_bilinear_bwd")
     for bad in (dict(B=0), dict(C=0), dict(h=0), dict(w=-1), dict(H=0), dict(W=0)):
         assert fn(*ok(**bad)) == -2, bad
     assert fn(*ok(gc=N - 1)) == -2 and b"overlap" in L.ts_last_error_string()

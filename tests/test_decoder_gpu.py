@@ -11,7 +11,6 @@ Bars, none taken from the code under test (the project's convention; the factor 
 Each case prints error / bar; with TS_DECODER_PARITY_FILE set the line is appended to that file (profiles/decoder_parity.txt is made so).
 """
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -20,6 +19,7 @@ import torch.nn as nn
 
 import decoder_ref as R
 import synth
+from compare import Parity, dev as _dev, gpu, same_bits, stage_bar
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
@@ -27,7 +27,8 @@ from temporalstereo_amd import layers
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
+P = Parity("TS_DECODER_PARITY_FILE")
+check, check_rel = P.check, P.check_rel
 #         tag        B  Cu   Cs   Cout  h  w   H   W
 LAYERS = {"ragged": (2, 12, 5, 20, 4, 7, 9, 13),            # nothing a multiple of a tile; the source seam inside a K chunk
           "deconv32_16": (1, 320, 160, 256, 2, 3, 3, 5),    # that layer's own widths, K = 4320
@@ -38,43 +39,6 @@ LAYERS = {"ragged": (2, 12, 5, 20, 4, 7, 9, 13),            # nothing a multiple
           "identity": (1, 4, 4, 16, 6, 6, 6, 6)}            # the resize is the identity
 LAYER_TAGS = tuple(LAYERS)
 FIXTURES = ("a", "b")
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_DECODER_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
-
-
-def check(name, got, want, bar):
-    err = float((got.double().cpu() - want.double().cpu()).abs().max())
-    report("%-64s max |err| %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def check_rel(name, got, want, ref, bar):
-    """relative L2 of got - want, in units of |ref|"""
-    err = float((got.double().cpu() - want.double().cpu()).norm() / ref.double().cpu().norm())
-    report("%-64s rel L2    %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def stage_bar(dev, peak):
-    return max(4.0 * dev, 16.0 * U * peak)
 
 
 # ------------------------------------------------------------------------------------------------------------------ one fused layer

@@ -12,39 +12,18 @@ Bars, those of tests/test_mbconv_cpu.py (argued there), with u = 2^-24:
 """
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
 import encoder_ref as R
+from compare import T, err, fp32_bar, fp32_rel_bar, null_sweep, rel_l2
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
 from temporalstereo_amd import layers
 
 MP = R.MEMORY_PERCENT
-U = 2.0 ** -24
-
-
-def fp32_bar(g, name):
-    return max(2.0 * float(g["dev_" + name]), 16.0 * U * float(g["max_" + name]))
-
-
-def fp32_rel_bar(g, name):
-    return max(2.0 * float(g["rel_" + name]), 1e-6)
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def err(a, b):
-    return float((a.double() - b.double()).abs().max())
-
-
-def rel_l2(a, b, ref):
-    return float((a.double() - b.double()).norm() / ref.double().norm())
 
 
 def own_net(tag, seed, dtype=torch.float32, training=False):
@@ -360,14 +339,6 @@ def test_drop_path_in_train_mode_takes_the_reference_route():
     assert y.shape == x.shape
 
 
-def _sweep(fn, args, pointers, what):
-    """every required pointer NULL in turn -> TS_ERR_NULL"""
-    for i in pointers:
-        a = list(args)
-        a[i] = None
-        assert fn(*a) == -1 and b"NULL" in _lib.lib().ts_last_error_string(), (what, i)
-
-
 def test_abi_version_and_argument_checks():
     L = _lib.lib()
     assert L.ts_version() >= 23
@@ -383,7 +354,7 @@ def test_abi_version_and_argument_checks():
     assert L.ts_conv3x3_s_weight_bytes(513, 8, 1) == 0 and L.ts_conv3x3_s_weight_bytes(129, 8, 2) == 0 and L.ts_conv3x3_s_weight_bytes(8, 513, 1) == 0
     assert L.ts_conv3x3_s_weight_bytes(8, 8, 3) == 0 and L.ts_conv3x3_s_weight_bytes(0, 8, 1) == 0
     fn = L.ts_conv3x3_s_weight_layout
-    _sweep(fn, (one, one, 24, 96, 2, None), (0, 1), "conv3x3_s_weight_layout")
+    null_sweep(fn, (one, one, 24, 96, 2, None), (0, 1), "conv3x3_s_weight_layout")
     assert fn(one, one, 0, 96, 1, None) == -2 and fn(one, one, 24, -1, 1, None) == -2 and fn(one, one, 24, 96, 3, None) == -2
     assert fn(one, one, 513, 96, 1, None) == -3 and fn(one, one, 129, 96, 2, None) == -3 and fn(one, one, 24, 513, 1, None) == -3
     assert fn(one, one + 4, 24, 96, 1, None) == -4
@@ -403,7 +374,7 @@ def test_abi_version_and_argument_checks():
         yb = Cout * yc if yb is None else yb
         return (x, w_l, scale, shift, res, y, B, Cin, Cout, H, W, stride, act, xb, xc, rb, rcs, yb, yc, None)
     for stride in (1, 2):
-        _sweep(fn, ok(stride=stride), (0, 1, 5), "conv3x3_s_fwd")
+        null_sweep(fn, ok(stride=stride), (0, 1, 5), "conv3x3_s_fwd")
         assert fn(*ok(stride=stride, w_l=one + 4, scale=None, shift=None)) == -4           # optional pointers: on to the alignment of w_l
     assert fn(*ok(res=one, w_l=one + 4)) == -4                                             # a residual at stride 1 is taken ...
     assert fn(*ok(res=one, stride=2)) == -2 and b"stride 1 only" in L.ts_last_error_string()            # ... at stride 2 refused
@@ -435,7 +406,7 @@ def test_abi_version_and_argument_checks():
         rb = Cout * rcs if rb is None else rb
         yb = Cout * yc if yb is None else yb
         return (x, w_l, scale, shift, res, y, B, Cmid, Cout, H, W, xb, xc, rb, rcs, yb, yc, None)
-    _sweep(fn, ok(), (0, 1, 5), "fused_project_fwd")
+    null_sweep(fn, ok(), (0, 1, 5), "fused_project_fwd")
     assert fn(*ok(w_l=one + 4, scale=None, shift=None, res=None)) == -4
     for bad in (dict(B=0), dict(Cmid=0), dict(Cout=0), dict(H=-1), dict(W=0)):
         assert fn(*ok(**bad)) == -2, bad

@@ -11,7 +11,6 @@ Bars, those of tests/test_mbconv_gpu.py unchanged; none is taken from the code u
 Each case prints error / bar; with TS_ENCODER_PARITY_FILE set the line is appended to that file (profiles/encoder_parity.txt is made so).
 """
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -21,6 +20,7 @@ import torch.nn.functional as F
 
 import encoder_ref as R
 import synth
+from compare import Parity, dev as _dev, gpu, same_bits, stage_bar
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
@@ -28,55 +28,11 @@ from temporalstereo_amd import layers
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
+P = Parity("TS_ENCODER_PARITY_FILE", width=72)
+check, check_rel, against_fp64 = P.check, P.check_rel, P.against_fp64
 MP = R.MEMORY_PERCENT
 PLANES = ((1, 1), (1, 5), (5, 1), (2, 2), (5, 7), (6, 8), (3, 70), (40, 3), (9, 66))
 WIDTHS = ((3, 8), (12, 24), (24, 40), (48, 192))          # (Cin, Cout): 40 is no multiple of 16, 192 is more than one row group
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_ENCODER_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
-
-
-def check(name, got, want, bar):
-    err = float((got.double().cpu() - want.double().cpu()).abs().max())
-    report("%-72s max |err| %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def check_rel(name, got, want, ref, bar):
-    """relative L2 of got - want, in units of |ref|"""
-    err = float((got.double().cpu() - want.double().cpu()).norm() / ref.double().cpu().norm())
-    report("%-72s rel L2    %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def stage_bar(dev, peak):
-    return max(4.0 * dev, 16.0 * U * peak)
-
-
-def against_fp64(name, got, fn, args):
-    """`got` against fn(*args) in fp64, the bar from fn in fp32 (both on the CPU)."""
-    w64 = fn(*[a.double() if torch.is_tensor(a) and a.is_floating_point() else a for a in args])
-    w32 = fn(*args)
-    check(name, got, w64, stage_bar(float((w32.double() - w64).abs().max()), float(w64.abs().max())))
-    return w64
 
 
 def t32(a):

@@ -21,17 +21,18 @@ Bars, none taken from the code under test:
   backward          bit-equal over two runs;  forward  bit-equal when replayed from a captured graph.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import flow_corr_ref as R
+from compare import Parity, dev as _dev, gpu, rel_l2, same_bits
 import temporalstereo_amd as ts
 
 pytestmark = pytest.mark.gpu
 
+report = Parity("TS_FLOW_PARITY_FILE").report
 #        tag  B  C   H   W   L  r
 SHAPES = {"a": (2, 6, 8, 11, 3, 2),        # batch stride; C no multiple of the MFMA step; ragged against every tile edge; 8x11 -> 4x5 -> 2x2, a dropped column
           "c": (1, 40, 4, 4, 2, 1),        # C past one staged chunk; last level 2x2, the smallest legal
@@ -42,30 +43,6 @@ SHAPES = {"a": (2, 6, 8, 11, 3, 2),        # batch stride; C no multiple of the 
 FIXTURES = ("a", "c", "e")
 TAGS = tuple(SHAPES)
 GRADS = ("fmap1", "fmap2", "coords")
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def rel_l2(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_FLOW_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
 
 
 def pixel_grid(B, H, W):

@@ -21,10 +21,12 @@ import torch
 
 import warp_ref as R
 import temporalstereo_amd as ts
+from compare import Parity, dev as _dev, gpu, rel_l2, same_bits
 from temporalstereo_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
+report = Parity("TS_WARP_PARITY_FILE").report
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MODES = ("disparity", "flow", "depth")
 PADS = ("zeros", "border", "reflection")
@@ -34,18 +36,6 @@ SHAPES = {"a": (2, 3, 7, 37, 7, 37, 3),          # batch stride, odd C, ragged q
           "c": (2, 1, 9, 13, 5, 21, 3),          # image size differs from motion size, single channel
           "d": (1, 8, 33, 130, 33, 130, 3),      # more rows than one workgroup covers, 130 = 4 * 32 + 2 (no fixture: warp_ref)
           "e": (1, 17, 5, 4, 5, 4, 4)}           # channel-chunk tail, minimal quad width
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return None if t is None else t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def geometry(rng, B, H, W, kdim, small=False):
@@ -110,14 +100,6 @@ def expectation(img, motion, mode, geo, interp, pad):
         if k != "flow_mask":
             dev[k] = float((s32[k].double() - s64[k]).abs().max())
     return o64, s64, dev
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_WARP_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
 
 
 def check_bar(name, got, want64, dev, floor):
@@ -257,13 +239,6 @@ def test_integer_disparities_shift_the_image():
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. gradients
-def rel_l2(a, b, keep=None):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    if keep is not None:
-        a, b = a * keep, b * keep
-    return float((a - b).norm() / b.norm().clamp_min(1e-300))
-
-
 def torch_grads(img, motion, mode, geo, interp, pad, gout, dtype, need_motion):
     cast = lambda t: None if t is None else t.to(dtype)
     i = img.detach().clone().to(dtype).requires_grad_(True)
@@ -320,11 +295,11 @@ def test_gradients_against_fp64_autograd(tag, mode, pad):
     gi64, gm64 = torch_grads(img, motion, mode, geo, "bilinear", pad, gout, torch.float64, True)
     gi32, gm32 = torch_grads(img, motion, mode, geo, "bilinear", pad, gout, torch.float32, True)
     bar_i = max(4 * rel_l2(gi32, gi64), 1e-6)
-    bar_m = max(4 * rel_l2(gm32, gm64, keep), 1e-6)
+    bar_m = max(4 * rel_l2(gm32, gm64, keep=keep), 1e-6)
     first = None
     for run in range(2 if (tag, mode, pad) == ("a", "flow", "zeros") else 1):
         gi, gm = hip_grads(img, motion, mode, geo, "bilinear", pad, gout, True)
-        ei, em = rel_l2(gi, gi64), rel_l2(gm, gm64, keep)
+        ei, em = rel_l2(gi, gi64), rel_l2(gm, gm64, keep=keep)
         report("grad %s %-9s %-10s img %.3e (bar %.3e, ratio %.3f)  motion %.3e (bar %.3e, ratio %.3f)"
                % (tag, mode, pad, ei, bar_i, ei / bar_i, em, bar_m, em / bar_m))
         assert gm.shape == motion.shape and ei <= bar_i and em <= bar_m

@@ -19,39 +19,17 @@ The fp64 comparisons keep the decoder's bars as they are.
 """
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
 import mbconv_ref as R
+from compare import T, err, fp32_bar, fp32_rel_bar, null_sweep, rel_l2
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
 
 MP = R.MEMORY_PERCENT
-U = 2.0 ** -24
-
-
-def fp32_bar(g, name):
-    """an fp32 run against fp64 (the docstring)"""
-    return max(2.0 * float(g["dev_" + name]), 16.0 * U * float(g["max_" + name]))
-
-
-def fp32_rel_bar(g, name):
-    return max(2.0 * float(g["rel_" + name]), 1e-6)
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def err(a, b):
-    return float((a.double() - b.double()).abs().max())
-
-
-def rel_l2(a, b, ref):
-    return float((a.double() - b.double()).norm() / ref.double().norm())
 
 
 def own_stage(tag, seed, dtype=torch.float32, training=False):
@@ -333,14 +311,6 @@ def test_memory_and_operands_that_do_not_fit_the_input_raise():
                        wide.se.conv_reduce.bias, wide.se.conv_expand.weight, wide.se.conv_expand.bias, wide.conv_pwl.weight, fold(516))
 
 
-def _sweep(fn, args, required, what):
-    """NULL in every required pointer position -> -1."""
-    for i in required:
-        a = list(args)
-        a[i] = None
-        assert fn(*a) == -1 and b"NULL" in _lib.lib().ts_last_error_string(), (what, i)
-
-
 def test_abi_version_and_argument_checks():
     L = _lib.lib()
     assert L.ts_version() >= 24
@@ -355,7 +325,7 @@ def test_abi_version_and_argument_checks():
     assert L.ts_mbconv_weight_bytes(160, 960) % 16 == 0
     assert L.ts_mbconv_weight_bytes(2049, 8) == 0 and L.ts_mbconv_weight_bytes(8, 2049) == 0 and L.ts_mbconv_weight_bytes(0, 8) == 0
     fn = L.ts_mbconv_weight_layout
-    _sweep(fn, (one, one, 17, 20, None), (0, 1), "weight_layout")
+    null_sweep(fn, (one, one, 17, 20, None), (0, 1), "weight_layout")
     assert fn(one, one, 0, 20, None) == -2 and fn(one, one, 17, -1, None) == -2
     assert fn(one, one, 2049, 20, None) == -3 and fn(one, one, 17, 2049, None) == -3
     assert fn(one, one + 4, 17, 20, None) == -4
@@ -373,7 +343,7 @@ def test_abi_version_and_argument_checks():
         ib = C * ics if ib is None else ib
         yb = Cmid * yc if yb is None else yb
         return (memory, inp, w_l, scale, shift, y, B, C, mc, Cmid, H, W, mb, mcs, ib, ics, yb, yc, None)
-    _sweep(fn, ok(), (1, 2, 5), "expand_fwd")
+    null_sweep(fn, ok(), (1, 2, 5), "expand_fwd")
     for kw in (dict(scale=None, shift=None), dict(memory=None), dict(memory=None, mb=0, mcs=0)):      # optional pointers: on to the alignment of w_l
         assert fn(*ok(w_l=one + 4, **kw)) == -4, kw
     for bad in (dict(B=0), dict(C=0), dict(Cmid=-1), dict(H=0), dict(W=0), dict(mc=-1), dict(mc=25)):
@@ -405,7 +375,7 @@ def test_abi_version_and_argument_checks():
         rb = C * rcs if rb is None else rb
         yb = C * yc if yb is None else yb
         return (x, gate, w_l, scale, shift, res, y, B, Cmid, C, H, W, xb, xc, rb, rcs, yb, yc, None)
-    _sweep(fn, ok(), (0, 1, 2, 5, 6), "project_fwd")
+    null_sweep(fn, ok(), (0, 1, 2, 5, 6), "project_fwd")
     assert fn(*ok(w_l=one + 4, scale=None, shift=None)) == -4
     for bad in (dict(B=0), dict(C=0), dict(Cmid=0), dict(H=-1), dict(W=0)):
         assert fn(*ok(**bad)) == -2, bad
@@ -434,7 +404,7 @@ def test_abi_version_and_argument_checks():
         xb = C * xc if xb is None else xb
         yb = C * yc if yb is None else yb
         return (x, w, scale, shift, y, sums, B, C, H, W, act, flip, xb, xc, yb, yc, None)
-    _sweep(fn, ok(), (0, 1, 4), "depthwise3x3_fwd")
+    null_sweep(fn, ok(), (0, 1, 4), "depthwise3x3_fwd")
     for bad in (dict(B=0), dict(C=0), dict(H=0), dict(W=-3), dict(act=2), dict(act=-1), dict(flip=2), dict(flip=-1)):
         assert fn(*ok(**bad)) == -2, bad
     assert fn(*ok(xc=N - 1)) == -2 and b"overlap" in L.ts_last_error_string()
@@ -449,7 +419,7 @@ def test_abi_version_and_argument_checks():
     # ts_depthwise3x3_bwd_weight(x, dy, dw, B, C, H, W, x_bs, x_cs, dy_bs, dy_cs, stream)
     fn = L.ts_depthwise3x3_bwd_weight
     ok = lambda B=2, C=12, H=9, W=13, xb=12 * N, xc=N, gb=12 * N, gc=N: (one, one, one, B, C, H, W, xb, xc, gb, gc, None)
-    _sweep(fn, ok(), (0, 1, 2), "depthwise3x3_bwd_weight")
+    null_sweep(fn, ok(), (0, 1, 2), "depthwise3x3_bwd_weight")
     for bad in (dict(B=0), dict(C=-1), dict(H=0), dict(W=0)):
         assert fn(*ok(**bad)) == -2, bad
     assert fn(*ok(xc=N - 1)) == -2 and b"overlap" in L.ts_last_error_string()
@@ -459,7 +429,7 @@ def test_abi_version_and_argument_checks():
     # ts_se_gate_fwd(plane_sum, w_reduce, b_reduce, w_expand, b_expand, gate, B, Cmid, Cr, inv_hw, stream)
     fn = L.ts_se_gate_fwd
     ok = lambda B=2, Cmid=96, Cr=6: (one, one, one, one, one, one, B, Cmid, Cr, 0.25, None)
-    _sweep(fn, ok(), (0, 1, 2, 3, 4, 5), "se_gate_fwd")
+    null_sweep(fn, ok(), (0, 1, 2, 3, 4, 5), "se_gate_fwd")
     for bad in (dict(B=0), dict(Cmid=0), dict(Cr=-1)):
         assert fn(*ok(**bad)) == -2, bad
     assert fn(*ok(Cmid=2049)) == -3 and fn(*ok(Cr=513)) == -3 and fn(*ok(B=big)) == -3

@@ -12,7 +12,6 @@ tests/test_raft_corr_gpu.py):
 Each case prints error / bar; with TS_MBCONV_PARITY_FILE set the line is appended to that file (profiles/mbconv_parity.txt is made so).
 """
 import functools
-import os
 
 import numpy as np
 import pytest
@@ -22,6 +21,7 @@ import torch.nn.functional as F
 
 import mbconv_ref as R
 import synth
+from compare import Parity, dev as _dev, gpu, same_bits, stage_bar
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 from temporalstereo_amd import functional as TF
@@ -29,54 +29,10 @@ from temporalstereo_amd import layers
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
+P = Parity("TS_MBCONV_PARITY_FILE")
+check, check_rel, against_fp64 = P.check, P.check_rel, P.against_fp64
 MP = R.MEMORY_PERCENT
 PLANES = ((1, 1), (1, 5), (5, 1), (3, 70), (40, 3), (6, 8), (10, 72))      # the last two: rows staged in 16-byte pieces, one and two column tiles
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_MBCONV_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
-
-
-def check(name, got, want, bar):
-    err = float((got.double().cpu() - want.double().cpu()).abs().max())
-    report("%-64s max |err| %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def check_rel(name, got, want, ref, bar):
-    """relative L2 of got - want, in units of |ref|"""
-    err = float((got.double().cpu() - want.double().cpu()).norm() / ref.double().cpu().norm())
-    report("%-64s rel L2    %.3e  bar %.3e  err / bar %.3f" % (name, err, bar, err / bar))
-    assert err <= bar, name
-
-
-def stage_bar(dev, peak):
-    return max(4.0 * dev, 16.0 * U * peak)
-
-
-def against_fp64(name, got, fn, args):
-    """`got` against fn(*args) in fp64, the bar from fn in fp32 (both on the CPU)."""
-    w64 = fn(*[a.double() if torch.is_tensor(a) and a.is_floating_point() else a for a in args])
-    w32 = fn(*args)
-    check(name, got, w64, stage_bar(float((w32.double() - w64).abs().max()), float(w64.abs().max())))
-    return w64
 
 
 def t32(a):

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+from compare import dev as _dev, gpu
 from temporalstereo_amd import _lib, preprocess as pp
 
 pytestmark = pytest.mark.gpu
@@ -27,16 +28,8 @@ RESIZED = ("prepare_dataset_up", "prepare_video_up", "prepare_down", "prepare_de
 WITH_K = ("prepare_same", "prepare_dataset_up", "prepare_video_up", "prepare_down", "prepare_train_crop")
 
 
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def load(name):
     return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
-
-
-def gpu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
 
 
 def run_case(g, k, **kw):

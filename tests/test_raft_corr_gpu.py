@@ -17,17 +17,18 @@ Bars, none taken from the code under test:
   backward          bit-equal over two runs;  forward  bit-equal when replayed from a captured graph.
 """
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import raft_ref as R
+from compare import Parity, gpu, rel_l2, same_bits
 import temporalstereo_amd as ts
 
 pytestmark = pytest.mark.gpu
 
+report = Parity("TS_RAFT_PARITY_FILE").report
 #        tag  B  C   H   W   L  r
 SHAPES = {"a": (2, 6, 3, 37, 4, 4),        # batch stride; C no multiple of the MFMA K step; W ragged against 16; 37 -> 18 -> 9 -> 4
           "b": (1, 5, 2, 66, 4, 4),        # two columns past one 64-pixel strip; 66 -> 33 -> 16 -> 8
@@ -37,30 +38,6 @@ SHAPES = {"a": (2, 6, 3, 37, 4, 4),        # batch stride; C no multiple of the 
           "f": (1, 3, 2, 9, 1, 4)}         # single level; window wider than the row (no fixture)
 FIXTURES = ("a", "b", "c", "e")
 TAGS = tuple(SHAPES)
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def rel_l2(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_RAFT_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
 
 
 def off_the_kinks(disp, rng, W, L, r):

@@ -7,28 +7,16 @@ fp64 run stands, so it lies within dev_* (+ 1e-9) of the stored fp32 values; an 
 which is the reference's op sequence) is a second fp32 run: within 4 x dev_* of the stored one (twice would be the triangle inequality if
 both had the same deviation; the factor 4 as in tests/test_raft_corr_gpu.py).  Gradients: relative L2 <= 4 x rel_grad_* + 1e-6.
 """
-import numpy as np
 import pytest
 import torch
 
 import spp3d_ref as R
+from compare import T, err, rel_l2
 import temporalstereo_amd as ts
 from temporalstereo_amd import _lib
 
 FIXTURES = ("a", "b", "c", "d")
 STRIDES = (2, 4, 8, 16)
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def err(a, b):
-    return float((a.double() - b.double()).abs().max())
-
-
-def rel_l2(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm())
 
 
 @pytest.mark.parametrize("tag", FIXTURES)

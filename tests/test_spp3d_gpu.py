@@ -24,7 +24,6 @@ Each case prints error / bar; with TS_SPP3D_PARITY_FILE set the line is appended
 """
 import functools
 import math
-import os
 
 import numpy as np
 import pytest
@@ -32,12 +31,14 @@ import torch
 import torch.nn.functional as F
 
 import spp3d_ref as R
+from compare import U, Parity, dev as _dev, gpu, rel_l2, same_bits
 import temporalstereo_amd as ts
 from temporalstereo_amd import functional as TF
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
+P = Parity("TS_SPP3D_PARITY_FILE", width=44)
+report, check = P.report, P.check
 STRIDES = (2, 4, 8, 16)
 #        tag  B  C   D   H   W   training
 SHAPES = {"a": (2, 8, 5, 6, 7, True),          # clamped boxes that are no multiples, dropped plane and column, one-cell levels, batch stride
@@ -49,39 +50,6 @@ SHAPES = {"a": (2, 8, 5, 6, 7, True),          # clamped boxes that are no multi
 #                                                  train mode refuses it (asserted below), as the reference does; values and gradients in eval mode
 FIXTURES = ("a", "b", "c", "d")
 TAGS = tuple(SHAPES)
-
-
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def gpu(t):
-    return t.to(_dev())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def rel_l2(a, b):
-    return float((a.double().cpu() - b.double().cpu()).norm() / b.double().cpu().norm())
-
-
-def report(line):
-    print(line)
-    path = os.environ.get("TS_SPP3D_PARITY_FILE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
-
-
-def check(name, got, want, bar):
-    """max over the elements of |got - want| / bar <= 1 (bar a scalar or a tensor)."""
-    err = (got.double().cpu() - want.double().cpu()).abs()
-    bar = torch.as_tensor(bar, dtype=torch.float64)
-    ratio = float((err / bar).max()) if bar.numel() > 1 else float(err.max()) / float(bar)
-    report("%-44s max |err| %.3e  bar %.3e  err / bar %.3f" % (name, float(err.max()), float(bar.max()), ratio))
-    assert ratio <= 1.0, name
 
 
 @functools.lru_cache(maxsize=None)

@@ -28,21 +28,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from benchlegs.k1 import stream_ceilings  # noqa: E402
 from temporalstereo_amd import augment as ag, preprocess as pp  # noqa: E402
+from timing import timed  # noqa: E402
 
 SRC, WIN = (540, 960), (512, 960)
-
-
-def timed(fn, iters, rounds=5):
-    per = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return sorted(per)[len(per) // 2], min(per)
 
 
 def mix(name, B, dev, size=WIN):
@@ -105,23 +93,23 @@ def main():
         lines.append("B = %d" % B)
         fn = lambda: pp.prepare_frames(L, Rt, size=WIN, crop=crop)
         fn(); torch.cuda.synchronize()
-        ref = timed(fn, args.iters)
+        ref = timed([fn], args.iters, warmup=0)[0][:2]
         lines.append("  prepare_frames(size, crop)            %8.1f us (%.1f)" % ref)
         for name in ("none", "no hue", "all"):
             a = mix(name, B, dev)
             fn = lambda: ag.augment_frames(L, Rt, a, WIN)
             fn(); torch.cuda.synchronize()
-            t = timed(fn, args.iters)
+            t = timed([fn], args.iters, warmup=0)[0][:2]
             fb = lambda: ag.prepare_train_batch(L, Rt, kn, base, WIN, a, disp_gt_raw=raw)
             fb(); torch.cuda.synchronize()
-            tb = timed(fb, args.iters)
+            tb = timed([fb], args.iters, warmup=0)[0][:2]
             lines.append("  augment_frames  %-8s              %8.1f us (%.1f)  %.2f x prepare_frames  %8.0f images/s%s" % (
                 (name,) + t + (t[0] / ref[0], 2 * B / (t[0] * 1e-6), ("  = %.0f x the host chain" % (2 * B / (t[0] * 1e-6) * host / 1e3)) if host else "")))
             lines.append("  prepare_train_batch %-8s          %8.1f us (%.1f)" % ((name,) + tb))
         a = mix("contrast last", B, dev, size=(4, 4))
         fn = lambda: ag.augment_frames(L, Rt, a, (4, 4))
         fn(); torch.cuda.synchronize()
-        t = timed(fn, args.iters)
+        t = timed([fn], args.iters, warmup=0)[0][:2]
         nbytes = 2 * B * SRC[0] * SRC[1] * 3
         ceil = list(stream_ceilings(dev, [2 * nbytes]).values())[0]["copy"]
         lines.append("  (b) statistics launch (4x4 window, contrast last) %8.1f us (%.1f): %.2f MB of frames read, %.0f GB/s = %.2f of the copy "

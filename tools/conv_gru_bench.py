@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import temporalstereo_amd as ts  # noqa: E402
 from temporalstereo_amd import _lib, layers  # noqa: E402
-from flow_corr_bench import span  # noqa: E402
+from timing import timed  # noqa: E402
 
 #          B  C   H    W
 SHAPES = [(1, 64, 68, 120), (4, 64, 68, 120), (1, 64, 136, 240), (4, 64, 136, 240), (1, 32, 272, 480)]
@@ -81,18 +81,6 @@ def legs_of(step, m, h, x, cot):
                 o = step(o, x)
             return o
     return (forward, both, chain)
-
-
-def timed(fns, iters, reps=5):
-    for _ in range(3):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    per = [[] for _ in fns]
-    for _ in range(reps):
-        for p, fn in zip(per, fns):
-            p.append(span(fn, iters))
-    return [(sorted(p)[reps // 2], min(p), max(p)) for p in per]
 
 
 def trace_run(dev):

@@ -26,40 +26,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import temporalstereo_amd as ts  # noqa: E402
-from temporalstereo_amd import _lib, layers  # noqa: E402
+from temporalstereo_amd import _lib  # noqa: E402
 from temporalstereo_amd import functional as TF  # noqa: E402
-from flow_corr_bench import span  # noqa: E402
+from timing import cell, timed, torch_backend  # noqa: E402
 
 PLANES = {"x32": (17, 30), "x16": (34, 60), "x8": (68, 120), "x4": (136, 240)}
 #          layer            up source  skip   (None: the plain form on the previous layer's output)
 LAYERS = [("conv32", None, "x32"), ("deconv32_16.0", "x32", "x16"), ("deconv32_16.1", None, "x16"), ("deconv16_8.0", "x16", "x8"),
           ("deconv16_8.1", None, "x8"), ("deconv8_4.0", "x8", "x4"), ("deconv8_4.1", None, "x4")]
-
-
-def timed(fns, iters, reps):
-    for _ in range(3):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    per = [[] for _ in fns]
-    for _ in range(reps):
-        for p, fn in zip(per, fns):
-            p.append(span(fn, iters))
-    return [(sorted(p)[reps // 2], min(p), max(p)) for p in per]
-
-
-def cell(t):
-    return "%10.1f (%8.1f ..%8.1f)" % t if t is not None else "%32s" % "-"
-
-
-def torch_backend(fn):
-    def run(*a):
-        layers.set_conv_backend("torch")
-        try:
-            return fn(*a)
-        finally:
-            layers.set_conv_backend("hip")
-    return run
 
 
 def conv_of(m, name):

@@ -26,7 +26,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import temporalstereo_amd as ts  # noqa: E402
 from temporalstereo_amd import functional as TF  # noqa: E402
-from decoder_bench import cell, timed, torch_backend  # noqa: E402
+from timing import cell, timed, torch_backend  # noqa: E402
 
 
 def rows():

@@ -20,6 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import synth  # noqa: E402
 from temporalstereo_amd import validation_metrics  # noqa: E402
+from timing import timed  # noqa: E402
 
 H, W = 544, 960
 LEVELS = [(H, W), (H // 4, W // 4), (H // 4, W // 4), (H // 8, W // 8)]
@@ -77,32 +78,13 @@ def main():
     for B in (1, 4):
         gl, gr, ests = scene(B, synth.SEED0 + 900 + B)
         dgl, dgr, dests = gl.to(dev), gr.to(dev), [e.to(dev) for e in ests]
-        for _ in range(20):
-            validation_metrics(dests, dgl, dgr)
-        torch.cuda.synchronize()
-        per = []
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.iters):
-                validation_metrics(dests, dgl, dgr)
-            e1.record()
-            torch.cuda.synchronize()
-            per.append(e0.elapsed_time(e1) * 1000.0 / args.iters)
+        eager = timed([lambda: validation_metrics(dests, dgl, dgr)], args.iters, warmup=20)[0]
         # device time alone: the two launches recorded once and replayed as a plan (no Python between them)
         from temporalstereo_amd import _lib
         with _lib.Recorder() as rec:
             validation_metrics(dests, dgl, dgr)
         torch.cuda.synchronize()
-        rep = []
-        for _ in range(5):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.iters):
-                rec.run()
-            e1.record()
-            torch.cuda.synchronize()
-            rep.append(e0.elapsed_time(e1) * 1000.0 / args.iters)
+        replay = timed([rec.run], args.iters, warmup=0)[0]
         cpu_log_metric(ests, gl, gr)
         cpu = []
         for _ in range(3):
@@ -110,8 +92,8 @@ def main():
             cpu_log_metric(ests, gl, gr)
             cpu.append((time.perf_counter() - t0) * 1e6)
         med = lambda v: sorted(v)[len(v) // 2]
-        lines.append("B=%d  (a) validation_metrics eager call  %8.1f us/call (median of 5 x %d; min %.1f)" % (B, med(per), args.iters, min(per)))
-        lines.append("B=%d  (a) same launches, plan replay    %8.1f us/call (median of 5 x %d; min %.1f)" % (B, med(rep), args.iters, min(rep)))
+        lines.append("B=%d  (a) validation_metrics eager call  %8.1f us/call (median of 5 x %d; min %.1f)" % (B, eager[0], args.iters, eager[1]))
+        lines.append("B=%d  (a) same launches, plan replay    %8.1f us/call (median of 5 x %d; min %.1f)" % (B, replay[0], args.iters, replay[1]))
         lines.append("B=%d  (b) reference semantics, CPU      %8.1f us/call (median of 3; min %.1f)" % (B, med(cpu), min(cpu)))
     text = "\n".join(lines) + "\n"
     print(text, end="")

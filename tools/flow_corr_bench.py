@@ -23,49 +23,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import flow_corr_ref as R  # noqa: E402
 import temporalstereo_amd as ts  # noqa: E402
-from temporalstereo_amd import _lib  # noqa: E402
+from timing import ceilings, timed  # noqa: E402
 
 SHAPES = [(1, 80, 24, 78), (1, 80, 48, 156), (4, 80, 24, 78)]
 L, RAD = 4, 4
-
-
-def span(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1000.0 / iters
-
-
-def timed_pair(fa, fb, iters, reps=5):
-    """(median, min) of fa and of fb, us per call; the two alternate within every repetition"""
-    for _ in range(3):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    pa, pb = [], []
-    for _ in range(reps):
-        pa.append(span(fa, iters))
-        pb.append(span(fb, iters))
-    return (sorted(pa)[reps // 2], min(pa), max(pa)), (sorted(pb)[reps // 2], min(pb), max(pb))
-
-
-def ceilings(dev):
-    """bytes per second of a 256 MiB device fill (written) and copy (read + written)"""
-    n = 256 << 20
-    a, b = torch.empty(n, device=dev, dtype=torch.uint8), torch.zeros(n, device=dev, dtype=torch.uint8)
-    lib, st = _lib.lib(), _lib.current_stream_handle()
-    out = []
-    for kind, mult in ((0, 1.0), (1, 2.0)):
-        fn = lambda: lib.ts_calib_stream(kind, a.data_ptr(), b.data_ptr(), n, st)
-        for _ in range(5):
-            fn()
-        torch.cuda.synchronize()
-        per = sorted(span(fn, 20) for _ in range(5))
-        out.append(mult * n / (per[2] * 1e-6))
-    return out
 
 
 def main():
@@ -129,7 +90,7 @@ def main():
                 ("build + lookup", nograd(lambda: ts.FlowCorrBlock(f1, f2, L, RAD)(coords)), nograd(lambda: R.flow_corr_block(f1, f2, coords, L, RAD))),
                 ("build + lookup + backward", train_a, train_b)]
         for leg, fa, fb in legs:
-            ta, tb = timed_pair(fa, fb, args.iters)
+            ta, tb = timed([fa, fb], args.iters)
             extra = ""
             if leg == "build":
                 nbytes = 4.0 * (B * H * W * sum((H >> i) * (W >> i) for i in range(L)) + 2 * B * C * H * W)

@@ -28,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import flow_frame_ref as R  # noqa: E402
 import synth  # noqa: E402
 from temporalstereo_amd import _lib, flow_validation_metrics, make_color_wheel, render_flow_frame  # noqa: E402
+from timing import timed  # noqa: E402
 
 H, W = 544, 960
 LEVELS = [(H, W), (H // 4, W // 4), (H // 4, W // 4), (H // 8, W // 8)]
@@ -104,22 +105,6 @@ def cpu_render(est, gt):
     return out, R.q8(R.class_colors(R.err_class(f, gt)))
 
 
-def gpu_time(fn, iters, reps=5):
-    for _ in range(10):
-        fn()
-    torch.cuda.synchronize()
-    per = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return sorted(per)[len(per) // 2], min(per)
-
-
 def cpu_time(fn, reps=3):
     fn()
     per = []
@@ -152,12 +137,12 @@ def main():
                 ("render ", lambda: render_flow_frame(dests[1], dgt), lambda: torch_render(dests[1], dgt, wheel, lo, rgb),
                  lambda: cpu_render(ests[1].numpy(), gt.numpy())))
         for name, ours, framework, cpu in work:
-            a = gpu_time(ours, args.iters)
+            a = timed([ours], args.iters, warmup=10)[0]
             with _lib.Recorder() as rec:
                 ours()
             torch.cuda.synchronize()
-            b = gpu_time(rec.run, args.iters)
-            c = gpu_time(framework, max(args.iters // 10, 5))
+            b = timed([rec.run], args.iters, warmup=10)[0]
+            c = timed([framework], max(args.iters // 10, 5), warmup=10)[0]
             d = cpu_time(cpu)
             lines.append("B=%d %s (a) eager call                 %9.1f us/call (median of 5 x %d; min %.1f)" % (B, name, a[0], args.iters, a[1]))
             lines.append("B=%d %s (b) same launches, plan replay %9.1f us/call (median of 5 x %d; min %.1f)" % (B, name, b[0], args.iters, b[1]))

@@ -19,21 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from temporalstereo_amd import functional as TF  # noqa: E402
 from temporalstereo_amd.aggregation import native as N  # noqa: E402
+from timing import timed  # noqa: E402
 
 LEVELS = {"fine": (128, 16, 68, 120, 5), "precise": (128, 8, 136, 240, 5)}
-
-
-def timed(fn, iters):
-    for _ in range(10):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3
 
 
 def main():
@@ -44,6 +32,7 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
+    us = lambda fn: timed([fn], a.iters, reps=1, warmup=10)[0][0]            # one span after ten untimed calls
     for B in a.batches:
         for name, (C, cout, H, W, D) in LEVELS.items():
             torch.manual_seed(0)
@@ -59,17 +48,17 @@ def main():
             lterm = N.conv_hw(left.unsqueeze(2), fl, 1, 1)
             Q = N.conv_d(right.unsqueeze(2), q, 1).squeeze(2)
             t = {}
-            t["k1_warped"] = timed(lambda: TF.block_cost_warped(left, right, disp, 3), a.iters)
+            t["k1_warped"] = us(lambda: TF.block_cost_warped(left, right, disp, 3))
             vol = TF.block_cost_warped(left, right, disp, 3)
-            t["conv_rest"] = timed(lambda: N.conv_hw(vol, rest, 1, 1, addend=lterm), a.iters)
-            t["materialised"] = timed(lambda: N.conv_hw(TF.block_cost_warped(left, right, disp, 3), rest, 1, 1, addend=lterm), a.iters)
-            t["k1_corr"] = timed(lambda: N.block_cost_corr(left, right, disp, 3), a.iters)
+            t["conv_rest"] = us(lambda: N.conv_hw(vol, rest, 1, 1, addend=lterm))
+            t["materialised"] = us(lambda: N.conv_hw(TF.block_cost_warped(left, right, disp, 3), rest, 1, 1, addend=lterm))
+            t["k1_corr"] = us(lambda: N.block_cost_corr(left, right, disp, 3))
             cv = N.block_cost_corr(left, right, disp, 3)
-            t["conv_warp"] = timed(lambda: N.conv_hw_warp(cv, corr, Q, disp, lterm.squeeze(2), 1), a.iters)
-            t["conv_corr_only"] = timed(lambda: N.conv_hw(cv, corr, 1, 1, addend=lterm), a.iters)
-            t["q_1x1"] = timed(lambda: N.conv_d(right.unsqueeze(2), q, 1), a.iters)
-            t["left_term"] = timed(lambda: N.conv_hw(left.unsqueeze(2), fl, 1, 1), a.iters)
-            t["contracted"] = timed(lambda: N.conv_hw_warp(N.block_cost_corr(left, right, disp, 3), corr, Q, disp, lterm.squeeze(2), 1), a.iters)
+            t["conv_warp"] = us(lambda: N.conv_hw_warp(cv, corr, Q, disp, lterm.squeeze(2), 1))
+            t["conv_corr_only"] = us(lambda: N.conv_hw(cv, corr, 1, 1, addend=lterm))
+            t["q_1x1"] = us(lambda: N.conv_d(right.unsqueeze(2), q, 1))
+            t["left_term"] = us(lambda: N.conv_hw(left.unsqueeze(2), fl, 1, 1))
+            t["contracted"] = us(lambda: N.conv_hw_warp(N.block_cost_corr(left, right, disp, 3), corr, Q, disp, lterm.squeeze(2), 1))
             t["contracted_incl_q"] = t["contracted"] + t["q_1x1"]
             # the unfused op's algorithmic bytes over the time of the form that replaces it
             nb = 4 * B * H * W * (2 * C + D + (2 * C + 3 * C // 8) * D)

@@ -15,6 +15,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from temporalstereo_amd import _lib  # noqa: E402
+from timing import span  # noqa: E402
 
 LEVELS = {"coarse": (256, 34, 60, 12, False), "fine": (128, 68, 120, 5, True), "precise": (128, 136, 240, 5, True)}
 
@@ -62,13 +63,7 @@ def main():
                 for _ in range(20):
                     _lib.check(fn(), "k1")
                 torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(a.iters):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                t = e0.elapsed_time(e1) / a.iters * 1e-3
+                t = span(fn, a.iters) * 1e-6
                 nb = alg_bytes(B, C, H, W, D, kind)
                 row = dict(level=name, kind=kind, batch=B, us=t * 1e6, algorithmic_bytes=nb, GBps=nb / t / 1e9, frac_of_8TBps=nb / t / 8e12,
                            frac_of_6p29TBps=nb / t / 6.29e12)
@@ -91,14 +86,7 @@ def main():
                 for _ in range(5):
                     _lib.check(fn(), "k1 bwd")
                 torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                n = max(a.iters // 4, 10)
-                e0.record()
-                for _ in range(n):
-                    fn()
-                e1.record()
-                torch.cuda.synchronize()
-                t = e0.elapsed_time(e1) / n * 1e-3
+                t = span(fn, max(a.iters // 4, 10)) * 1e-6
                 nb = 4 * B * H * W * (4 * C + (2 * D if sampled else 0) + ctot * D)
                 rows.append(dict(level=name, kind="backward", batch=B, us=t * 1e6, algorithmic_bytes=nb, GBps=nb / t / 1e9, frac_of_8TBps=nb / t / 8e12))
                 print("K1 %-8s %-8s B=%d  %8.2f us  %8.1f MB  %7.1f GB/s  %.3f of 8.0 TB/s" % (name, "backward", B, t * 1e6, nb / 1e6, nb / t / 1e9, nb / t / 8e12), flush=True)

@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import temporalstereo_amd as ts  # noqa: E402
 from temporalstereo_amd import functional as TF  # noqa: E402
-from decoder_bench import cell, timed, torch_backend  # noqa: E402
+from timing import cell, timed, torch_backend  # noqa: E402
 
 #          C    Cmid  Cr   plane
 SHAPES = [(128, 512, 32, (34, 60)), (160, 960, 40, (34, 60)), (272, 1632, 68, (17, 30))]

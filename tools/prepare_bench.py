@@ -28,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import synth  # noqa: E402
 from benchlegs.k1 import stream_ceilings  # noqa: E402
 from temporalstereo_amd import _lib, preprocess as pp  # noqa: E402
+from timing import timed  # noqa: E402
 
 # (name, batch, source size, target size)
 GEOMETRIES = (("config 1", 1, (480, 640), (544, 960)), ("config 2", 4, (480, 640), (544, 960)),
@@ -42,19 +43,6 @@ def host_image(u8, size):
     if tuple(size) != tuple(u8.shape[:2]):
         proc = F.interpolate(proc.unsqueeze(dim=1), size=size, mode='bilinear', align_corners=True).squeeze(dim=1)
     return image, proc
-
-
-def timed(fn, iters, rounds=5):
-    per = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return sorted(per)[len(per) // 2], min(per)
 
 
 def wall(fn, rounds=5):
@@ -107,11 +95,11 @@ def main():
             for _ in range(20):
                 fn()
             torch.cuda.synchronize()
-            eager = timed(fn, args.iters)
+            eager = timed([fn], args.iters, warmup=0)[0]
             with _lib.Recorder() as rec:
                 fn()
             torch.cuda.synchronize()
-            plan = timed(rec.run, args.iters)
+            plan = timed([rec.run], args.iters, warmup=0)[0]
             in_bytes, out_bytes = 2 * B * 3 * s[0] * s[1], 2 * B * 3 * d[0] * d[1] * 4
             fill = list(stream_ceilings(dev, [out_bytes]).values())[0]["fill"]
             ach = (in_bytes + out_bytes) / (plan[0] * 1e-6)
@@ -127,7 +115,7 @@ def main():
         for _ in range(20):
             fn()
         torch.cuda.synchronize()
-        e2e = timed(fn, args.iters)
+        e2e = timed([fn], args.iters, warmup=0)[0]
         lines.append("  (e) prepare_batch (3 launches + allocations), eager   %8.1f us (median of 5 x %d; min %.1f)" % (e2e[0], args.iters, e2e[1]))
         lines.append("      (a)+(b) = %.1f us against (c)+(d) = %.1f us: %.0fx" % (t_host[0] + t_up32[0], t_up8[0] + kernel_us,
                                                                                  (t_host[0] + t_up32[0]) / (t_up8[0] + kernel_us)))

@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import raft_ref as R  # noqa: E402
 import temporalstereo_amd as ts  # noqa: E402
-from flow_corr_bench import ceilings, timed_pair  # noqa: E402
+from timing import ceilings, timed  # noqa: E402
 
 SHAPES = [(1, 32, 96, 312), (4, 32, 96, 312), (1, 64, 136, 240), (4, 64, 136, 240), (2, 128, 68, 120)]
 L, RAD = 4, 4
@@ -90,7 +90,7 @@ def main():
                 ("build + lookup", nograd(lambda: ts.CorrBlock(f1, f2, L, RAD)(disp)), nograd(lambda: R.corr_block(f1, f2, disp, L, RAD))),
                 ("build + lookup + backward", train_a, train_b)]
         for leg, fa, fb in legs:
-            ta, tb = timed_pair(fa, fb, args.iters)
+            ta, tb = timed([fa, fb], args.iters)
             extra = ""
             if leg == "build":
                 nbytes = 4.0 * (B * H * W * W * (2.0 - 2.0 ** -(L - 1)) + 2 * B * C * H * W)

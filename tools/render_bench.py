@@ -27,6 +27,7 @@ import synth  # noqa: E402
 from benchlegs.k1 import stream_ceilings  # noqa: E402
 from temporalstereo_amd import _lib, render_frame  # noqa: E402
 from temporalstereo_amd.visualization import jet_table  # noqa: E402
+from timing import timed  # noqa: E402
 
 H, W, LH, LW = 544, 960, 136, 240
 JET = jet_table().astype(np.float64)
@@ -78,19 +79,6 @@ def host_frame(est, gt):
     return disp_color, cls, np.concatenate((jet, legend), axis=0), (e * 256).astype('uint16')
 
 
-def timed(fn, iters, rounds=5):
-    per = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return sorted(per)[len(per) // 2], min(per)
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -109,11 +97,11 @@ def main():
             for _ in range(20):
                 fn()
             torch.cuda.synchronize()
-            eager = timed(fn, args.iters)
+            eager = timed([fn], args.iters, warmup=0)[0]
             with _lib.Recorder() as rec:
                 fn()
             torch.cuda.synchronize()
-            plan = timed(rec.run, args.iters)
+            plan = timed([rec.run], args.iters, warmup=0)[0]
             out_bytes = B * ((2 * H + H + H + 50) * W * 3 * size + H * W * 2)
             in_bytes = B * (H * W + LH * LW) * 4
             ceil = stream_ceilings(dev, [out_bytes])

@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import temporalstereo_amd as ts  # noqa: E402
-from flow_corr_bench import ceilings, timed_pair  # noqa: E402
+from timing import ceilings, timed  # noqa: E402
 
 SHAPES = [(1, 64, 48, 136, 240), (1, 32, 24, 68, 120), (4, 32, 24, 68, 120)]
 STRIDES = (2, 4, 8, 16)
@@ -111,7 +111,7 @@ def main():
                 ("module forward (eval)", module_eval(m), module_eval(m._reference_forward), None),
                 ("module forward + backward (train)", module_train(m), module_train(m._reference_forward), None)]
         for leg, fa, fb, nbytes in legs:
-            ta, tb = timed_pair(fa, fb, iters)
+            ta, tb = timed([fa, fb], iters)
             extra = "   %.0f %% of the copy ceiling" % (100.0 * nbytes / (ta[0] * 1e-6) / copy) if nbytes else ""
             if ta[0] > tb[0]:
                 losers.append("%s %s: HIP %.1f us against %.1f us (%.2f x slower)" % (name, leg, ta[0], tb[0], ta[0] / tb[0]))

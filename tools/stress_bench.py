@@ -17,21 +17,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import temporalstereo_amd as ts  # noqa: E402
+from timing import timed  # noqa: E402
 
 PEAK = 8.0e12
-
-
-def timed(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e-3
 
 
 def main():
@@ -39,6 +27,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    seconds = lambda fn: timed([fn], a.iters, reps=1)[0][0] * 1e-6          # one span after three untimed calls
     torch.manual_seed(0)
     rows = []
     with torch.no_grad():
@@ -48,14 +37,14 @@ def main():
             disp = torch.arange(D, device=dev, dtype=torch.float32).view(1, D, 1, 1).expand(B, D, H, W).contiguous()
             for name, fn, out_ch in (("cat_fms", lambda: ts.cat_fms(L, R, disp), 2 * C), ("dif_fms", lambda: ts.dif_fms(L, R, disp), C)):
                 nbytes = 4 * B * H * W * (2 * C + D + out_ch * D)
-                t = timed(fn, a.iters)
+                t = seconds(fn)
                 rows.append(dict(op=name, shape=[B, C, D, H, W], algorithmic_bytes=nbytes, mean_us=t * 1e6, achieved_GBps=nbytes / t / 1e9,
                                  frac_of_8TBps=nbytes / t / PEAK, note="dif_fms is two passes over the inputs (tensor-wide max first, dif_fms.py:38)" if name == "dif_fms" else ""))
         # native 1-D correlation (correlation.py:32-57): output [B, max_disp, H, W]; arithmetic intensity C MACs per output element
         for (B, C, D, H, W) in [(4, 32, 48, 136, 240), (8, 64, 192, 136, 240), (4, 32, 192, 272, 480)]:
             L, R = torch.randn(B, C, H, W, device=dev), torch.randn(B, C, H, W, device=dev)
             nbytes = 4 * B * H * W * (2 * C + D)
-            t = timed(lambda: ts.correlation1d(L, R, D), a.iters)
+            t = seconds(lambda: ts.correlation1d(L, R, D))
             rows.append(dict(op="correlation1d", shape=[B, C, D, H, W], algorithmic_bytes=nbytes, mean_us=t * 1e6, achieved_GBps=nbytes / t / 1e9,
                              frac_of_8TBps=nbytes / t / PEAK, flops=2.0 * B * C * D * H * W, tflops=2.0 * B * C * D * H * W / t / 1e12,
                              note="a band of the row's Gram matrix on the matrix cores (v_mfma_f32_16x16x4_f32: corr_row_mfma_kernel, csrc/correlation.hip)"))

@@ -23,24 +23,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import warp_ref as R  # noqa: E402
 import temporalstereo_amd as ts  # noqa: E402
 from temporalstereo_amd import _lib  # noqa: E402
+from timing import timed  # noqa: E402
 
 SHAPES = [(544, 960, 3), (136, 240, 32), (136, 240, 64)]
-
-
-def timed(fn, iters, reps=5):
-    for _ in range(10):
-        fn()
-    torch.cuda.synchronize()
-    per = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        per.append(e0.elapsed_time(e1) * 1000.0 / iters)
-    return sorted(per)[len(per) // 2], min(per)
 
 
 def copy_rate(dev):
@@ -50,7 +35,7 @@ def copy_rate(dev):
     a.zero_()
     L = _lib.lib()
     st = _lib.current_stream_handle()
-    med, _ = timed(lambda: L.ts_calib_stream(1, b.data_ptr(), a.data_ptr(), n, st), 20)
+    med = timed([lambda: L.ts_calib_stream(1, b.data_ptr(), a.data_ptr(), n, st)], 20, warmup=10)[0][0]
     return 2.0 * n / (med * 1e-6)
 
 
@@ -87,12 +72,12 @@ def main():
                 geo = (K, iK, T) if mode == "depth" else (None, None, None)
                 name = "B=%d C=%-2d %dx%d %-9s" % (B, C, H, W, mode)
                 # ---- forward
-                a = timed(lambda: ts.inverse_warp(img, motion, mode, *geo), args.iters)
+                a = timed([lambda: ts.inverse_warp(img, motion, mode, *geo)], args.iters, warmup=10)[0]
                 with _lib.Recorder() as rec:
                     ts.inverse_warp(img, motion, mode, *geo)
-                b = timed(rec.run, args.iters)
+                b = timed([rec.run], args.iters, warmup=10)[0]
                 with torch.no_grad():
-                    c = timed(lambda: R.inverse_warp(img, motion, mode, *geo), args.iters)
+                    c = timed([lambda: R.inverse_warp(img, motion, mode, *geo)], args.iters, warmup=10)[0]
                 nbytes = 4.0 * (img.numel() + motion.numel() + B * C * H * W)
                 lines.append("%-34s %8.1f (%5.1f) %8.1f (%5.1f) %8.1f (%5.1f) %8.2f %7.0f%%"
                              % (name + " fwd", a[0], a[1], b[0], b[1], c[0], c[1], c[0] / b[0], 100 * nbytes / (b[0] * 1e-6) / rate))
@@ -100,7 +85,7 @@ def main():
                 gout = torch.randn(B, C, H, W, device=dev)
                 i1, m1 = img.clone().requires_grad_(True), motion.clone().requires_grad_(True)
                 o1 = ts.inverse_warp(i1, m1, mode, *geo)
-                a = timed(lambda: torch.autograd.grad(o1, (i1, m1), gout, retain_graph=True), args.iters)
+                a = timed([lambda: torch.autograd.grad(o1, (i1, m1), gout, retain_graph=True)], args.iters, warmup=10)[0]
                 gi, gm = torch.zeros_like(img), torch.empty_like(motion)
                 p = _lib.ptr
                 kd = 3 if mode == "depth" else 0
@@ -109,10 +94,10 @@ def main():
                                                         H, W, 0 if mode == "disparity" else 2, 0, 0, kd, kd, 1e-7,
                                                         _lib.current_stream_handle())
                     _lib.check(rc, "ts_inverse_warp_bwd")
-                b = timed(rec.run, args.iters)
+                b = timed([rec.run], args.iters, warmup=10)[0]
                 i2, m2 = img.clone().requires_grad_(True), motion.clone().requires_grad_(True)
                 o2 = R.inverse_warp(i2, m2, mode, *geo)[0]
-                c = timed(lambda: torch.autograd.grad(o2, (i2, m2), gout, retain_graph=True), args.iters)
+                c = timed([lambda: torch.autograd.grad(o2, (i2, m2), gout, retain_graph=True)], args.iters, warmup=10)[0]
                 nbytes = 4.0 * (gout.numel() + 2 * img.numel() + 2 * motion.numel())
                 lines.append("%-34s %8.1f (%5.1f) %8.1f (%5.1f) %8.1f (%5.1f) %8.2f %7.0f%%"
                              % (name + " bwd", a[0], a[1], b[0], b[1], c[0], c[1], c[0] / b[0], 100 * nbytes / (b[0] * 1e-6) / rate))

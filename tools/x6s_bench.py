@@ -5,6 +5,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from temporalstereo_amd.aggregation import native as N
+from timing import span
 
 dev = torch.device("cuda:0")
 N._X6S_MIN_GRID = N._X6S_MIN_GRID_T3 = 1
@@ -41,14 +42,8 @@ for B in (1, 4):
             N.X6S = on
             for _ in range(5):
                 run()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(100):
-                r = run()
-            e1.record()
-            torch.cuda.synchronize()
-            t[on] = e0.elapsed_time(e1) * 10.0
-            outs[on] = (out if mode == N.X6S_T4 else r).clone()
+            t[on] = span(run, 100)
+            outs[on] = (out if mode == N.X6S_T4 else run()).clone()
         N.X6S = True
         err = float((outs[True] - outs[False]).abs().max()) / max(float(outs[False].abs().max()), 1.0)
         print("B=%d %-32s f32 %7.1f us (%5.1f TF)   x6s %7.1f us (%5.1f TF eq.)   x%.2f   max rel diff %.2e" %
